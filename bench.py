@@ -7,6 +7,7 @@ A "step" = one pass of the hot path over one batch: Terse-encode the resident 20
 region; nothing is cached between steps (outputs are re-produced every step).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its own N ranks, one per GPU)
+    python bench.py ... --dump-outputs DIR     (also writes what the last timed step computed: see dump_outputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (same, under a launcher)
 
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel,
@@ -38,6 +39,9 @@ DEC_STAGES_FRAMES = ["decode_frames", "deferred_frames"]  # one workgroup per fr
 # (k_chain_walk -- start states, walk and links in one launch --, k_chain_resolve, k_chain_index), then the other route's launch for listed frames
 # (k_seg_fallback, normally empty) + the extraction (k_unpack_tiles / k_decode_units_indexed / k_decode_parts)
 DEC_STAGES_LARGE = ["chain_walk_to_index", "fallback_and_extract"]
+DUMP_FRAMES = 32                       # --dump-outputs: frames whose encoded bytes and decoded pixels are written in full
+DUMP_SEED = 20240807
+DUMP_MAX_BYTES = 64 * 10**6
 
 
 def dec_stage_names(n_values):
@@ -101,6 +105,34 @@ def cpu_baseline(px_host: np.ndarray, cores: int):
     }
 
 
+def dump_outputs(dirname, out, offs, st_e, back, st_d):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float64 / float32 (every value
+    exact), at most DUMP_MAX_BYTES in all.  The encode's frame offsets and status words 0..1 (error code, prolix_bits) and the
+    decode's status word 0 in full; the encoded bytes and the decoded pixels of a fixed seeded set of frames (frame 0, the
+    last frame and DUMP_FRAMES - 2 between them, listed in sample_frames): the whole stack and its pixels are ~1.2 GB."""
+    frames = offs.numel() - 1
+    if frames <= DUMP_FRAMES:
+        pick = np.arange(frames)
+    else:
+        mid = np.random.default_rng(DUMP_SEED).choice(np.arange(1, frames - 1), DUMP_FRAMES - 2, replace=False)
+        pick = np.sort(np.concatenate([[0, frames - 1], mid]))
+    o = offs.cpu().numpy()
+    arrays = {
+        "frame_offsets": o.astype(np.float64),
+        "encode_status": st_e[:2].cpu().numpy().astype(np.float64),
+        "decode_status": st_d[:1].cpu().numpy().astype(np.float64),
+        "sample_frames": pick.astype(np.float64),
+        # the sampled frames' bytes one after the other (frame f: frame_offsets[f + 1] - frame_offsets[f] of them)
+        "sample_encoded_bytes": np.concatenate([out[int(o[f]): int(o[f + 1])].cpu().numpy() for f in pick]).astype(np.float32),
+        "sample_decoded_pixels": np.stack([back[int(f)].cpu().numpy() for f in pick]).astype(np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def rank_commands(n: int, port: int):
     """One (argv, env additions) pair per rank: this script again, with the rendezvous a launcher would have set."""
     argv = [sys.executable, os.path.abspath(__file__)] + [a for a in sys.argv[1:] if a != "--spawn-dry-run"]
@@ -162,7 +194,11 @@ def main():
                     help="N > 1: if the C-ABI RCCL size gather cannot be set up, exchange the sizes through torch.distributed instead of failing")
     ap.add_argument("--headline-only", action="store_true",
                     help="skip the informative legs (configs[3], noisy_u16, index decode): profiler passes see the headline kernels only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float32 / float64, <= 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher: this process becomes the launcher (it never touches the GPU)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -296,6 +332,9 @@ def main():
         if one_call:
             assert rccl_ranks == world and -int(ri[1].item()) == world and int(ri[2].item()) == 1, \
                 f"RCCL communicator spans {info[0]} ranks (rank {info[1]}) but the job has {world} (rank {rank})"
+
+    if args.dump_outputs and rank == 0:                      # (before anything below reuses the buffers)
+        dump_outputs(args.dump_outputs, out, offs, st_e, back, st_d)
 
     # ---- correctness of what was just timed (every rank) -----------------------------------
     assert int(st_e[0].item()) == 0 and int(st_d[0].item()) == 0, "device status reports an error"

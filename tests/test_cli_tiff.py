@@ -5,6 +5,7 @@ exists): small TIFF stacks, the .trpx the reference `terse` makes of each, and t
 (`*.expect.tif`; index.json records for which of them the reference `prolix` wrote exactly these bytes -- all but the
 3-frame stack, where the reference mislocates frames >= 2, defects D1/D2).
 """
+import hashlib
 import json
 import os
 import shutil
@@ -151,38 +152,45 @@ def _indexed_trpx(name):
 
 @pytest.mark.parametrize("name", ["u8_stack2_16x12", "u16_bigendian_24x24", "i16_single_17x9"])
 def test_reference_prolix_ignores_the_frame_index_attribute(name, tmp_path):
-    """CPU, only where the reference tools can be built (/root/reference): a .trpx file with the extra frame_sizes
-    and group_bit_offsets attributes expands with the REFERENCE `prolix` to the same TIFF as the plain file (stacks of <= 2 frames: the
-    reference mislocates later frames either way, D1/D2)."""
+    """CPU: a .trpx file with the extra frame_sizes and group_bit_offsets attributes expands with the REFERENCE `prolix` to
+    the same TIFF as the plain file (stacks of <= 2 frames: the reference mislocates later frames either way, D1/D2).
+    tests/golden/reference_runs.json holds the hashes of the file the reference was given and of the TIFF it wrote; where
+    oracle/_ref/prolix_cli is built in this checkout, the reference runs again."""
     indexed = _indexed_trpx(name)
+    run = _reference_runs()["prolix_cli"][name]
+    want = open(os.path.join(CLI, INDEX[name]["expect_tif"]), "rb").read()
+    assert _sha256(indexed) == run["trpx_sha256"]            # this file, byte for byte, is the one the reference expanded ...
+    assert run["tif_sha256"] == _sha256(want)                 # ... to the plain file's TIFF
     ref = _reference_prolix()
-    work = tmp_path / (name + ".trpx")
-    work.write_bytes(indexed)
-    subprocess.check_call([ref, str(work)], stdout=subprocess.DEVNULL)
-    assert (tmp_path / (name + ".tif")).read_bytes() == open(os.path.join(CLI, INDEX[name]["expect_tif"]), "rb").read()
+    if ref:
+        work = tmp_path / (name + ".trpx")
+        work.write_bytes(indexed)
+        subprocess.check_call([ref, str(work)], stdout=subprocess.DEVNULL)
+        assert (tmp_path / (name + ".tif")).read_bytes() == want
+
+
+def _sha256(b):
+    return hashlib.sha256(b).hexdigest()
+
+
+def _reference_runs():
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_runs.json")))
 
 
 def _reference_prolix():
+    """The reference `prolix` tool where `make -C oracle ref` built it (oracle/_ref/prolix_cli), else None."""
     ref = os.path.join(ROOT, "oracle", "_ref", "prolix_cli")
-    if not os.path.exists(ref):
-        if not os.path.isdir("/root/reference"):
-            pytest.skip("reference sources not available here")
-        os.makedirs(os.path.dirname(ref), exist_ok=True)
-        subprocess.check_call(["g++", "-std=c++20", "-O2", "-w", "-I/root/reference/include", "/root/reference/src/prolix.cpp",
-                               "-o", ref])
-    return ref
+    return ref if os.path.exists(ref) else None
 
 
-def test_reference_prolix_reads_a_file_with_many_group_states(tmp_path):
-    """CPU, where the reference tool can be built: two 200x160 u16 frames (2667 blocks = 11 groups each, a 22-token
-    group_bit_offsets attribute of several hundred characters) written with both index attributes expand with the
-    REFERENCE `prolix` to the original pixels -- the attributes are skipped like any unknown one (XML_element.hpp:296-307)."""
+def _many_group_states_file():
+    """Two 200x160 u16 frames (2667 blocks = 11 groups each) as a .trpx file with both index attributes, the
+    group_bit_offsets one of 22 tokens and several hundred characters: (pixels [2, 32000], file bytes)."""
     import ctypes as C
     import sys
     sys.path.insert(0, ROOT)
     from oracle import oracle as O
     from trpx_amd import _lib
-    ref = _reference_prolix()
     rng = np.random.RandomState(5)
     px = (rng.poisson(3.0, size=(2, 160 * 200)) * (rng.rand(2, 160 * 200) < 0.7)).astype(np.uint16)
     px[:, ::97] = 40000
@@ -197,10 +205,23 @@ def test_reference_prolix_reads_a_file_with_many_group_states(tmp_path):
     buf = C.create_string_buffer(1 << 14)
     n = _lib.lib().trpx_header_format_grouped(C.byref(h), s64.ctypes.data, 2, gs.ctypes.data, gs.size, buf, 1 << 14)
     assert n > 300
-    work = tmp_path / "many.trpx"
-    work.write_bytes(buf.raw[:n] + stream.tobytes())
-    subprocess.check_call([ref, str(work)], stdout=subprocess.DEVNULL)
-    assert (_parse_tiff(str(tmp_path / "many.tif")).reshape(2, -1) == px).all()
+    return px, buf.raw[:n] + stream.tobytes()
+
+
+def test_reference_prolix_reads_a_file_with_many_group_states(tmp_path):
+    """CPU: _many_group_states_file() expands with the REFERENCE `prolix` to the original pixels -- the attributes are
+    skipped like any unknown one (XML_element.hpp:296-307).  Checked against the hashes of the file the reference was given
+    and of the pixels it wrote (tests/golden/reference_runs.json), and live where oracle/_ref/prolix_cli is built."""
+    px, blob = _many_group_states_file()
+    run = _reference_runs()["prolix_cli"]["many_group_states"]
+    assert _sha256(blob) == run["trpx_sha256"]
+    assert run["pixels_sha256"] == _sha256(px.astype("<u2").tobytes())
+    ref = _reference_prolix()
+    if ref:
+        work = tmp_path / "many.trpx"
+        work.write_bytes(blob)
+        subprocess.check_call([ref, str(work)], stdout=subprocess.DEVNULL)
+        assert (_parse_tiff(str(tmp_path / "many.tif")).reshape(2, -1) == px).all()
 
 
 @pytest.mark.gpu

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +51,36 @@ def _bench(extra_env, *flags):
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float .npy files of at most 64 MB -- the frame offsets, prolix_bits
+    and the sampled frames' encoded bytes and decoded pixels equal to the CPU oracle's on the same synth-v1 frames."""
+    frames = 40                                           # more than bench.DUMP_FRAMES: the seeded sample is taken
+    b = _bench({}, "--steps", "2", "--warmup", "1", "--frames", str(frames), "--headline-only", "--no-cpu-baseline",
+               "--dump-outputs", str(tmp_path))
+    assert b["steps"] == 2
+    names = {"frame_offsets", "encode_status", "decode_status", "sample_frames", "sample_encoded_bytes", "sample_decoded_pixels"}
+    assert {f[:-4] for f in os.listdir(tmp_path)} == names
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert sum(os.path.getsize(tmp_path / (k + ".npy")) for k in names) <= 64 * 10**6
+    from oracle import oracle as O
+    px = O.synth(np.uint16, 0, frames, 512 * 512)
+    want, sizes, pb = O.encode_stack(px)
+    offs, pick = d["frame_offsets"].astype(np.int64), d["sample_frames"].astype(np.int64)
+    assert pick.size == 32 and pick[0] == 0 and pick[-1] == frames - 1 and (np.diff(pick) > 0).all()
+    assert offs[0] == 0 and (np.diff(offs) == sizes.astype(np.int64)).all()
+    assert list(d["encode_status"]) == [0, pb] and list(d["decode_status"]) == [0]
+    assert (d["sample_encoded_bytes"] == np.concatenate([want[offs[f]: offs[f + 1]] for f in pick])).all()
+    assert (d["sample_decoded_pixels"] == px[pick]).all()
+
+
+def test_bench_rejects_fewer_than_one_step():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300,
+                       cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr, r.stderr[-2000:]
 
 
 @pytest.mark.gpu

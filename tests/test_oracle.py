@@ -2,10 +2,19 @@
 
 Sources of truth, in order: (1) tests/golden/terse_golden.json -- produced by the REAL reference
 (oracle/_ref, generator tests/golden/make_golden.py); (2) the doc-comment known answers of
-Terse.hpp:53-57 / :127-154 and SURVEY.md section 8.0; (3) a live differential run against
-oracle/_ref when that library is present in the checkout."""
+Terse.hpp:53-57 / :127-154 and SURVEY.md section 8.0; (3) a differential run against what the
+reference made of seeded frames (tests/golden/reference_runs.json, generator
+tests/golden/make_reference_runs.py), and against oracle/_ref itself when that library is
+present in the checkout."""
+import json
+import os
+
 import numpy as np
 import pytest
+
+
+def _reference_runs():
+    return json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_runs.json")))
 
 
 def _px(case):
@@ -98,14 +107,12 @@ def test_worst_case_bound_is_tight_enough(oracle):
     assert (oracle.decode(s, n, np.uint16) == px).all()
 
 
-@pytest.mark.parametrize("dtype", [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.int64])
-def test_live_differential_vs_reference(oracle, dtype):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built in this checkout (reference sources absent)")
+def differential_cases(oracle, dtype):
+    """Seeded (n, hi, pixels) frames inside the reference's validity domain whose oracle stream fits the
+    reference's own buffer (D7); tests/golden/make_reference_runs.py records what the reference makes of each."""
     rng = np.random.RandomState(7)
     dt = np.dtype(dtype)
     bits = dt.itemsize * 8
-    # stay inside the reference's validity domain
     top = bits - 2 if dt.kind == "i" else (31 if bits == 32 else bits)
     if bits == 64:
         top = 30   # Terse.hpp:554 calls the C `abs(int)` on 64-bit values: broken above 2^31
@@ -115,9 +122,26 @@ def test_live_differential_vs_reference(oracle, dtype):
             if dt.kind == "i":
                 mag = mag * rng.choice([-1, 1], size=n)
             px = mag.astype(dt)
-            so, pbo = oracle.encode(px)
-            if so.size > int(np.ceil(n * (dt.itemsize + 12.0 / (12 * 8)))):
+            if oracle.encode(px)[0].size > int(np.ceil(n * (dt.itemsize + 12.0 / (12 * 8)))):
                 continue   # defect D7: the reference's own buffer (Terse.hpp:503) overflows here
+            yield n, hi, px
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.int64])
+def test_live_differential_vs_reference(oracle, dtype):
+    """The oracle against the real reference on differential_cases(): against what the reference made of them
+    (tests/golden/reference_runs.json: stream size, FNV-1a64 and prolix_bits of its encode, FNV-1a64 of its decode of that
+    stream) and, where oracle/_ref is built in this checkout, against the reference itself."""
+    dt = np.dtype(dtype)
+    want = _reference_runs()["differential"][dt.name]
+    cases = list(differential_cases(oracle, dt))
+    assert [[n, hi] for n, hi, _ in cases] == [w[:2] for w in want], dtype
+    for (n, hi, px), (_, _, size, pb, stream_fnv, back_fnv) in zip(cases, want):
+        so, pbo = oracle.encode(px)
+        assert so.size == size and f"{oracle.fnv1a64(so):016x}" == stream_fnv and pbo == pb, (dtype, n, hi)
+        assert back_fnv == f"{oracle.fnv1a64(px):016x}", (dtype, n, hi)      # the reference expanded this stream to px
+        assert (oracle.decode(so, n, dt) == px).all()
+        if oracle.have_ref():
             sr, pbr, _ = oracle.ref_encode(px)
             assert so.tobytes() == sr.tobytes() and pbo == pbr, (dtype, n, hi)
             assert (oracle.ref_decode(so, n, dt, pbo) == px).all()
