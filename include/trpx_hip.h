@@ -115,6 +115,8 @@ int trpx_encode(int dtype, const void* pixels, size_t n_values, size_t n_frames,
  *   pixels_out     DEVICE T[n_frames * n_values], aligned to T (16-byte aligned with n_values % 4 == 0: the fastest case)
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT if a frame's
  *                  bits run past its end (the reference does not check; we do)
+ * Callers with an index-free stack (a .trpx file) call trpx_locate_frames first and then decode with the offsets it wrote:
+ * frame_offsets = NULL locates the frames by one serial walk over the whole stack.
  */
 int trpx_decode(int stream_signed, int out_dtype, const uint8_t* terse, size_t terse_bytes,
                 const uint64_t* frame_offsets, size_t n_values, size_t n_frames, unsigned block,
@@ -178,12 +180,33 @@ int trpx_decode_host(int stream_signed, int out_dtype, const uint8_t* terse, siz
                      unsigned block, void* pixels_out, int device);
 
 /*
- * Locate the frames of a stack that comes without an index (a .trpx file): serial header walk on
- * the device, the intended semantics of jpa::Terse::f_find_terse_frame (Terse.hpp:562-585).
+ * Locate the frames of a stack that comes without an index (a .trpx file): trpx_locate_frames on a device copy of the
+ * stack, the intended semantics of jpa::Terse::f_find_terse_frame (Terse.hpp:562-585).
  * frame_offsets: HOST uint64_t[n_frames + 1].  max_bits = widest legal block (8, 16 or 32).
  */
 int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames,
                             unsigned block, unsigned max_bits, uint64_t* frame_offsets, int device);
+
+/*
+ * Locate the frames of an index-free stack on the device: frame_offsets[k] = first byte of frame k, [n_frames] = end of the
+ * last frame asked for -- the intended semantics of Terse.hpp:562-585, the offsets trpx_decode's own walk finds.  For callers
+ * whose stack is already in device memory (a torch pipeline, trpx_decode_sharded's global table, a graph capture).  The
+ * frames are walked one after another by one wavefront (decode_locate.hip: the run-skipping header walk of trpx_decode's own
+ * serial walk, count only), so the time grows with the number of frames and of width changes.  Any block size, max_bits up
+ * to 64.
+ *   terse          DEVICE const uint8_t[terse_bytes], 4-byte aligned
+ *   max_bits       widest legal block: 8, 16, 32 or 64 by the pixel type
+ *   frame_offsets  DEVICE uint64_t[n_frames + 1], 8-byte aligned; unspecified when status[0] = TRPX_ERR_CORRUPT
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT for a chain past terse_bytes, a width above
+ *                  max_bits or fewer frames present than n_frames (n_frames smaller than the frames present is no error)
+ *   workspace      DEVICE >= trpx_locate_workspace_bytes(), 8-byte aligned: a function of terse_bytes alone, never of
+ *                  n_frames x blocks (256 bytes in this version, for every stack)
+ * Stream-ordered, no allocation, no host synchronisation: capturable into a HIP graph.  Argument errors are return codes.
+ */
+size_t trpx_locate_workspace_bytes(size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block);
+int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                       unsigned max_bits, uint64_t* frame_offsets, uint32_t* status, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
@@ -334,8 +357,8 @@ size_t trpx_header_group_states(const char* data, size_t len, uint64_t* group_st
  * src/prolix.cpp:69-92 expands a .trpx file with one `trpx_data.prolix(image, i)` per frame, src/terse.cpp:63-69 pushes
  * one image at a time.  The *_host entry points keep their device buffers per calling thread between calls (no
  * allocation per frame; trpx_host_release frees them).  For the expanding loop a stack object keeps the compressed stack
- * on the device: trpx_stack_open uploads it once (frame_offsets may be NULL: the frames are then located by the serial
- * walk, Terse.hpp:562-585, max_bits as in trpx_frame_offsets_host; group_states, if the file carried them, make the
+ * on the device: trpx_stack_open uploads it once (frame_offsets may be NULL: the frames are then located on that copy by
+ * trpx_locate_frames, Terse.hpp:562-585, max_bits as in trpx_frame_offsets_host; group_states, if the file carried them, make the
  * expansion walk-free), trpx_stack_read(frame) expands a window of frames
  * starting at `frame` in ONE device call on a miss (<= 64 MB of pixels) and afterwards only copies the frame asked for
  * -- any output type of trpx_decode_host.  Not thread safe per object (the reference's prolix is not const either,

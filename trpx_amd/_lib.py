@@ -53,6 +53,8 @@ SYMBOLS = {
     "trpx_encode_host": (_I, [_I, _P, _SZ, _SZ, _U, _P, _SZ, C.POINTER(_SZ), _P, C.POINTER(_U), _I]),
     "trpx_decode_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _P, _I]),
     "trpx_frame_offsets_host": (_I, [_P, _SZ, _SZ, _SZ, _U, _U, _P, _I]),
+    "trpx_locate_workspace_bytes": (_SZ, [_SZ, _SZ, _SZ, _U]),
+    "trpx_locate_frames": (_I, [_P, _SZ, _SZ, _SZ, _U, _U, _P, _P, _P, _SZ, _P]),
     "trpx_gather_workspace_bytes": (_SZ, [_SZ, _I]),
     "trpx_gather_frame_offsets": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P, _SZ, _P]),
     "trpx_encode_sharded_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _I]),

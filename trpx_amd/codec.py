@@ -178,6 +178,31 @@ def decode(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: in
     return out, status
 
 
+def locate_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, block: int = BLOCK) -> int:
+    return lib().trpx_locate_workspace_bytes(terse_bytes, n_values, n_frames, block)
+
+
+def _max_bits(dtype) -> int:
+    return 8 * lib().trpx_dtype_size(dtype_code(torch_dtype(dtype)))
+
+
+def locate_frames(terse: torch.Tensor, n_values: int, n_frames: int, dtype, block: int = BLOCK,
+                  workspace: Workspace | None = None, status: torch.Tensor | None = None,
+                  out: torch.Tensor | None = None):
+    """Frame offsets of an index-free stack resident on the GPU (trpx_locate_frames).  Returns (offsets int64
+    [n_frames + 1], status); asynchronous on the current stream, status[0] != 0: corrupt or truncated stack."""
+    dev = terse.device
+    if out is None:
+        out = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    ws = (workspace or Workspace(dev)).get(locate_workspace_bytes(terse.numel(), n_values, n_frames, block))
+    with torch.cuda.device(dev):
+        check(lib().trpx_locate_frames(terse.data_ptr(), terse.numel(), n_values, n_frames, block, _max_bits(dtype),
+                                       out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+    return out, status
+
+
 def build_index(terse: torch.Tensor, frame_offsets: torch.Tensor, n_values: int, n_frames: int, dtype,
                 block: int = BLOCK) -> torch.Tensor:
     """Walk an existing stack once and keep the decode index (trpx_build_index)."""

@@ -757,6 +757,31 @@ int trpx_decode_host(int stream_signed, int out_dtype, const uint8_t* terse, siz
     return TRPX_OK;
 }
 
+size_t trpx_locate_workspace_bytes(size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    if (!terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return 0;
+    return trpx::locate_workspace_bytes(g, terse_bytes);
+}
+
+int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned max_bits,
+                       uint64_t* frame_offsets, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    if (!terse || !terse_bytes || !frame_offsets || !status || !workspace || max_bits == 0 || max_bits > 64)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad argument");
+    if (!geom_of(n_values, block, &g))
+        return fail(block != 12 ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "trpx_locate_frames: unsupported sizes/block (block=%u)", block);
+    if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                      // every frame is at least one byte (Terse.hpp:547)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: misaligned pointer (terse needs 4 B, workspace 8 B)");
+    const size_t need = trpx::locate_workspace_bytes(g, terse_bytes);
+    if (workspace_bytes < need) return fail(TRPX_ERR_CAPACITY, "trpx_locate_frames: workspace %zu < %zu", workspace_bytes, need);
+    trpx::fused_ws_forget(workspace, workspace_bytes);
+    HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_bits, frame_offsets, status, workspace,
+                                static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
 int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames,
                             unsigned block, unsigned max_bits, uint64_t* frame_offsets, int device) {
     if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_frame_offsets_host: no HIP device");
@@ -769,35 +794,25 @@ int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_v
                     "trpx_frame_offsets_host: unsupported sizes/block (block=%u)", block);
     if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                     // every frame is at least one byte (Terse.hpp:547)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_frame_offsets_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    const DecWs w = dec_ws(g, n_frames, 4);
-    struct { void* p = nullptr; } d_in, d_st, d_ws;
+    const size_t ws_bytes = trpx::locate_workspace_bytes(g, terse_bytes);
+    struct { void* p = nullptr; } d_in, d_off, d_st, d_ws;
     Arena& A = arena();
     hipStream_t hs = nullptr;
     HIP_TRY(A.get_stream(&hs));
     HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
+    HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1), &d_off.p));
     HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, w.total, &d_ws.p));
+    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws.p));
     HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));
     HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
-    trpx::DecodeArgs a{};
-    a.terse = static_cast<const uint8_t*>(d_in.p);
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = nullptr;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.pixels_out = nullptr;
-    a.status = static_cast<uint32_t*>(d_st.p);
-    char* ws = static_cast<char*>(d_ws.p);
-    a.walk_offsets = reinterpret_cast<uint64_t*>(ws + w.walk_offsets);
-    a.tile_off = reinterpret_cast<uint64_t*>(ws + w.tile_off);
-    a.widths = reinterpret_cast<uint8_t*>(ws + w.widths);
-    a.seg_ws = ws + w.seg;
-    HIP_TRY(trpx::launch_walk_serial(a, max_bits, hs));
+    const int rc = trpx_locate_frames(static_cast<const uint8_t*>(d_in.p), terse_bytes, n_values, n_frames, block, max_bits,
+                                      static_cast<uint64_t*>(d_off.p), static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(hs));
     uint32_t st[TRPX_STATUS_WORDS];
     HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
     if (st[0]) return fail((int)st[0], "trpx_frame_offsets_host: corrupt or truncated stack");
-    HIP_TRY(copy_sync(hs, frame_offsets, a.walk_offsets, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(hs, frame_offsets, d_off.p, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -919,14 +934,14 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
     if (!terse || !terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || n_frames > terse_bytes)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_open: bad argument / sizes");
     std::vector<uint64_t> offs(n_frames + 1);
-    if (frame_offsets) memcpy(offs.data(), frame_offsets, 8 * (n_frames + 1));
-    else {
-        const int rc = trpx_frame_offsets_host(terse, terse_bytes, n_values, n_frames, block, max_bits ? max_bits : 32, offs.data(), -1);
-        if (rc) return rc;
+    if (frame_offsets) {
+        memcpy(offs.data(), frame_offsets, 8 * (n_frames + 1));
+        if (offs[0] != 0 || offs[n_frames] > terse_bytes) return fail(TRPX_ERR_CORRUPT, "trpx_stack_open: frame offsets do not fit the stack");
+        for (size_t f = 0; f < n_frames; ++f)
+            if (offs[f + 1] <= offs[f]) return fail(TRPX_ERR_CORRUPT, "trpx_stack_open: frame offsets are not increasing");
+    } else if (max_bits > 64) {
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_open: max_bits=%u", max_bits);
     }
-    if (offs[0] != 0 || offs[n_frames] > terse_bytes) return fail(TRPX_ERR_CORRUPT, "trpx_stack_open: frame offsets do not fit the stack");
-    for (size_t f = 0; f < n_frames; ++f)
-        if (offs[f + 1] <= offs[f]) return fail(TRPX_ERR_CORRUPT, "trpx_stack_open: frame offsets are not increasing");
     hipStream_t hs = nullptr;                                                  // the calling thread's private stream (see Arena)
     HIP_TRY(arena().get_stream(&hs));
     trpx_stack* s = new trpx_stack;
@@ -945,7 +960,21 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
     if ((e = hipMalloc(&s->d_ws, s->ws_bytes ? s->ws_bytes : 256)) != hipSuccess) return bail(e, "hipMalloc(workspace)");
     if ((e = hipMemsetAsync(s->d_terse, 0, trpx::align_up(terse_bytes, 4) + 8, hs)) != hipSuccess) return bail(e, "hipMemset");
     if ((e = copy_sync(hs, s->d_terse, terse, terse_bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(stack)");
-    if ((e = copy_sync(hs, s->d_offs, s->offs.data(), 8 * (n_frames + 1), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
+    if (frame_offsets) {
+        if ((e = copy_sync(hs, s->d_offs, s->offs.data(), 8 * (n_frames + 1), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
+    } else {                                                                   // no index: the frames are located on the stack just uploaded
+        const size_t lb = trpx::locate_workspace_bytes(g, terse_bytes);
+        void* d_lws = nullptr;
+        if ((e = arena().get(Arena::kWorkspace, lb, &d_lws)) != hipSuccess) return bail(e, "locate workspace");
+        const int rc = trpx_locate_frames(static_cast<const uint8_t*>(s->d_terse), terse_bytes, n_values, n_frames, block,
+                                          max_bits ? max_bits : 32, static_cast<uint64_t*>(s->d_offs),
+                                          static_cast<uint32_t*>(s->d_status), d_lws, lb, hs);
+        if (rc) { stack_free(s); return rc; }
+        uint32_t st[TRPX_STATUS_WORDS];
+        if ((e = copy_sync(hs, st, s->d_status, sizeof st, hipMemcpyDeviceToHost)) != hipSuccess) return bail(e, "hipMemcpy(status)");
+        if (st[0]) { stack_free(s); return fail((int)st[0], "trpx_stack_open: corrupt or truncated stack"); }
+        if ((e = copy_sync(hs, s->offs.data(), s->d_offs, 8 * (n_frames + 1), hipMemcpyDeviceToHost)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
+    }
     if (group_states && block == (unsigned)trpx::kBlock) {   // row f1: the file carried its group states
         s->groups = g.n_tiles;
         if ((e = hipMalloc(&s->d_states, 8 * n_frames * s->groups)) != hipSuccess) return bail(e, "hipMalloc(states)");
