@@ -110,13 +110,17 @@ int trpx_encode(int dtype, const void* pixels, size_t n_values, size_t n_frames,
  *   stream_signed  the header's `signed` attribute; must equal trpx_dtype_is_signed(out_dtype)
  *                  (same-type decode is the reference's contract)
  *   terse          DEVICE const uint8_t[terse_bytes], 4-byte aligned
- *   frame_offsets  DEVICE const uint64_t[n_frames + 1], or NULL: the frames are then located by
- *                  a serial header walk on the device (the .trpx format stores no index)
+ *   frame_offsets  DEVICE const uint64_t[n_frames + 1], or NULL: the frames are then located on the device
+ *                  (the .trpx format stores no index), see below
  *   pixels_out     DEVICE T[n_frames * n_values], aligned to T (16-byte aligned with n_values % 4 == 0: the fastest case)
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT if a frame's
  *                  bits run past its end (the reference does not check; we do)
- * Callers with an index-free stack (a .trpx file) call trpx_locate_frames first and then decode with the offsets it wrote:
- * frame_offsets = NULL locates the frames by one serial walk over the whole stack.
+ * frame_offsets = NULL (an index-free stack, a .trpx file): where trpx_locate_frames takes its position-parallel route (block
+ * 12, pixels of up to 32 bits, 4 frames and 8 KB and more, not TRPX_LOCATE_PATH=serial / TRPX_DECODE_PATH=basic) and its
+ * workspace fits behind the offsets in this call's workspace, the frames are located that way and then decoded by the same
+ * routes as with offsets given (trpx_decode_workspace_bytes does not change); otherwise by one serial walk over the whole
+ * stack and the basic kernels.  Offsets, status and pixels are the same either way.  Callers that keep the offsets call
+ * trpx_locate_frames and decode with what it wrote.
  */
 int trpx_decode(int stream_signed, int out_dtype, const uint8_t* terse, size_t terse_bytes,
                 const uint64_t* frame_offsets, size_t n_values, size_t n_frames, unsigned block,
@@ -190,23 +194,35 @@ int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_v
 /*
  * Locate the frames of an index-free stack on the device: frame_offsets[k] = first byte of frame k, [n_frames] = end of the
  * last frame asked for -- the intended semantics of Terse.hpp:562-585, the offsets trpx_decode's own walk finds.  For callers
- * whose stack is already in device memory (a torch pipeline, trpx_decode_sharded's global table, a graph capture).  The
- * frames are walked one after another by one wavefront (decode_locate.hip: the run-skipping header walk of trpx_decode's own
- * serial walk, count only), so the time grows with the number of frames and of width changes.  Any block size, max_bits up
- * to 64.
+ * whose stack is already in device memory (a torch pipeline, trpx_decode_sharded's global table, a graph capture).  Block 12
+ * with max_bits <= 32, from 4 frames and 8 KB on: position-parallel (decode_locate.hip: header chains of fixed chunks of the
+ * stack with checkpoints and links, one wavefront that resolves each frame's end by block counts along them, a parallel
+ * verification of every frame by the serial walk, and that serial walk from the first frame that fails verification on,
+ * decided on the device) -- the offsets and the status are the serial walk's in every case.  Otherwise, or after
+ * trpx_set_locate_path(1) / TRPX_LOCATE_PATH=serial: the frames are walked one after another by one wavefront (the
+ * run-skipping header walk of trpx_decode's own serial walk, count only).  Any block size, max_bits up to 64.
  *   terse          DEVICE const uint8_t[terse_bytes], 4-byte aligned
  *   max_bits       widest legal block: 8, 16, 32 or 64 by the pixel type
  *   frame_offsets  DEVICE uint64_t[n_frames + 1], 8-byte aligned; unspecified when status[0] = TRPX_ERR_CORRUPT
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT for a chain past terse_bytes, a width above
  *                  max_bits or fewer frames present than n_frames (n_frames smaller than the frames present is no error)
- *   workspace      DEVICE >= trpx_locate_workspace_bytes(), 8-byte aligned: a function of terse_bytes alone, never of
- *                  n_frames x blocks (256 bytes in this version, for every stack)
+ *   workspace      DEVICE >= trpx_locate_workspace_bytes(), 8-byte aligned: a function of terse_bytes and n_frames, never
+ *                  of n_frames x blocks -- for block 12 in this version 256 bytes + one byte per frame + 16 bytes per 4096
+ *                  bits of the stack (about terse_bytes / 32) + 32 bytes per 256 Kbit, rounded up to 256; 256 bytes otherwise.
+ *                  The size does not depend on max_bits, so a block-12 stack that takes the serial route (max_bits 64,
+ *                  fewer than 4 frames, under 8 KB) is asked for the same scratch and leaves it unused
  * Stream-ordered, no allocation, no host synchronisation: capturable into a HIP graph.  Argument errors are return codes.
  */
 size_t trpx_locate_workspace_bytes(size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block);
 int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
                        unsigned max_bits, uint64_t* frame_offsets, uint32_t* status, void* workspace, size_t workspace_bytes,
                        void* stream);
+/*
+ * Frame locator selection (trpx_locate_frames and the entry points built on it): 0 = auto (position-parallel where its
+ * preconditions hold), 1 = always the serial walk.  Both yield the same offsets and status; the setter exists for tests and
+ * A/B measurements.  Process-wide; also settable with the environment variable TRPX_LOCATE_PATH=serial.
+ */
+int trpx_set_locate_path(int path);
 
 /*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
@@ -264,7 +280,7 @@ int trpx_set_encode_path(int path);
  * or more, which keep them whole on the per-frame decoder -- such a
  * stack fills the GPU by itself; TRPX_SINGLE_PART=<frames>,<blocks> moves that line for tuning runs (stacks of <frames>
  * frames and more keep frames of up to <blocks> blocks whole).
- * These three variables are the only ones the library reads; further switches exist in -DTRPX_DIAGNOSTICS builds only.
+ * These three variables and TRPX_LOCATE_PATH (trpx_set_locate_path) are the only ones the library reads; further switches exist in -DTRPX_DIAGNOSTICS builds only.
  * The tuned kernels issue 8- and 16-byte accesses at addresses that are only aligned to the pixel type (frames of any
  * pixel count): they rely on the HSA unaligned-access mode, which ROCm enables on gfx950.
  */

@@ -1,14 +1,13 @@
-"""HIP-event timing of trpx_locate_frames (decode_locate.hip) on index-free stacks, alone, followed by trpx_decode with the
-offsets it wrote, and -- for comparison -- trpx_decode with frame_offsets = NULL (its own serial walk, then the basic
-kernels) with the time of that walk alone (k_walk_serial, the width-storing serial walk trpx_frame_offsets_host ran before
-trpx_locate_frames existed: stage 0 of trpx_profile_read).  One JSON line per stack; offsets and pixels are checked against
-the encoder's before anything is timed.
+"""HIP-event timing of trpx_locate_frames (decode_locate.hip) on index-free stacks: the auto route (position-parallel) and the
+serial route (trpx_set_locate_path(1), one timed call) side by side on the same stack, then the auto route followed by
+trpx_decode with the offsets it wrote, trpx_decode with frame_offsets = NULL (which locates the same way, then takes the
+tuned routes), and that call on the serial route (its own serial walk, then the basic kernels; one timed call).  One JSON
+line per stack; offsets and pixels are checked against the encoder's before anything is timed.
 
     python tools/locate_time.py [--reps R] [--stacks synth,poisson3,poisson3_big,int32_4k]
 
-The locator walks the frames one after another: seconds per 2000-frame Poisson(3) stack.  Run it under a timeout."""
+The serial route and trpx_decode(frame_offsets = NULL) take seconds per 2000-frame Poisson(3) stack.  Run it under a timeout."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -78,6 +77,14 @@ def main():
         assert int(st[0].item()) == 0 and torch.equal(offs, want), f"{label}: offsets differ from the encoder's"
         reps = a.reps
         loc_med, loc_min = timed(locate, reps)
+        L.trpx_set_locate_path(1)                              # the serial route on the same stack, same process
+        try:
+            locate()
+            torch.cuda.synchronize()
+            assert int(st[0].item()) == 0 and torch.equal(offs, want), f"{label}: serial offsets differ from the encoder's"
+            ser_med, _ = timed(locate, 1)
+        finally:
+            L.trpx_set_locate_path(0)
 
         def both():
             locate()
@@ -93,20 +100,17 @@ def main():
         torch.cuda.synchronize()
         assert int(st[0].item()) == 0 and torch.equal(back.view(torch.uint8), px.view(torch.uint8)), f"{label}: pixels differ"
         walk_med, _ = timed(walk_decode, reps)
-        stage = (C.c_float * 16)()
-        walk_ms = []
-        for _ in range(reps):
-            L.trpx_profile_enable(1)
-            walk_decode()
-            got = L.trpx_profile_read(stage, 16)
-            L.trpx_profile_enable(0)
-            assert got >= 1
-            walk_ms.append(stage[0])
+        L.trpx_set_locate_path(1)                              # trpx_decode(NULL) as before the parallel locator: its serial walk
+        try:
+            ser_dec_med, _ = timed(walk_decode, 1)
+        finally:
+            L.trpx_set_locate_path(0)
         assert int(st[0].item()) == 0
         print(json.dumps({"stack": label, "frames": frames, "n_values": n,
                           "stack_bytes": stack.numel(), "locate_ms": round(loc_med, 3), "locate_min_ms": round(loc_min, 3),
+                          "locate_serial_ms": round(ser_med, 3), "speedup": round(ser_med / loc_med, 1),
                           "locate_decode_ms": round(both_med, 3), "decode_no_offsets_ms": round(walk_med, 3),
-                          "k_walk_serial_ms": round(float(np.median(walk_ms)), 3),
+                          "decode_no_offsets_serial_ms": round(ser_dec_med, 3),
                           "frames_per_s_locate": round(frames / loc_med * 1e3), "workspace_bytes": lb}), flush=True)
         del px, back, stack, ws_l, ws_d, ws
         torch.cuda.empty_cache()

@@ -81,6 +81,7 @@ SYMBOLS = {
     "trpx_host_release": (None, []),
     "trpx_set_encode_path": (_I, [_I]),
     "trpx_set_decode_path": (_I, [_I]),
+    "trpx_set_locate_path": (_I, [_I]),
     "trpx_profile_enable": (_I, [_I]),
     "trpx_profile_read": (_I, [C.POINTER(C.c_float), _I]),
     "trpx_bench_stream": (_I, [_I, _P, _P, _SZ, _P]),

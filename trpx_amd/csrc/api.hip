@@ -343,6 +343,19 @@ int trpx_decode(int stream_signed, int out_dtype, const uint8_t* terse, size_t t
     const int route = g_decode_path;                                          // trpx_set_decode_path / $TRPX_DECODE_PATH
     const bool basic = route == 1, force_tiles = route == 2;
     const bool bits32 = 8 * (uint64_t)trpx_worst_case_bytes(out_dtype, n_values, block) < 0xF0000000ull;   // 32-bit frame-relative bit offsets
+    // no offsets: the frames located by trpx_locate_frames' position-parallel route into walk_offsets, its scratch laid over the
+    // regions behind them (nothing the decode writes exists yet), and then the routes a caller with offsets takes.  Elsewhere
+    // (the basic or serial route asked for, other sizes, scratch too small): the decode's own serial walk, launch_decode.
+    const uint32_t max_w = 8u * (uint32_t)trpx_dtype_size(out_dtype);
+    const bool located = !frame_offsets && !basic && bits32 && block == (unsigned)trpx::kBlock &&
+                         trpx::locate_parallel(g, terse_bytes, n_frames, max_w) &&
+                         w.total - w.tile_off >= trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
+    if (located) {
+        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, a.walk_offsets, status, ws + w.tile_off,
+                                    static_cast<hipStream_t>(stream)));
+        frame_offsets = a.walk_offsets;
+        a.frame_offsets = frame_offsets;
+    }
     const bool fast_ok = frame_offsets && !basic && bits32 && block == (unsigned)trpx::kBlock;
     // frames whose worst case fits 2^26 bits: one workgroup per frame, the walk and the extraction overlap inside it -- whatever
     // the number of frames (since the round-3 walker a single 512^2 frame takes 0.10 ms this way against 0.24 ms through the
@@ -365,6 +378,8 @@ int trpx_decode(int stream_signed, int out_dtype, const uint8_t* terse, size_t t
         HIP_TRY(trpx::launch_decode_fast(out_dtype, a, false, static_cast<hipStream_t>(stream)));
     else
         HIP_TRY(trpx::launch_decode(out_dtype, a, frame_offsets != nullptr, static_cast<hipStream_t>(stream)));
+    if (located)                                                               // (the decode cleared the status: the locate's verdict again)
+        HIP_TRY(trpx::launch_locate_status(a.walk_offsets, (uint32_t)n_frames, status, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -564,6 +579,12 @@ int trpx_set_decode_path(int path) {
     return TRPX_OK;
 }
 
+int trpx_set_locate_path(int path) {
+    if (path != 0 && path != 1) return fail(TRPX_ERR_INVALID_ARG, "trpx_set_locate_path: 0 = auto, 1 = serial");
+    trpx::g_locate_path = path;
+    return TRPX_OK;
+}
+
 int trpx_profile_enable(int on) {
     trpx::profiler().enabled = on != 0;
     return TRPX_OK;
@@ -760,7 +781,7 @@ int trpx_decode_host(int stream_signed, int out_dtype, const uint8_t* terse, siz
 size_t trpx_locate_workspace_bytes(size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
     trpx::FrameGeom g;
     if (!terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return 0;
-    return trpx::locate_workspace_bytes(g, terse_bytes);
+    return trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
 }
 
 int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned max_bits,
@@ -774,7 +795,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
         return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
     if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: misaligned pointer (terse needs 4 B, workspace 8 B)");
-    const size_t need = trpx::locate_workspace_bytes(g, terse_bytes);
+    const size_t need = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
     if (workspace_bytes < need) return fail(TRPX_ERR_CAPACITY, "trpx_locate_frames: workspace %zu < %zu", workspace_bytes, need);
     trpx::fused_ws_forget(workspace, workspace_bytes);
     HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_bits, frame_offsets, status, workspace,
@@ -794,7 +815,7 @@ int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_v
                     "trpx_frame_offsets_host: unsupported sizes/block (block=%u)", block);
     if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                     // every frame is at least one byte (Terse.hpp:547)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_frame_offsets_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    const size_t ws_bytes = trpx::locate_workspace_bytes(g, terse_bytes);
+    const size_t ws_bytes = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
     struct { void* p = nullptr; } d_in, d_off, d_st, d_ws;
     Arena& A = arena();
     hipStream_t hs = nullptr;
@@ -963,7 +984,7 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
     if (frame_offsets) {
         if ((e = copy_sync(hs, s->d_offs, s->offs.data(), 8 * (n_frames + 1), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
     } else {                                                                   // no index: the frames are located on the stack just uploaded
-        const size_t lb = trpx::locate_workspace_bytes(g, terse_bytes);
+        const size_t lb = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
         void* d_lws = nullptr;
         if ((e = arena().get(Arena::kWorkspace, lb, &d_lws)) != hipSuccess) return bail(e, "locate workspace");
         const int rc = trpx_locate_frames(static_cast<const uint8_t*>(s->d_terse), terse_bytes, n_values, n_frames, block,

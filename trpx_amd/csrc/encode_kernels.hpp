@@ -106,11 +106,16 @@ hipError_t launch_seg_groups(const DecodeArgs& a, uint32_t max_w, const uint64_t
 // header walk only (fills a.widths / a.tile_off from the stream): builds the decode index of an existing stack
 hipError_t launch_walk_only(const DecodeArgs& a, uint32_t max_w, bool clear_status, hipStream_t st);
 hipError_t launch_walk_serial(const DecodeArgs& a, uint32_t max_w, hipStream_t st);
-// decode_locate.hip: frame_offsets[0 .. n_frames] of a stack without an index (trpx_locate_frames): the serial walk, count only.
-// Workspace: locate_workspace_bytes (a function of the stream's size, never of n_frames x blocks).
-size_t locate_workspace_bytes(const FrameGeom& g, uint64_t terse_bytes);
+// decode_locate.hip: frame_offsets[0 .. n_frames] of a stack without an index (trpx_locate_frames): the position-parallel
+// locator (block 12, max_w <= 32) or the serial walk, count only.  Workspace: locate_workspace_bytes (about terse_bytes / 64 +
+// n_frames, never n_frames x blocks).  g_locate_path: 0 = auto, 1 = serial ($TRPX_LOCATE_PATH, trpx_set_locate_path).
+extern int g_locate_path;
+size_t locate_workspace_bytes(const FrameGeom& g, uint64_t terse_bytes, uint64_t n_frames);
 hipError_t launch_locate(const uint8_t* terse, uint64_t terse_bytes, const FrameGeom& g, uint32_t n_frames, uint32_t max_w,
-                         uint64_t* offsets, uint32_t* status, void* workspace, hipStream_t st);
+                         uint64_t* offsets, uint32_t* status, void* workspace, hipStream_t st, bool clear_status = true);
+bool locate_parallel(const FrameGeom& g, uint64_t terse_bytes, uint64_t n_frames, uint32_t max_w);   // launch_locate's route
+// status[0] = TRPX_ERR_CORRUPT if the offsets launch_locate wrote show a failed walk (its last frame empty)
+hipError_t launch_locate_status(const uint64_t* offsets, uint32_t n_frames, uint32_t* status, hipStream_t st);
 // group states (chain state at every 256th block): read them off an index (a.widths / a.tile_off) / rebuild the index from them
 hipError_t launch_index_group_states(const DecodeArgs& a, uint64_t* states, hipStream_t st);
 hipError_t launch_walk_groups(const DecodeArgs& a, uint32_t max_w, const uint64_t* states, bool clear_status, hipStream_t st);
