@@ -189,6 +189,28 @@ public:
                                                f_states(), d_size, d_frame_sizes.size(), d_block, out, -1), "Terse::prolix_all");
     }
 
+    /// Sums of `group` consecutive frames into `out` (ceil(number_of_frames() / group) x size() values) in one device call,
+    /// without expanding the frames (trpx_decode_sum_host).  A group that does not divide the frame count leaves a shorter last
+    /// group.  V: int32 / uint32 (clamped), int64 / uint64 (exact), float / double (the exact sum rounded once).
+    template <typename V>
+    void prolix_sum(V* out, std::size_t group) {
+        static_assert(std::is_same_v<V, std::int32_t> || std::is_same_v<V, std::uint32_t> || std::is_same_v<V, std::int64_t> ||
+                          std::is_same_v<V, std::uint64_t> || std::is_same_v<V, float> || std::is_same_v<V, double>,
+                      "prolix_sum: int32, uint32, int64, uint64, float or double sums");
+        if (d_signed && std::is_unsigned_v<V>)
+            throw std::invalid_argument("signed data cannot be decompressed into unsigned data");
+        if (group == 0) throw std::invalid_argument("prolix_sum: group must be at least 1");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_sum: values of more than 32 bits are not supported");
+        if (d_frame_sizes.empty()) return;
+        group = std::min(group, d_frame_sizes.size());
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_sum_host(bits + (d_signed ? 1 : 0), detail::out_dtype_of<V>(), d_terse_data.data(),
+                                           d_terse_data.size(), offs.data(), d_size, d_frame_sizes.size(), d_block,
+                                           (unsigned)group, out, -1), "Terse::prolix_sum");
+    }
+
     std::size_t size() const { return d_size; }                                   // Terse.hpp:396
     std::size_t number_of_frames() const { return d_frame_sizes.size(); }         // :403
     std::vector<std::size_t> const& dim() const { return d_dim; }                 // :410

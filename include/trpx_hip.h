@@ -225,6 +225,47 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 int trpx_set_locate_path(int path);
 
 /*
+ * Summing decode: sums of consecutive frames straight from the stream, without writing the decoded frames.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32: its signedness and the widest legal block (as trpx_build_index)
+ *   out_dtype      TRPX_I32, U32, I64, U64, F32 or F64
+ *   terse          DEVICE const uint8_t[terse_bytes], 4-byte aligned
+ *   frame_offsets  DEVICE const uint64_t[n_frames + 1], 8-byte aligned, or NULL (an index-free stack): the frames are then
+ *                  located in the workspace first, as trpx_decode(frame_offsets = NULL) does (position-parallel where
+ *                  trpx_locate_frames takes that route, the serial walk otherwise)
+ *   index          DEVICE decode index of exactly these frames (trpx_encode_indexed / trpx_build_index), 16-byte aligned, or
+ *                  NULL: the index is built in the workspace by trpx_build_index's walk.  Given, it is validated against the
+ *                  frame sizes as in trpx_decode_indexed (a mismatch: status[0] = TRPX_ERR_CORRUPT).  Needs frame_offsets.
+ *   group          frames per output, >= 1
+ *   sums_out       DEVICE [n_out][n_values] of out_dtype, n_out = ceil(n_frames / group), aligned to its type (16 B: the
+ *                  fast case).  Output j = the sum of frames [j * group, min((j + 1) * group, n_frames)): a group that does
+ *                  not divide n_frames leaves a shorter last group.
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT in the cases of trpx_decode, for an index
+ *                  that does not fit the frames and for a block wider than dtype's; the sums are then unspecified
+ *   workspace      DEVICE, 8-byte aligned, >= trpx_decode_sum_workspace_bytes() (the need with frame_offsets and index both
+ *                  NULL; with them given less is used: a call with offsets, index and no frame chunks needs none)
+ * The sum is exact in integers and converted once: I32 / U32 clamp to their limits (the narrowing of Bit_pointer.hpp:747-763),
+ * I64 / U64 are exact, F32 / F64 are the exact sum rounded once to nearest even.  A signed stream into U32 / U64 is
+ * TRPX_ERR_UNSUPPORTED (Terse.hpp:356-357); an unsigned stream into a signed output keeps the value, up to the clamp.  The
+ * sums are bit-identical across runs, input forms and launch splits (integer accumulation, no float atomics).
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL (offsets are absolute into terse).
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, a signed stream into an
+ * unsigned output; TRPX_ERR_INVALID_ARG for group 0, null or misaligned pointers, an unknown dtype / out_dtype, an index
+ * without offsets; TRPX_ERR_CAPACITY for a workspace that is too small.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape and split is
+ * decided on the host from the geometry alone.
+ * trpx_decode_sum_host: host terse / frame_offsets (or NULL) / sums_out; stages, calls trpx_decode_sum and synchronises.
+ */
+size_t trpx_decode_sum_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames,
+                                       unsigned block, unsigned group);
+int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes,
+                    const uint64_t* frame_offsets, const void* index, size_t n_values, size_t n_frames,
+                    unsigned block, unsigned group, void* sums_out, uint32_t* status,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes,
+                         const uint64_t* frame_offsets, size_t n_values, size_t n_frames, unsigned block,
+                         unsigned group, void* sums_out, int device);
+
+/*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
  * box regenerates exactly the pixels the oracle anchors were computed on.  dtype U16 or I32.
  */

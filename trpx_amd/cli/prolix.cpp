@@ -1,13 +1,15 @@
 // prolix -- expands .trpx files to greyscale TIFF stacks on the MI355X.
 // Command line and behaviour of the reference tool (senikm/trpx src/prolix.cpp:18-128):
-//   prolix [-help] [-verbose] [-delete] [file ...]
+//   prolix [-help] [-verbose] [-delete] [-sum N] [file ...]
 // every argument with a .trpx extension is read (Terse(std::ifstream&)), the pixel type is chosen from bits_per_val() and
 // is_signed() (16-bit up to 16 bits, else 32-bit; :69-92), all frames are decoded in one device call into a TIFF stack
 // written next to it as <name>.tif.  Differences: 32-bit stacks are decoded into 32-bit images (the reference passes
 // image<int16_t> there, defect D5), frames >= 2 of a stack are located correctly (D1/D2), and the input is kept unless
-// -delete is given (the reference always deletes it, :111).
+// -delete is given (the reference always deletes it, :111).  -sum N (not in the reference) writes the sums of N consecutive
+// frames instead of the frames (Terse::prolix_sum): a 32-bit TIFF stack, int32 for signed data, uint32 otherwise, clamped.
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <filesystem>
 #include <fstream>
@@ -31,18 +33,39 @@ static void expand_stack(trpx::Terse& data, std::uint32_t w, std::uint32_t h, tr
     }
 }
 
+template <typename T>
+static void sum_stack(trpx::Terse& data, std::size_t group, std::uint32_t w, std::uint32_t h, trpx::Grey_tif& tif) {
+    const std::size_t n = data.size(), frames = data.number_of_frames(), n_out = (frames + group - 1) / group;
+    std::vector<T> sums(n * n_out);
+    data.prolix_sum(sums.data(), group);
+    for (std::size_t i = 0; i < n_out; ++i) {
+        T* dst = tif.push_back<T>(w, h);
+        std::memcpy(dst, sums.data() + i * n, n * sizeof(T));
+    }
+}
+
 int main(int argc, char const* argv[]) {
     bool help = false, verbose = false, del = false;
+    std::size_t sum = 0;                                      // -sum N: frames per summed image (0: expand the frames)
     std::vector<fs::path> params;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "-help") help = true;
         else if (a == "-verbose") verbose = true;
         else if (a == "-delete") del = true;
-        else params.emplace_back(a);
+        else if (a == "-sum") {
+            char* end = nullptr;
+            const unsigned long long v = i + 1 < argc ? std::strtoull(argv[i + 1], &end, 10) : 0;
+            if (i + 1 >= argc || !end || *end || v == 0 || v > 0xFFFFFFFFull) {
+                std::cerr << "prolix: -sum needs a frame count from 1 to 4294967295" << std::endl;
+                return 1;
+            }
+            sum = (std::size_t)v;
+            ++i;
+        } else params.emplace_back(a);
     }
     if (help) {
-        std::cout << "prolix [-help] [-verbose] [-delete] [file ...]\n"
+        std::cout << "prolix [-help] [-verbose] [-delete] [-sum N] [file ...]\n"
                      "  expands trpx files to tiff files (on the GPU).\n"
                      "Examples:\n"
                      "   prolix *              // all TRPX files with .trpx extensions are expanded to tiff files with .tif extensions.\n"
@@ -50,7 +73,9 @@ int main(int argc, char const* argv[]) {
                      "\nkeywords:\n"
                      "  -help      print help\n"
                      "  -verbose   print expanded file names and compute times\n"
-                     "  -delete    delete each trpx file after it has been expanded (the reference tool always does)\n";
+                     "  -delete    delete each trpx file after it has been expanded (the reference tool always does)\n"
+                     "  -sum N     write the sums of N consecutive frames instead of the frames (the last sum may cover fewer):\n"
+                     "             a 32-bit tiff stack, int32 for signed data, uint32 otherwise, clamped\n";
         return 0;
     }
     std::chrono::duration<double> user_time(0), io_time(0);
@@ -76,7 +101,10 @@ int main(int argc, char const* argv[]) {
             else { w = (std::uint32_t)data.dim()[0]; h = 1; }
             if ((std::size_t)w * h != data.size()) throw std::runtime_error("frame dimensions do not match the number of values.");
             trpx::Grey_tif tif;
-            if (data.bits_per_val() <= 16) {
+            if (sum && data.bits_per_val() <= 32) {
+                if (data.is_signed()) sum_stack<std::int32_t>(data, sum, w, h, tif);
+                else sum_stack<std::uint32_t>(data, sum, w, h, tif);
+            } else if (data.bits_per_val() <= 16) {
                 if (data.is_signed()) expand_stack<std::int16_t>(data, w, h, tif);
                 else expand_stack<std::uint16_t>(data, w, h, tif);
             } else if (data.bits_per_val() <= 32) {

@@ -224,3 +224,39 @@ def synth(dtype, frame0: int, n_frames: int, n_values: int, device="cuda", seed:
         check(lib().trpx_synth_fill(dtype_code(tdt), seed, frame0, n_frames, n_values, out.data_ptr(),
                                     _stream_ptr(out)))
     return out
+
+
+_SUM_OUT = {torch.int32: _lib.I32, torch.uint32: _lib.U32, torch.int64: _lib.I64, torch.uint64: _lib.U64,
+            torch.float32: _lib.F32, torch.float64: _lib.F64}
+
+
+def decode_sum_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, group: int, block: int = BLOCK) -> int:
+    return lib().trpx_decode_sum_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block, group)
+
+
+def decode_sum(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, group: int,
+               out_dtype=torch.int32, index: torch.Tensor | None = None, out: torch.Tensor | None = None,
+               workspace: Workspace | None = None, status: torch.Tensor | None = None, block: int = BLOCK):
+    """Sums of ``group`` consecutive frames of a stack resident on the GPU (trpx_decode_sum), without decoding it to memory.
+
+    ``dtype`` is the stream's pixel type; ``out_dtype`` one of int32, uint32, int64, uint64, float32, float64.  Returns
+    (sums [ceil(n_frames / group), n_values], status); asynchronous on the current stream, like ``decode``.
+    ``frame_offsets = None``: the frames are located first; ``index = None``: the decode index is built on the way."""
+    odt = torch_dtype(out_dtype)
+    if odt not in _SUM_OUT:
+        raise TypeError(f"decode_sum: out_dtype {odt} (int32, uint32, int64, uint64, float32, float64)")
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    n_out = -(-n_frames // group) if group > 0 else 0
+    if out is None:
+        out = torch.empty((n_out, n_values), dtype=odt, device=dev)
+    if status is None:
+        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    ws_bytes = lib().trpx_decode_sum_workspace_bytes(code, terse.numel(), n_values, n_frames, block, group)
+    ws = (workspace or Workspace(dev)).get(ws_bytes)
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_sum(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(),
+                                    frame_offsets.data_ptr() if frame_offsets is not None else None,
+                                    index.data_ptr() if index is not None else None, n_values, n_frames, block, group,
+                                    out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+    return out, status

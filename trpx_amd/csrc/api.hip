@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/trpx_hip.h"
+#include "decode_sum.hpp"
 #include "encode_kernels.hpp"
 #include "profile.hpp"
 
@@ -834,6 +835,143 @@ int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_v
     HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
     if (st[0]) return fail((int)st[0], "trpx_frame_offsets_host: corrupt or truncated stack");
     HIP_TRY(copy_sync(hs, frame_offsets, d_off.p, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+}  // extern "C"
+// ---- summing decode (decode_sum.hip) -------------------------------------------------------------------------------------
+namespace {
+bool sum_out_ok(int out_dtype) {
+    return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_I64 || out_dtype == TRPX_U64 ||
+           out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
+}
+size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
+// workspace: [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)] [partial slab]
+struct SumWs { size_t offsets, region, partial, total; };
+SumWs sum_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, size_t group, bool have_offsets, bool have_index) {
+    SumWs w;
+    w.offsets = 0;
+    w.region = have_offsets ? 0 : trpx::align_up(8 * (n_frames + 1), 256);
+    const size_t idx = have_index ? 0 : idx_layout(g, n_frames, trpx_dtype_size(dtype)).total;
+    const size_t loc = have_offsets ? 0 : trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
+    w.partial = w.region + trpx::align_up(std::max(idx, loc), 256);
+    w.total = w.partial + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes;
+    return w;
+}
+}  // namespace
+
+extern "C" {
+
+size_t trpx_decode_sum_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                       unsigned group) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != (unsigned)trpx::kBlock || !group || !terse_bytes ||
+        !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
+        return 0;
+    return sum_ws(dtype, g, terse_bytes, n_frames, group, false, false).total;
+}
+
+int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                    const void* index, size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out,
+                    uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: no decode index for 64-bit containers");
+    if (dtype < TRPX_U8 || dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: unknown stream dtype %d", dtype);
+    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: out_dtype %d (I32, U32, I64, U64, F32, F64)", out_dtype);
+    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: block=%u (the decode index needs 12)", block);
+    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
+        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: signed stream into an unsigned output (Terse.hpp:356-357)");
+    if (group == 0) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: group = 0");
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0 || n_frames > terse_bytes)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (!terse || !sums_out || !status) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null pointer");
+    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: an index needs its frame offsets");
+    if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 ||
+        (uintptr_t)workspace % 8 || (uintptr_t)sums_out % sum_out_size(out_dtype))
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: misaligned pointer (terse 4 B, offsets / workspace 8 B, index 16 B, sums their type)");
+    if (8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block) >= 0xF0000000ull)
+        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: frames of >= 2^32 bits");
+    const SumWs w = sum_ws(dtype, g, terse_bytes, n_frames, group, frame_offsets != nullptr, index != nullptr);
+    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sum: workspace %zu < %zu", workspace_bytes, w.total);
+    if (w.total && !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null workspace");
+    const trpx::SumPlan p = trpx::sum_plan(dtype, g, n_frames, group);
+    if (p.n_out * p.chunks * (uint64_t)p.tpf >= (1ull << 40)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes");
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);
+    const uint32_t max_w = 8u * (uint32_t)trpx_dtype_size(dtype);
+    bool clear = true;
+    if (!frame_offsets) {                                                       // index-free: locate the frames first (its scratch: the index region)
+        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
+        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, offs, status, ws + w.region, st));
+        frame_offsets = offs;
+        clear = false;                                                          // (the locator's verdict stays)
+    }
+    if (!index) {                                                               // the walk of trpx_build_index, into the workspace
+        const int rc = build_index_impl(dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, ws + w.region, status,
+                                        clear, stream);
+        if (rc) return rc;
+        index = ws + w.region;
+        clear = false;
+    }
+    const IdxLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
+    trpx::SumArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.geom = g;
+    a.n_frames = n_frames;
+    a.group = group;
+    a.n_out = p.n_out;
+    a.tpf = p.tpf;
+    a.chunks = p.chunks;
+    a.fpc = p.fpc;
+    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.group_off);
+    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    a.out = sums_out;
+    a.out_code = out_dtype;
+    a.partial = p.chunks > 1 ? ws + w.partial : nullptr;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_sum(dtype, a, clear, st));
+    return TRPX_OK;
+}
+
+int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                         size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out, int device) {
+    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_decode_sum_host: no HIP device");
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    trpx::FrameGeom g;
+    if (!terse || !sums_out || !terse_bytes || !sum_out_ok(out_dtype) || !group)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad argument");
+    if (block != (unsigned)trpx::kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum_host: block=%u dtype=%d", block, dtype);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad sizes");
+    const size_t ws_bytes = trpx_decode_sum_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group);
+    if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad dtype/sizes");
+    const size_t out_bytes = (n_frames + group - 1) / group * n_values * sum_out_size(out_dtype);
+    struct { void* p = nullptr; } d_in, d_out, d_off, d_st, d_ws;
+    Arena& A = arena();
+    hipStream_t hs = nullptr;
+    HIP_TRY(A.get_stream(&hs));
+    HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
+    HIP_TRY(A.get(Arena::kPixels, out_bytes, &d_out.p));
+    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
+    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws.p));
+    HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));
+    HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
+    if (frame_offsets) {
+        HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1), &d_off.p));
+        HIP_TRY(copy_sync(hs, d_off.p, frame_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
+    }
+    const int rc = trpx_decode_sum(dtype, out_dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes,
+                                   frame_offsets ? static_cast<const uint64_t*>(d_off.p) : nullptr, nullptr, n_values, n_frames,
+                                   block, group, d_out.p, static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(hs));
+    uint32_t st[TRPX_STATUS_WORDS];
+    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
+    if (st[0]) return fail((int)st[0], "trpx_decode_sum_host: corrupt or truncated stream (device status %u)", st[0]);
+    HIP_TRY(copy_sync(hs, sums_out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

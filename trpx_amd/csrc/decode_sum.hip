@@ -1,0 +1,362 @@
+// Summing decode (trpx_decode_sum): a stack with its decode index -> sums of `group` consecutive frames, without writing the
+// decoded frames.  The work unit is (output j, tile t, frame chunk c): one 256-thread workgroup walks the frames of its chunk
+// through the tile geometry of k_unpack_tiles (unpack_tile.hpp) and keeps the sums of its 12 * kSub values per lane in
+// registers; only the sums leave the workgroup, once, through LDS as whole lines.
+//
+//   per frame   widths -> lengths -> wave/LDS scan -> the tile's stream dwords (registers -> LDS) -> width-specialised
+//               extraction (UnpackDispatch) -> register accumulators.  Software-pipelined: while frame f is extracted from
+//               LDS, the stream dwords of frame f + 1 are in flight to registers and the widths of frame f + 2 are loaded.
+//   accumulate  u32 for 8/16-bit streams (two's complement: exact for up to 65 535 frames per chunk, signed included),
+//               u64 for 32-bit streams.
+//   chunks      few outputs (group = n_frames) leave the GPU idle: each group's frames are split over `chunks` chunks so that
+//               about kSumTargetUnits workgroups run; each chunk writes its raw accumulators to a partial slab in the
+//               workspace and k_sum_reduce adds the chunks in a fixed order and converts.  Integer sums: the result does not
+//               depend on the split.
+// HBM traffic: stream + widths (+ group offsets) read once, n_out * n_values sums written (+ 2 x the partial slab when split).
+#include "codec_common.hpp"
+#include "decode_sum.hpp"
+#include "unpack_common.hpp"
+#include "unpack_tile.hpp"
+#include <limits.h>
+#include <type_traits>
+
+namespace trpx {
+
+namespace {
+
+// 512 blocks per tile for every pixel type (k_unpack_tiles: 1024 for 8/16-bit pixels): the accumulators stay at 24 per lane
+template <typename T> constexpr int sum_sub_tiles() { return kSumSubTiles; }
+template <typename T> constexpr int sum_image_dwords() { return kSumSubTiles * ((kThreads * max_block_bits<T>() + 31) / 32) + 12; }
+template <typename T> using SumAcc = std::conditional_t<PixelTraits<T>::bits == 32, uint64_t, uint32_t>;
+template <typename T> constexpr int sum_stage_dwords() {   // LDS: the tile's stream image, reused for the sums (4 waves x 768 x 8 B)
+    return sum_image_dwords<T>() > 2 * kThreads * kBlock ? sum_image_dwords<T>() : 2 * kThreads * kBlock;
+}
+// stream dwords held in registers per lane while the previous frame is extracted (4 per load, all 256 lanes)
+template <typename T> constexpr int sum_prefetch_loads() { return (sum_image_dwords<T>() + 4 * kThreads - 1) / (4 * kThreads); }
+
+// The exact sum s -> one element of the output type: 32-bit integers clamp (Bit_pointer.hpp:747-763), 64-bit integers keep
+// it, float / double round it once to nearest even.  kPart32 / kPart64: a chunk's raw accumulator (partial slab).
+__device__ __forceinline__ void put_sum(void* __restrict__ out, uint64_t i, int code, int64_t s) {
+    switch (code) {
+    case kSumI32: static_cast<int32_t*>(out)[i] = (int32_t)(s > INT_MAX ? (int64_t)INT_MAX : s < INT_MIN ? (int64_t)INT_MIN : s); break;
+    case kSumU32: static_cast<uint32_t*>(out)[i] = (uint32_t)(s > (int64_t)UINT_MAX ? (int64_t)UINT_MAX : s < 0 ? 0 : s); break;
+    case kSumI64: static_cast<int64_t*>(out)[i] = s; break;
+    case kSumU64: static_cast<uint64_t*>(out)[i] = (uint64_t)s; break;
+    case kSumF32: static_cast<float*>(out)[i] = (float)s; break;
+    case kSumF64: static_cast<double*>(out)[i] = (double)s; break;
+    case kSumPart32: static_cast<uint32_t*>(out)[i] = (uint32_t)s; break;
+    case kSumPart64: static_cast<uint64_t*>(out)[i] = (uint64_t)s; break;
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ int64_t acc_value(SumAcc<T> a) {
+    if constexpr (PixelTraits<T>::bits == 32) return (int64_t)a;
+    else if constexpr (PixelTraits<T>::is_signed) return (int64_t)(int32_t)a;
+    else return (int64_t)a;
+}
+
+// what a frame's tile needs before its scan: the lanes' widths and the frame / tile positions
+template <typename T> struct SumPre {
+    uint32_t w[sum_sub_tiles<T>()], wp[sum_sub_tiles<T>()];
+    uint64_t fo, fe, t_off;
+};
+// ... and after it
+template <typename T> struct SumCur {
+    uint32_t w[sum_sub_tiles<T>()], hl[sum_sub_tiles<T>()], off[sum_sub_tiles<T>()];
+    int nb[sum_sub_tiles<T>()];
+    uint32_t tile_bits, n_dw, img_bit0;
+    uint64_t d_lo;
+};
+
+template <typename T>
+__device__ __forceinline__ void sum_load_pre(SumPre<T>& p, const uint64_t* __restrict__ frame_offsets, const FrameGeom& g,
+                                             uint64_t frame, uint32_t t, const uint8_t* __restrict__ widths,
+                                             const uint64_t* __restrict__ tile_off) {
+    constexpr int kSub = sum_sub_tiles<T>();
+    const uint32_t b0 = t * kSub * kThreads;
+    const uint8_t* __restrict__ wf = widths + frame * g.n_blocks;
+#pragma unroll
+    for (int r = 0; r < kSub; ++r) {
+        const uint32_t b = b0 + r * kThreads + threadIdx.x;
+        p.w[r] = 0; p.wp[r] = 0;
+        if (b < g.n_blocks) {
+            p.w[r] = wf[b];
+            p.wp[r] = b ? wf[b - 1] : 0u;                   // significant_bits = 0 at frame start (Terse.hpp:359)
+        }
+    }
+    // vector loads (the index in a VGPR): a scalar load in flight shares lgkmcnt with LDS, and every LDS access of the frame
+    // being extracted would wait for it
+    uint64_t fi = frame, ti = frame * g.n_tiles + (uint64_t)t * kSub;   // (walk records every 256 blocks)
+    asm volatile("" : "+v"(fi));
+    asm volatile("" : "+v"(ti));
+    p.fo = frame_offsets[fi];
+    p.fe = frame_offsets[fi + 1];
+    p.t_off = tile_off[ti];
+}
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+}
+
+// widths -> bit offsets inside the tile (unpack_tile's scan).  Returns false when the index does not fit the frame or the
+// LDS image (uniform over the workgroup: every lane sees the same positions and totals).
+template <typename T>
+__device__ __forceinline__ bool sum_scan(SumCur<T>& c, const SumPre<T>& p, const FrameGeom& g, uint32_t t, uint64_t terse_bytes,
+                                         uint32_t* __restrict__ s_wtot) {
+    constexpr int kSub = sum_sub_tiles<T>();
+    const int lane = lane_id(), wave = wave_id();
+    const uint32_t b0 = t * kSub * kThreads;
+    uint32_t len[kSub], inc[kSub];
+#pragma unroll
+    for (int r = 0; r < kSub; ++r) {
+        const uint32_t b = b0 + r * kThreads + threadIdx.x;
+        c.w[r] = p.w[r];
+        c.nb[r] = 0; c.hl[r] = 0;
+        if (b < g.n_blocks) {
+            const uint64_t first = (uint64_t)b * kBlock;
+            c.nb[r] = first + kBlock <= g.n_values ? kBlock : (int)(g.n_values - first);
+            c.hl[r] = header_len(p.w[r], p.wp[r]);
+        }
+        len[r] = c.nb[r] ? c.hl[r] + (uint32_t)c.nb[r] * p.w[r] : 0u;
+        inc[r] = wave_inclusive_scan(len[r]);
+        if (lane == 63) s_wtot[r * 4 + wave] = inc[r];
+    }
+    __syncthreads();
+    {
+        const uint32_t tot = lane < kSub * 4 ? s_wtot[lane] : 0u;
+        const uint32_t incl = wave_inclusive_scan(tot);
+        const uint32_t excl = incl - tot;
+#pragma unroll
+        for (int r = 0; r < kSub; ++r) c.off[r] = (uint32_t)__shfl((int)excl, r * 4 + wave, 64) + inc[r] - len[r];
+        c.tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, kSub * 4 - 1);
+    }
+    const uint64_t fo = uniform64(p.fo), fe = uniform64(p.fe), t_off = uniform64(p.t_off);
+    if (fe > terse_bytes || fe <= fo || t_off > 8 * (fe - fo) || c.tile_bits > 8 * (fe - fo) - t_off)
+        return false;                                       // chain / index inconsistent with the frame
+    const uint64_t a0 = 8 * fo + t_off;
+    c.d_lo = (a0 >> 5) & ~3ull;                             // 16-byte aligned start (terse is 4-byte aligned: use dwords)
+    c.n_dw = (uint32_t)(((a0 + c.tile_bits + 31) >> 5) - c.d_lo) + 1;   // + 1: alignbit peeks one dword further
+    c.img_bit0 = (uint32_t)(a0 - 32 * c.d_lo);
+    return c.n_dw <= (uint32_t)(sum_image_dwords<T>() - 8);   // (widths above the type's: more bits than the image holds)
+}
+
+template <typename T>
+__device__ __forceinline__ void sum_fetch(uint4 (&R)[sum_prefetch_loads<T>()], const SumCur<T>& c, const uint8_t* __restrict__ terse,
+                                          uint64_t terse_bytes) {
+    const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(terse);
+    const uint64_t total_dw = (terse_bytes + 3) / 4;
+    const bool base16 = ((uintptr_t)terse & 15) == 0;
+#pragma unroll
+    for (int k = 0; k < sum_prefetch_loads<T>(); ++k) {
+        const uint32_t i = threadIdx.x * 4 + k * kThreads * 4;
+        if (i < c.n_dw) {
+            const uint64_t d = c.d_lo + i;
+            uint4 x;
+            if (base16 && d + 4 <= total_dw) x = *reinterpret_cast<const uint4*>(s32 + d);
+            else {
+                x.x = d < total_dw ? s32[d] : 0u; x.y = d + 1 < total_dw ? s32[d + 1] : 0u;
+                x.z = d + 2 < total_dw ? s32[d + 2] : 0u; x.w = d + 3 < total_dw ? s32[d + 3] : 0u;
+            }
+            R[k] = x;
+        }
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void sum_stage(uint32_t* __restrict__ s_image, const uint4 (&R)[sum_prefetch_loads<T>()], uint32_t n_dw) {
+#pragma unroll
+    for (int k = 0; k < sum_prefetch_loads<T>(); ++k) {
+        const uint32_t i = threadIdx.x * 4 + k * kThreads * 4;
+        if (i < n_dw) *reinterpret_cast<uint4*>(&s_image[i]) = R[k];
+    }
+}
+
+// The frame's fields from the LDS image, added to the lane's accumulators.  Returns false for a width above the type's.
+template <typename T>
+__device__ __forceinline__ bool sum_extract(SumAcc<T> (&acc)[sum_sub_tiles<T>()][kBlock], const SumCur<T>& c,
+                                            const uint32_t* __restrict__ s_image) {
+    constexpr int kSub = sum_sub_tiles<T>();
+    constexpr uint32_t bits = (uint32_t)PixelTraits<T>::bits;
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < kSub; ++r) {
+        const uint32_t q = c.img_bit0 + c.off[r] + c.hl[r];  // first payload bit in the image
+        uint32_t u[kBlock];
+#pragma unroll
+        for (int k = 0; k < kBlock; ++k) u[k] = 0u;         // w == 0 -> zeros (Terse.hpp:373-374)
+        if (c.nb[r] && c.w[r] > bits) ok = false;
+        uint64_t todo = __ballot(c.nb[r] == kBlock && c.w[r] != 0u);
+        while (todo) {
+            const int l0 = __builtin_ctzll(todo);
+            const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)c.w[r], l0);
+            const bool mine = c.nb[r] == kBlock && c.w[r] == w0;
+            uint32_t wd = w0 > bits ? bits : w0;
+            asm volatile("" : "+s"(wd));                    // (the dispatch stays scalar)
+            uint32_t qq = q;
+            asm volatile("" : "+v"(qq));                    // keep the specialised bodies out of LICM's reach
+            if (mine) UnpackDispatch<T, 1, PixelTraits<T>::bits>::run(s_image, qq, wd, u);
+            todo &= ~__ballot(mine);
+        }
+        if (c.nb[r] && c.nb[r] < kBlock) {                  // the frame's last, partial block: generic
+            const uint32_t ww = c.w[r] > bits ? 0u : c.w[r];
+            const uint32_t mask = ww >= 32u ? 0xFFFFFFFFu : ((1u << ww) - 1u);
+            uint32_t p = q;
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) {
+                if (k < c.nb[r] && ww) {
+                    const uint64_t two = (uint64_t)s_image[p >> 5] | ((uint64_t)s_image[(p >> 5) + 1] << 32);
+                    uint32_t f = (uint32_t)(two >> (p & 31u)) & mask;
+                    if (PixelTraits<T>::is_signed) f = (uint32_t)((int32_t)(f << (32u - ww)) >> (32u - ww));
+                    u[k] = f;
+                    p += ww;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kBlock; ++k) {
+            if constexpr (PixelTraits<T>::bits == 32)
+                acc[r][k] += PixelTraits<T>::is_signed ? (uint64_t)(int64_t)(int32_t)u[k] : (uint64_t)u[k];
+            else acc[r][k] += u[k];                         // (sign-extended to 32 bits: two's complement sums)
+        }
+    }
+    return ok;
+}
+
+}  // namespace
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_sum_tiles(SumArgs a) {
+    constexpr int kSub = sum_sub_tiles<T>();
+    __shared__ __attribute__((aligned(16))) uint32_t s_image[sum_stage_dwords<T>()];
+    __shared__ uint32_t s_wtot[kSub * 4];
+    if (a.status[0] != 0) return;                           // corrupt chain (the walk or the locator said so): produce nothing
+    const FrameGeom g = a.geom;
+    const uint64_t units = (uint64_t)a.n_out * a.chunks * a.tpf;
+    for (uint64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const uint32_t t = (uint32_t)(unit % a.tpf);        // adjacent workgroups: adjacent tiles of one output
+        const uint64_t rest = unit / a.tpf;
+        const uint32_t ch = (uint32_t)(rest % a.chunks);
+        const uint64_t j = rest / a.chunks;
+        const uint64_t g0 = j * a.group;
+        const uint64_t g1 = g0 + a.group < a.n_frames ? g0 + a.group : a.n_frames;
+        const uint64_t f0 = g0 + (uint64_t)ch * a.fpc;      // (past g1 for the empty chunks of a short last group: zeros)
+        const uint64_t f1 = f0 + a.fpc < g1 ? f0 + a.fpc : g1;
+
+        SumAcc<T> acc[kSub][kBlock];
+#pragma unroll
+        for (int r = 0; r < kSub; ++r)
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) acc[r][k] = 0;
+        bool bad = false;
+        uint4 R[sum_prefetch_loads<T>()];
+        SumPre<T> pn;
+        SumCur<T> cur;
+        if (f0 < f1) {
+            sum_load_pre(pn, a.frame_offsets, g, f0, t, a.widths, a.tile_off);
+            bad = !sum_scan(cur, pn, g, t, a.terse_bytes, s_wtot);
+            if (!bad) sum_fetch<T>(R, cur, a.terse, a.terse_bytes);
+            if (f0 + 1 < f1) sum_load_pre(pn, a.frame_offsets, g, f0 + 1, t, a.widths, a.tile_off);
+        }
+        for (uint64_t f = f0; f < f1 && !bad; ++f) {
+            __syncthreads();                                // (the previous frame's extraction is done with the image)
+            sum_stage<T>(s_image, R, cur.n_dw);
+            __syncthreads();
+            SumCur<T> nxt;
+            if (f + 1 < f1) {                               // frame f + 1: scan, then its stream is in flight during f's extraction
+                bad = !sum_scan(nxt, pn, g, t, a.terse_bytes, s_wtot);
+                if (!bad) sum_fetch<T>(R, nxt, a.terse, a.terse_bytes);
+                if (f + 2 < f1) sum_load_pre(pn, a.frame_offsets, g, f + 2, t, a.widths, a.tile_off);
+            }
+            if (!sum_extract<T>(acc, cur, s_image)) atomicMax(&a.status[0], (uint32_t)kSumCorrupt);
+            cur = nxt;
+        }
+        if (bad && threadIdx.x == 0) atomicMax(&a.status[0], (uint32_t)kSumCorrupt);
+
+        // ---- the sums leave once: per wavefront, its 64 blocks (768 values) as int64 through LDS, then consecutive elements
+        // per lane (every store instruction writes whole lines)
+        const int lane = lane_id(), wave = wave_id();
+        int64_t* const row = reinterpret_cast<int64_t*>(s_image) + wave * (kWave * kBlock);
+        const bool part = a.partial != nullptr;
+        void* const dst = part ? a.partial : a.out;
+        const int code = part ? (PixelTraits<T>::bits == 32 ? kSumPart64 : kSumPart32) : a.out_code;
+        const uint64_t base = part ? ((uint64_t)ch * a.n_out + j) * g.n_values : j * g.n_values;
+#pragma unroll
+        for (int r = 0; r < kSub; ++r) {
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) row[lane * kBlock + k] = acc_value<T>(acc[r][k]);
+            __syncthreads();
+            const uint64_t first = ((uint64_t)t * kSub * kThreads + (uint64_t)r * kThreads + (uint64_t)wave * kWave) * kBlock;
+            if (first < g.n_values) {
+                const uint32_t n_valid = g.n_values - first < (uint64_t)(kWave * kBlock) ? (uint32_t)(g.n_values - first) : kWave * kBlock;
+                for (uint32_t e = lane; e < n_valid; e += kWave) put_sum(dst, base + first + e, code, row[e]);
+            }
+        }
+        __syncthreads();                                    // (the next unit's first frame reuses the image)
+    }
+}
+
+// partial slabs [chunks][n_out * n_values] -> the sums, added in chunk order and converted
+__global__ __launch_bounds__(kThreads) void k_sum_reduce(const void* __restrict__ partial, int acc64, int acc_signed, uint32_t chunks,
+                                                          uint64_t n_elems, void* __restrict__ out, int code) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n_elems; i += (uint64_t)gridDim.x * kThreads) {
+        int64_t s = 0;
+        for (uint32_t c = 0; c < chunks; ++c) {
+            if (acc64) s += (int64_t)static_cast<const uint64_t*>(partial)[(uint64_t)c * n_elems + i];
+            else {
+                const uint32_t v = static_cast<const uint32_t*>(partial)[(uint64_t)c * n_elems + i];
+                s += acc_signed ? (int64_t)(int32_t)v : (int64_t)v;
+            }
+        }
+        put_sum(out, i, code, s);
+    }
+}
+
+SumPlan sum_plan(int dtype, const FrameGeom& g, uint64_t n_frames, uint64_t group) {
+    SumPlan p;
+    const uint32_t kSub = kSumSubTiles;
+    p.tpf = (g.n_blocks + kSub * kThreads - 1) / (kSub * kThreads);
+    p.n_out = (n_frames + group - 1) / group;
+    const uint64_t per_group = group < n_frames ? group : n_frames;
+    const uint64_t max_fpc = dtype >= 4 ? 0xFFFFFFFFull : 65535ull;   // 32-bit accumulators: 65 535 frames of 8/16-bit values
+    const uint64_t units = p.n_out * p.tpf;
+    uint64_t chunks = units < kSumTargetUnits ? (kSumTargetUnits + units - 1) / units : 1;
+    if (chunks > per_group) chunks = per_group;
+    uint64_t fpc = (per_group + chunks - 1) / chunks;
+    if (fpc > max_fpc) fpc = max_fpc;
+    p.fpc = (uint32_t)fpc;
+    p.chunks = (uint32_t)((per_group + fpc - 1) / fpc);
+    p.partial_bytes = p.chunks > 1 ? align_up((uint64_t)p.chunks * p.n_out * g.n_values * (dtype >= 4 ? 8 : 4), 256) : 0;
+    return p;
+}
+
+template <typename T>
+static hipError_t launch_sum_t(const SumArgs& a, hipStream_t st) {
+    const uint64_t units = (uint64_t)a.n_out * a.chunks * a.tpf;
+    const uint32_t grid = (uint32_t)(units < (1ull << 22) ? units : (1ull << 22));
+    hipLaunchKernelGGL((k_sum_tiles<T>), dim3(grid), dim3(kThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_sum(int dtype, const SumArgs& a, bool clear_status, hipStream_t st) {
+    if (clear_status) zero_status(a.status, st);
+    hipError_t e = hipErrorInvalidValue;
+    switch (dtype) {
+    case 0: e = launch_sum_t<uint8_t>(a, st); break;
+    case 1: e = launch_sum_t<int8_t>(a, st); break;
+    case 2: e = launch_sum_t<uint16_t>(a, st); break;
+    case 3: e = launch_sum_t<int16_t>(a, st); break;
+    case 4: e = launch_sum_t<uint32_t>(a, st); break;
+    case 5: e = launch_sum_t<int32_t>(a, st); break;
+    }
+    if (e != hipSuccess || !a.partial) return e;
+    const uint64_t n = a.n_out * a.geom.n_values;
+    const uint64_t blocks = (n + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(k_sum_reduce, dim3((uint32_t)(blocks < 8192 ? blocks : 8192)), dim3(kThreads), 0, st, a.partial,
+                       dtype >= 4 ? 1 : 0, dtype & 1, a.chunks, n, a.out, a.out_code);
+    return hipGetLastError();
+}
+
+}  // namespace trpx

@@ -181,6 +181,30 @@ class Terse:
                                              out.ctypes.data, self._device))
         return out
 
+    def prolix_sum(self, group: int | None = None, dtype=np.int64) -> np.ndarray:
+        """Sums of ``group`` consecutive frames (``None``: all frames) in ONE GPU call (trpx_decode_sum_host), without
+        decoding the stack to memory; returns [ceil(number_of_frames / group), size] of ``dtype`` (int32 / uint32 clamp,
+        int64 / uint64 exact, float32 / float64 rounded once)."""
+        f = self.number_of_frames()
+        if group is None:
+            group = f
+        if group < 1:
+            raise ValueError("group must be >= 1")
+        if self._signed and np.dtype(dtype).kind == "u":
+            raise ValueError("signed data cannot be decompressed into unsigned data")            # Terse.hpp:356-357
+        if self._prolix_bits > 32:
+            raise ValueError("prolix_sum: values of more than 32 bits are not supported")
+        bits = 8 if self._prolix_bits <= 8 else 16 if self._prolix_bits <= 16 else 32
+        stream = {8: _lib.U8, 16: _lib.U16, 32: _lib.U32}[bits] + int(self._signed)
+        out = np.empty((-(-f // group) if f else 0, self._size), np.dtype(dtype))
+        if f == 0:
+            return out
+        buf = np.frombuffer(self._data, np.uint8)
+        offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+        check(lib().trpx_decode_sum_host(stream, _code(dtype, True), buf.ctypes.data, buf.size, offs.ctypes.data, self._size,
+                                         f, self._block, group, out.ctypes.data, self._device))
+        return out
+
     # ---- accessors (Terse.hpp:396-444) --------------------------------------------------------
     def size(self) -> int:
         return self._size
