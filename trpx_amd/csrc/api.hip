@@ -1,12 +1,15 @@
 // C ABI of libtrpx_hip.so (declared in include/trpx_hip.h).  Thin: argument checks, workspace
 // carving, kernel launches on the caller's stream.  No CPU codec lives here: without a gfx950
 // device every compute entry point fails with TRPX_ERR_NO_DEVICE / TRPX_ERR_HIP.
+// Layout: predicates and routes, the one argument prologue, workspace layouts, the device-pointer ABI, then the host
+// staging helpers (Arena, enter, upload_stream, ...) and the host-pointer wrappers built from them.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/trpx_hip.h"
@@ -24,7 +27,6 @@ Profiler& profiler() {
 namespace {
 
 thread_local char g_err[512] = "";
-thread_local bool t_force_two_pass = false;   // trpx_encode_host's retry after a look-back timeout
 
 int fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -39,7 +41,22 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(TRPX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-constexpr unsigned kMaxBlock = 4096;   // generic kernels: tile bit counts stay well inside 32 bits
+constexpr unsigned kMaxBlock = 4096;           // generic kernels: tile bit counts stay well inside 32 bits
+constexpr unsigned kBlock = trpx::kBlock;      // the tuned kernels' block size (Terse.hpp:264), the only one with a decode index
+
+bool is64(int dtype) { return dtype == TRPX_U64 || dtype == TRPX_I64; }
+// element size of a converting decode's output: the integer containers and float / double
+size_t convert_elem_size(int out_dtype) { return out_dtype == TRPX_F32 ? 4 : out_dtype == TRPX_F64 ? 8 : trpx_dtype_size(out_dtype); }
+// the tuned decoders' types: an integer container of <= 32 bits with the stream's signedness (Terse.hpp:356-357)
+bool tuned_type(int stream_signed, int out_dtype) {
+    return trpx_dtype_size(out_dtype) && out_dtype <= TRPX_I32 && (stream_signed != 0) == (trpx_dtype_is_signed(out_dtype) != 0);
+}
+uint64_t worst_frame_bits(int dtype, size_t n_values, unsigned block) { return 8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block); }
+// frame-relative bit positions are kept in 32 bits (with head room for one step's overshoot)
+bool frame_bits_fit_32(int dtype, size_t n_values, unsigned block) { return worst_frame_bits(dtype, n_values, block) < 0xF0000000ull; }
+// the per-frame decoder packs a block's bit position with its width into 32 bits: frames of < 2^26 bits less the walker's ring
+// offset and one step's overshoot
+bool fits_per_frame_decoder(int dtype, size_t n_values, unsigned block) { return worst_frame_bits(dtype, n_values, block) + (1u << 17) < (1ull << 26); }
 
 bool geom_of(size_t n_values, unsigned block, trpx::FrameGeom* g) {
     if (n_values == 0 || block == 0 || block > kMaxBlock) return false;
@@ -59,8 +76,43 @@ bool sizes_ok(const trpx::FrameGeom& g, size_t n_frames) {
     const unsigned __int128 bytes = (unsigned __int128)g.n_values * n_frames * 8;
     return bytes < ((unsigned __int128)1 << 62);
 }
+// the locator and the host wrappers: a geometry that cannot be had is laid to the block size unless that is the tuned one
+int bad_geom(const char* fn, unsigned block) {
+    return fail(block != kBlock ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "%s: unsupported sizes/block (block=%u)", fn, block);
+}
 
-// workspace layouts ------------------------------------------------------------------------
+// ---- the argument prologue of the device-pointer entry points ---------------------------------------------------------------
+// Every error is decided here, before the first device call, in one order: [unknown dtype] -> block size -> 64-bit container ->
+// signedness (all UNSUPPORTED) -> dtype / sizes -> null -> misaligned pointers (all INVALID_ARG).  tests/test_abi_args.py pins
+// the code and the prefix of each; trpx_locate_frames and trpx_decode_sum keep their own, different orders.
+struct PtrReq { const void* p; size_t align; bool required = true; };
+enum : unsigned {
+    kDtypeFirst = 1,     // an unknown dtype is reported in front of the block size (otherwise with the sizes, behind it)
+    kIndexOnly = 2,      // works on a decode index: block = kBlock, containers of <= 32 bits
+    kSameSign = 4,       // the stream's signedness must be the container's
+    kHasStream = 8,      // takes a stream: terse_bytes != 0
+};
+int check_args(const char* fn, unsigned rules, int dtype, size_t elem, int stream_signed, size_t terse_bytes, size_t n_values,
+               size_t n_frames, unsigned block, std::initializer_list<PtrReq> ptrs, trpx::FrameGeom* g) {
+    if ((rules & kDtypeFirst) && !elem) return fail(TRPX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (rules & kIndexOnly ? block != kBlock : block == 0 || block > kMaxBlock)
+        return fail(TRPX_ERR_UNSUPPORTED, rules & kIndexOnly ? "%s: block=%u (the decode index needs %u)" : "%s: block=%u (supported: 1..%u; 12 is the tuned default, Terse.hpp:264)",
+                    fn, block, rules & kIndexOnly ? kBlock : kMaxBlock);
+    if ((rules & kIndexOnly) && is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "%s: no decode index for 64-bit containers (generic kernels)", fn);
+    if ((rules & kSameSign) && (stream_signed != 0) != (trpx_dtype_is_signed(dtype) != 0))
+        return fail(TRPX_ERR_UNSUPPORTED, "%s: stream signed=%d into dtype %d: only same-signedness decode is defined by the reference (Terse.hpp:356-357)",
+                    fn, stream_signed, dtype);
+    if (!elem) return fail(TRPX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
+    if (!geom_of(n_values, block, g) || !sizes_ok(*g, n_frames) || ((rules & kHasStream) && !terse_bytes))
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", fn, n_values, n_frames);
+    for (const PtrReq& q : ptrs)
+        if (q.required && !q.p) return fail(TRPX_ERR_INVALID_ARG, "%s: null pointer", fn);
+    for (const PtrReq& q : ptrs)
+        if ((uintptr_t)q.p % q.align) return fail(TRPX_ERR_INVALID_ARG, "%s: misaligned pointer (%p needs %zu B)", fn, q.p, q.align);
+    return TRPX_OK;
+}
+
+// ---- workspace layouts ------------------------------------------------------------------------------------------------------
 struct EncWs { size_t frame_size, tile_off, tile_bits, fused, total; };
 EncWs enc_ws(const trpx::FrameGeom& g, size_t n_frames) {
     EncWs w;
@@ -73,59 +125,95 @@ EncWs enc_ws(const trpx::FrameGeom& g, size_t n_frames) {
     return w;
 }
 
+// The decode index and the decode workspace are one carve: [front] [tile_off] [widths] | [seg] [defer] [parts] [part_ws].
+// An index has no front and its tile_off is its group offsets; what lies behind the bar is scratch of the walk that
+// writes it.  A workspace starts with the serial walk's frame offsets (walk_offsets, at 0) and leaves room for round 4's
+// parts route as well, which shares `parts` / `part_ws` with the index route (many short parts).  The index a caller
+// builds and the one trpx_decode builds in its workspace agree on everything behind tile_off.
+struct DecLayout { size_t tile_off, widths, seg, defer, parts, part_ws, total; };
+DecLayout dec_layout(const trpx::FrameGeom& g, size_t n_frames, size_t pixel_bytes, size_t front, bool parts_route) {
+    DecLayout l;
+    l.tile_off = trpx::align_up(front, 16);
+    l.widths = trpx::align_up(l.tile_off + 8 * n_frames * (size_t)g.n_tiles, 16);
+    l.seg = trpx::align_up(l.widths + n_frames * (size_t)g.n_blocks, 256);    // scratch of the position-parallel walk
+    l.defer = l.seg + trpx::seg_workspace_bytes(g, n_frames);                  // list of the frames the per-frame walker hands over
+    l.parts = l.defer + trpx::defer_bytes(n_frames);                           // large frames: the part table and its scratch (decode_part.hip)
+    size_t P = trpx::chain_parts_per_frame(g, n_frames, pixel_bytes), scratch = trpx::chain_workspace_bytes(g, n_frames, pixel_bytes);
+    if (parts_route) {
+        P = std::max<size_t>(P, trpx::parts_per_frame(g, n_frames));
+        scratch = std::max(scratch, trpx::part_workspace_bytes(g, n_frames));
+    }
+    l.part_ws = l.parts + (P > 1 ? trpx::align_up(sizeof(trpx::PartDesc) * n_frames * P, 256) : 0);
+    l.total = l.part_ws + scratch;
+    return l;
+}
+// (pixel_bytes: only the scratch behind the index proper depends on it)
+DecLayout idx_layout(const trpx::FrameGeom& g, size_t n_frames, size_t pixel_bytes = 4) { return dec_layout(g, n_frames, pixel_bytes, 0, false); }
+DecLayout dec_ws(const trpx::FrameGeom& g, size_t n_frames, size_t pixel_bytes) { return dec_layout(g, n_frames, pixel_bytes, 8 * (n_frames + 1), true); }
+
+trpx::DecodeArgs decode_args(const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const trpx::FrameGeom& g,
+                             size_t n_frames, void* pixels_out, uint32_t* status) {
+    trpx::DecodeArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.geom = g;
+    a.n_frames = (uint32_t)n_frames;
+    a.pixels_out = pixels_out;
+    a.status = status;
+    return a;
+}
+// points a's index (always) and the scratch asked for into an index or workspace block laid out as l
+enum : unsigned { kSeg = 1, kDefer = 2, kParts = 4 };
+void point_into(trpx::DecodeArgs& a, const void* block, const DecLayout& l, unsigned scratch = 0) {
+    char* b = const_cast<char*>(static_cast<const char*>(block));
+    a.tile_off = reinterpret_cast<uint64_t*>(b + l.tile_off);
+    a.widths = reinterpret_cast<uint8_t*>(b + l.widths);
+    if (scratch & kSeg) a.seg_ws = b + l.seg;
+    if (scratch & kDefer) a.defer = reinterpret_cast<uint32_t*>(b + l.defer + trpx::kDeferFront);
+    if (scratch & kParts) {
+        a.parts = reinterpret_cast<trpx::PartDesc*>(b + l.parts);
+        a.part_ws = b + l.part_ws;
+    }
+}
+
+// ---- routes -----------------------------------------------------------------------------------------------------------------
 // 0 = auto (single-pass encoder), 1 = force the two-pass pipeline.
 // Initialised from $TRPX_ENCODE_PATH ("twopass" / "fused"), changed by trpx_set_encode_path().
 int g_encode_path = [] {
     const char* e = getenv("TRPX_ENCODE_PATH");
     return e && strcmp(e, "twopass") == 0 ? 1 : 0;
 }();
-// Decode route: 0 = auto, 1 = basic (decode.hip), 2 = tiled (position-parallel walk + k_unpack_tiles), 3 = per-frame
-// decoder for any number of frames, 4 = large frames by round 4's parts route (two walks) instead of the index route.
-// Initialised from $TRPX_DECODE_PATH ("basic" / "tiles" / "frames" / "parts"), changed by trpx_set_decode_path().  A forced
-// route is still subject to its preconditions (alignment, block = 12, frame size).
-int g_decode_path = [] {
+// The decode route, with the values trpx_set_decode_path documents.  Initialised from $TRPX_DECODE_PATH ("basic" / "tiles" /
+// "frames" / "parts"), changed by trpx_set_decode_path().  A forced route is still subject to its preconditions (alignment,
+// block = 12, frame size).  Selector 5 / "dense" is no route: it is kRouteAuto plus a flag of decode_seg.hip (set_dense_route).
+enum DecodeRoute {
+    kRouteAuto = 0,
+    kRouteBasic = 1,     // decode.hip
+    kRouteTiled = 2,     // position-parallel walk + k_unpack_tiles
+    kRouteFrames = 3,    // per-frame decoder for any number of frames
+    kRouteParts = 4,     // large frames by round 4's parts route (two walks) instead of the index route
+};
+constexpr int kSelectDense = 5;
+DecodeRoute g_decode_path = [] {
     const char* e = getenv("TRPX_DECODE_PATH");
-    if (!e) return 0;
-    return strcmp(e, "basic") == 0 ? 1 : (strcmp(e, "tiles") == 0 || strcmp(e, "seg") == 0) ? 2 : strcmp(e, "frames") == 0 ? 3
-           : strcmp(e, "parts") == 0 ? 4 : strcmp(e, "dense") == 0 ? (trpx::set_dense_route(true), 0) : 0;
+    if (!e) return kRouteAuto;
+    if (strcmp(e, "dense") == 0) trpx::set_dense_route(true);
+    return strcmp(e, "basic") == 0 ? kRouteBasic : (strcmp(e, "tiles") == 0 || strcmp(e, "seg") == 0) ? kRouteTiled
+           : strcmp(e, "frames") == 0 ? kRouteFrames : strcmp(e, "parts") == 0 ? kRouteParts : kRouteAuto;
 }();
+// Large frames (more than 32 K blocks) take the index route -- one walk of many short parts, decode_part.hip -- unless the tiled
+// route is forced (it walks them position-parallel) or round 4's parts route is.  trpx_decode and trpx_build_index must choose
+// alike for the same stack: both ask here.
+bool large_frames_by_index() { return g_decode_path != kRouteTiled && g_decode_path != kRouteParts; }
 // $TRPX_SINGLE_PART = "frames,blocks": stacks of that many frames and more keep frames of up to that many blocks on the per-frame
 // route (encode_kernels.hpp: single_part_blocks; tuning runs -- the built-in rule otherwise)
-[[maybe_unused]] static const int g_single_part_env = [] {
+[[maybe_unused]] const int g_single_part_env = [] {
     const char* e = getenv("TRPX_SINGLE_PART");
     unsigned f = 0, b = 0;
     if (e && sscanf(e, "%u,%u", &f, &b) == 2) trpx::set_single_part_rule(f, b);
     return 0;
 }();
-struct IdxLayout { size_t group_off, widths, seg, defer, parts, part_ws, total; };
-IdxLayout idx_layout(const trpx::FrameGeom& g, size_t n_frames, size_t pixel_bytes = 4) {   // (pixel_bytes: only the scratch behind the index proper depends on it)
-    IdxLayout l;
-    l.group_off = 0;
-    l.widths = trpx::align_up(8 * n_frames * (size_t)g.n_tiles, 16);
-    l.seg = trpx::align_up(l.widths + n_frames * (size_t)g.n_blocks, 256);   // scratch of trpx_build_index's walk
-    l.defer = l.seg + trpx::seg_workspace_bytes(g, n_frames);                 // list of the frames the per-frame walker hands over
-    l.parts = l.defer + trpx::defer_bytes(n_frames);                          // large frames: the index route's part table and scratch (decode_part.hip)
-    const size_t P = trpx::chain_parts_per_frame(g, n_frames, pixel_bytes);
-    l.part_ws = l.parts + (P > 1 ? trpx::align_up(sizeof(trpx::PartDesc) * n_frames * P, 256) : 0);
-    l.total = l.part_ws + trpx::chain_workspace_bytes(g, n_frames, pixel_bytes);
-    return l;
-}
-struct DecWs { size_t walk_offsets, tile_off, widths, seg, defer, parts, part_ws, total; };
-DecWs dec_ws(const trpx::FrameGeom& g, size_t n_frames, size_t pixel_bytes) {
-    DecWs w;
-    const size_t tiles = n_frames * (size_t)g.n_tiles;
-    w.walk_offsets = 0;
-    w.tile_off = trpx::align_up(w.walk_offsets + 8 * (n_frames + 1), 16);
-    w.widths = trpx::align_up(w.tile_off + 8 * tiles, 16);
-    w.seg = trpx::align_up(w.widths + n_frames * (size_t)g.n_blocks, 256);
-    w.defer = w.seg + trpx::seg_workspace_bytes(g, n_frames);
-    w.parts = w.defer + trpx::defer_bytes(n_frames);                            // large frames on the per-frame route: the part table
-    // (two routes for large frames share these two areas: the index route -- many short parts -- and round 4's parts route)
-    const size_t P = std::max<size_t>(trpx::parts_per_frame(g, n_frames), trpx::chain_parts_per_frame(g, n_frames, pixel_bytes));
-    w.part_ws = w.parts + (P > 1 ? trpx::align_up(sizeof(trpx::PartDesc) * n_frames * P, 256) : 0);
-    w.total = w.part_ws + std::max(trpx::part_workspace_bytes(g, n_frames), trpx::chain_workspace_bytes(g, n_frames, pixel_bytes));
-    return w;
-}
 
 // trpx_decode_indexed's hand-over list (see there): per calling thread, one buffer per (device, stream), grow-only, freed with the thread.
 struct IdxScratch {
@@ -157,6 +245,106 @@ void* indexed_scratch(size_t bytes, hipStream_t st) {
     return p;
 }
 
+int build_index_impl(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                     size_t n_frames, unsigned block, void* index, uint32_t* status, bool clear_status, void* stream) {
+    trpx::FrameGeom g;
+    if (const int rc = check_args("trpx_build_index", kIndexOnly | kHasStream, dtype, trpx_dtype_size(dtype), 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {frame_offsets, 8}, {index, 16}, {status, 8}}, &g))
+        return rc;
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_build_index: frames of >= 2^32 bits");
+    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, nullptr, status);
+    const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
+    point_into(a, index, il, kSeg | kDefer);
+    // frames of < 2^26 bits: the per-frame decoder's walker writes the index (the conditions of trpx_decode's per-frame route)
+    a.index_per_frame = fits_per_frame_decoder(dtype, n_values, block) && g_decode_path != kRouteTiled;
+    a.parts_per_frame = trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(dtype));
+    a.chain = a.parts_per_frame > 1u && n_frames * (uint64_t)a.parts_per_frame < 0x7FFFFFFFull && large_frames_by_index();
+    if (a.chain) point_into(a, index, il, kParts);
+    else a.parts_per_frame = 1;
+    HIP_TRY(trpx::launch_walk_only(a, (uint32_t)(8 * trpx_dtype_size(dtype)), clear_status, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+// trpx_encode / trpx_encode_indexed; two_pass: the retry of the checked entry points after a look-back timeout
+int encode_impl(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out, size_t out_capacity,
+                uint64_t* frame_offsets, uint32_t* status, void* index, void* workspace, size_t workspace_bytes, void* stream,
+                bool two_pass) {
+    trpx::FrameGeom g;
+    if (const int rc = check_args("trpx_encode", kDtypeFirst, dtype, trpx_dtype_size(dtype), 0, 0, n_values, n_frames, block,
+                                  {{pixels, trpx_dtype_size(dtype)}, {frame_offsets, 8}, {status, 8}, {workspace, 8},
+                                   {out, 16, out_capacity != 0}}, &g))   // (out: the kernels' 16-byte stores)
+        return rc;
+    const EncWs w = enc_ws(g, n_frames);
+    if (workspace_bytes < w.total)
+        return fail(TRPX_ERR_CAPACITY, "trpx_encode: workspace %zu < %zu", workspace_bytes, w.total);
+
+    trpx::EncodeArgs a;
+    a.pixels = pixels;
+    a.geom = g;
+    a.n_frames = (uint32_t)n_frames;
+    a.out = out;
+    a.out_capacity = out_capacity;
+    a.frame_offsets = frame_offsets;
+    a.status = status;
+    char* ws = static_cast<char*>(workspace);
+    a.frame_size = reinterpret_cast<uint64_t*>(ws + w.frame_size);
+    a.tile_off = reinterpret_cast<uint64_t*>(ws + w.tile_off);
+    a.tile_bits = reinterpret_cast<uint32_t*>(ws + w.tile_bits);
+    if ((uintptr_t)index % 16) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_indexed: index must be 16-byte aligned");
+    const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
+    a.idx_group_off = index ? reinterpret_cast<uint64_t*>(static_cast<char*>(index) + il.tile_off) : nullptr;
+    a.idx_widths = index ? reinterpret_cast<uint8_t*>(static_cast<char*>(index) + il.widths) : nullptr;
+    if (block != kBlock || is64(dtype)) {  // any other block size, 64-bit containers: generic (correct-first) kernels
+        if (index) return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode_indexed: the decode index needs block=12 and pixels of <= 32 bits");
+        trpx::fused_ws_forget(workspace, workspace_bytes);
+        HIP_TRY(trpx::launch_encode_generic(dtype, a, static_cast<hipStream_t>(stream)));
+        return TRPX_OK;
+    }
+    // (frames need not be vector aligned -- most detectors' pixel counts are not multiples of 4: 1030 x 1065, 2463 x 2527 --: the
+    // kernels' 16-byte accesses only need what the hardware needs, which in HSA's unaligned access mode is nothing)
+    const bool vec_ok = (uint64_t)g.n_blocks * 396 < (1ull << 40);       // frame bits fit the fused encoder's 40-bit accumulator
+    if (g_encode_path == 0 && !two_pass && vec_ok) {
+        trpx::fused_ws_forget(workspace, workspace_bytes, ws + w.fused);   // (a clean descriptor block of another geometry in this memory is no longer)
+        HIP_TRY(trpx::launch_encode_fused(dtype, a, ws + w.fused, static_cast<hipStream_t>(stream)));
+    } else {
+        trpx::fused_ws_forget(workspace, workspace_bytes);
+        HIP_TRY(trpx::launch_encode(dtype, a, static_cast<hipStream_t>(stream)));
+        if (index && out)   // the two-pass pipeline does not emit the index: build it from the stream it just wrote
+            return build_index_impl(dtype, out, out_capacity, frame_offsets, n_values, n_frames, block, index, status, false, stream);
+    }
+    return TRPX_OK;
+}
+
+// copy on the caller's private stream and wait for that stream (never for the device)
+hipError_t copy_sync(hipStream_t hs, void* dst, const void* src, size_t n, hipMemcpyKind kind) {
+    const hipError_t e = hipMemcpyAsync(dst, src, n, kind, hs);
+    return e != hipSuccess ? e : hipStreamSynchronize(hs);
+}
+// the status block of the work queued on hs so far, on the host (waits for hs alone) ...
+int read_status(hipStream_t hs, const uint32_t* d_status, uint32_t st[TRPX_STATUS_WORDS]) {
+    HIP_TRY(copy_sync(hs, st, d_status, 4 * TRPX_STATUS_WORDS, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+// ... and its verdict as a return code
+int status_result(const char* fn, const uint32_t* st) {
+    return st[0] ? fail((int)st[0], "%s: device status %u (5: corrupt or truncated stream)", fn, st[0]) : TRPX_OK;
+}
+
+// Encode and read the status back; after a look-back wait that gave up (TRPX_ERR_TIMEOUT: never seen in practice, keeps the API
+// total) once more through the two-pass pipeline, which has no waits.  (With the two-pass pipeline forced by
+// trpx_set_encode_path the first attempt has no waits either: its status is never TIMEOUT and there is no second one.)
+int encode_retrying(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out, size_t out_capacity,
+                    uint64_t* frame_offsets, uint32_t* status, void* index, void* workspace, size_t workspace_bytes, void* stream,
+                    uint32_t st[TRPX_STATUS_WORDS]) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int rc = encode_impl(dtype, pixels, n_values, n_frames, block, out, out_capacity, frame_offsets, status, index, workspace,
+                             workspace_bytes, stream, attempt == 1);
+        if (rc || (rc = read_status(static_cast<hipStream_t>(stream), status, st))) return rc;   // the caller's stream alone, not the device
+        if (st[0] != TRPX_ERR_TIMEOUT) break;
+    }
+    return TRPX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,7 +362,6 @@ size_t trpx_dtype_size(int dtype) {
     return 0;
 }
 int trpx_dtype_is_signed(int dtype) { return dtype >= 0 && dtype <= TRPX_I32 ? (dtype & 1) : (dtype == TRPX_I64 ? 1 : 0); }
-static bool is64(int dtype) { return dtype == TRPX_U64 || dtype == TRPX_I64; }
 
 int trpx_device_count(void) {
     int n = 0;
@@ -199,226 +386,103 @@ size_t trpx_decode_workspace_bytes(int dtype, size_t n_values, size_t n_frames, 
     if (!trpx_dtype_size(dtype) || !geom_of(n_values, block, &g)) return 0;
     return dec_ws(g, n_frames, trpx_dtype_size(dtype)).total;
 }
-
-unsigned trpx_decode_parts_per_frame(int dtype, size_t n_values, size_t n_frames, unsigned block) {
-    trpx::FrameGeom g;
-    if (!trpx_dtype_size(dtype) || is64(dtype) || block != (unsigned)trpx::kBlock || !geom_of(n_values, block, &g)) return 1;
-    const bool bits32 = 8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block) < 0xF0000000ull;
-    return g_decode_path != 4 && bits32 ? trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(dtype)) : trpx::parts_per_frame(g, n_frames);
-}
-
-static int build_index_impl(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
-                            size_t n_values, size_t n_frames, unsigned block, void* index, uint32_t* status,
-                            bool clear_status, void* stream);
-
 size_t trpx_index_bytes(int dtype, size_t n_values, size_t n_frames, unsigned block) {
     trpx::FrameGeom g;
     if (!trpx_dtype_size(dtype) || !geom_of(n_values, block, &g)) return 0;
     return idx_layout(g, n_frames, trpx_dtype_size(dtype)).total;
 }
 
+unsigned trpx_decode_parts_per_frame(int dtype, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    if (!trpx_dtype_size(dtype) || is64(dtype) || block != kBlock || !geom_of(n_values, block, &g)) return 1;
+    return g_decode_path != kRouteParts && frame_bits_fit_32(dtype, n_values, block) ? trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(dtype))
+                                                                                   : trpx::parts_per_frame(g, n_frames);
+}
+
 int trpx_encode(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out,
                 size_t out_capacity, uint64_t* frame_offsets, uint32_t* status, void* workspace,
                 size_t workspace_bytes, void* stream) {
-    return trpx_encode_indexed(dtype, pixels, n_values, n_frames, block, out, out_capacity, frame_offsets, status,
-                               nullptr, workspace, workspace_bytes, stream);
+    return encode_impl(dtype, pixels, n_values, n_frames, block, out, out_capacity, frame_offsets, status, nullptr, workspace,
+                       workspace_bytes, stream, false);
 }
 
 int trpx_encode_indexed(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out,
                         size_t out_capacity, uint64_t* frame_offsets, uint32_t* status, void* index,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    trpx::FrameGeom g;
-    if (!trpx_dtype_size(dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode: unknown dtype %d", dtype);
-    if (block == 0 || block > kMaxBlock)
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode: block=%u (supported: 1..%u; 12 is the tuned default, Terse.hpp:264)", block, kMaxBlock);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_encode: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    if (!pixels || !frame_offsets || !status || !workspace || (!out && out_capacity))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_encode: null pointer");
-    if (((uintptr_t)out | (uintptr_t)workspace | (uintptr_t)frame_offsets) % 8 || (uintptr_t)out % 16 ||
-        (uintptr_t)status % 8 || (uintptr_t)pixels % trpx_dtype_size(dtype))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_encode: misaligned pointer (out needs 16 B, workspace/offsets 8 B)");
-    const EncWs w = enc_ws(g, n_frames);
-    if (workspace_bytes < w.total)
-        return fail(TRPX_ERR_CAPACITY, "trpx_encode: workspace %zu < %zu", workspace_bytes, w.total);
-
-    trpx::EncodeArgs a;
-    a.pixels = pixels;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.out = out;
-    a.out_capacity = out_capacity;
-    a.frame_offsets = frame_offsets;
-    a.status = status;
-    char* ws = static_cast<char*>(workspace);
-    a.frame_size = reinterpret_cast<uint64_t*>(ws + w.frame_size);
-    a.tile_off = reinterpret_cast<uint64_t*>(ws + w.tile_off);
-    a.tile_bits = reinterpret_cast<uint32_t*>(ws + w.tile_bits);
-    if ((uintptr_t)index % 16) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_indexed: index must be 16-byte aligned");
-    const IdxLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
-    a.idx_group_off = index ? reinterpret_cast<uint64_t*>(static_cast<char*>(index) + il.group_off) : nullptr;
-    a.idx_widths = index ? reinterpret_cast<uint8_t*>(static_cast<char*>(index) + il.widths) : nullptr;
-    if (block != (unsigned)trpx::kBlock || is64(dtype)) {  // any other block size, 64-bit containers: generic (correct-first) kernels
-        if (index) return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode_indexed: the decode index needs block=12 and pixels of <= 32 bits");
-        trpx::fused_ws_forget(workspace, workspace_bytes);
-        HIP_TRY(trpx::launch_encode_generic(dtype, a, static_cast<hipStream_t>(stream)));
-        return TRPX_OK;
-    }
-    // (frames need not be vector aligned -- most detectors' pixel counts are not multiples of 4: 1030 x 1065, 2463 x 2527 --: the
-    // kernels' 16-byte accesses only need what the hardware needs, which in HSA's unaligned access mode is nothing)
-    const bool vec_ok = (uint64_t)g.n_blocks * 396 < (1ull << 40);       // frame bits fit the fused encoder's 40-bit accumulator
-    if (g_encode_path == 0 && !t_force_two_pass && vec_ok) {
-        trpx::fused_ws_forget(workspace, workspace_bytes, ws + w.fused);   // (a clean descriptor block of another geometry in this memory is no longer)
-        HIP_TRY(trpx::launch_encode_fused(dtype, a, ws + w.fused, static_cast<hipStream_t>(stream)));
-    } else {
-        trpx::fused_ws_forget(workspace, workspace_bytes);
-        HIP_TRY(trpx::launch_encode(dtype, a, static_cast<hipStream_t>(stream)));
-        if (index && out)   // the two-pass pipeline does not emit the index: build it from the stream it just wrote
-            return build_index_impl(dtype, out, out_capacity, frame_offsets, n_values, n_frames, block, index, status, false, stream);
-    }
-    return TRPX_OK;
+    return encode_impl(dtype, pixels, n_values, n_frames, block, out, out_capacity, frame_offsets, status, index, workspace,
+                       workspace_bytes, stream, false);
 }
 
 int trpx_encode_checked(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out,
                         size_t out_capacity, uint64_t* frame_offsets, uint32_t* status, void* index, void* workspace,
                         size_t workspace_bytes, void* stream, uint32_t* host_status) {
     uint32_t st[TRPX_STATUS_WORDS] = {0};
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        t_force_two_pass = attempt == 1;                     // (this thread's next call only)
-        const int rc = trpx_encode_indexed(dtype, pixels, n_values, n_frames, block, out, out_capacity, frame_offsets, status,
-                                           index, workspace, workspace_bytes, stream);
-        t_force_two_pass = false;
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
-        HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // the caller's stream alone, not the device
-        if (st[0] != TRPX_ERR_TIMEOUT) break;                // a look-back wait gave up: the two-pass pipeline has no waits
-    }
+    if (const int rc = encode_retrying(dtype, pixels, n_values, n_frames, block, out, out_capacity, frame_offsets, status, index,
+                                       workspace, workspace_bytes, stream, st))
+        return rc;
     if (host_status) memcpy(host_status, st, sizeof st);
-    if (st[0]) return fail((int)st[0], "trpx_encode_checked: device status %u", st[0]);
-    return TRPX_OK;
+    return status_result("trpx_encode_checked", st);
 }
 
 int trpx_decode(int stream_signed, int out_dtype, const uint8_t* terse, size_t terse_bytes,
                 const uint64_t* frame_offsets, size_t n_values, size_t n_frames, unsigned block, void* pixels_out,
                 uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     trpx::FrameGeom g;
-    if (!trpx_dtype_size(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode: unknown dtype %d", out_dtype);
+    const size_t es = trpx_dtype_size(out_dtype);
+    if (!es) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode: unknown dtype %d", out_dtype);
     if (is64(out_dtype))                                   // 64-bit containers: the converting decoder (fields of up to 64 bits)
         return trpx_decode_convert(stream_signed, out_dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, pixels_out,
                                    status, workspace, workspace_bytes, stream);
-    if (block == 0 || block > kMaxBlock)
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode: block=%u (supported: 1..%u)", block, kMaxBlock);
-    if ((stream_signed != 0) != (trpx_dtype_is_signed(out_dtype) != 0))
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode: stream signed=%d into dtype %d: only same-signedness decode "
-                    "is defined by the reference (Terse.hpp:356-357)", stream_signed, out_dtype);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode: bad sizes");
-    if (!terse || !pixels_out || !status || !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode: null pointer");
-    if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8 ||
-        (uintptr_t)pixels_out % trpx_dtype_size(out_dtype))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode: misaligned pointer (terse needs 4 B, workspace 8 B)");
-    const DecWs w = dec_ws(g, n_frames, trpx_dtype_size(out_dtype));
+    if (const int rc = check_args("trpx_decode", kDtypeFirst | kSameSign | kHasStream, out_dtype, es, stream_signed, terse_bytes, n_values, n_frames,
+                                  block, {{terse, 4}, {pixels_out, es}, {status, 8}, {workspace, 8}, {frame_offsets, 8, false}}, &g))
+        return rc;
+    const DecLayout w = dec_ws(g, n_frames, es);
     if (workspace_bytes < w.total)
         return fail(TRPX_ERR_CAPACITY, "trpx_decode: workspace %zu < %zu", workspace_bytes, w.total);
 
+    hipStream_t hs = static_cast<hipStream_t>(stream);
     trpx::fused_ws_forget(workspace, workspace_bytes);      // (an encoder's clean descriptor words in this memory are about to be overwritten)
-    trpx::DecodeArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.pixels_out = pixels_out;
-    a.status = status;
+    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
     char* ws = static_cast<char*>(workspace);
-    a.walk_offsets = reinterpret_cast<uint64_t*>(ws + w.walk_offsets);
-    a.tile_off = reinterpret_cast<uint64_t*>(ws + w.tile_off);
-    a.widths = reinterpret_cast<uint8_t*>(ws + w.widths);
-    a.seg_ws = ws + w.seg;
+    a.walk_offsets = reinterpret_cast<uint64_t*>(ws);
 #ifdef TRPX_DIAGNOSTICS
     static const bool no_defer = getenv("TRPX_NO_DEFER") != nullptr;          // (diagnostic build: the per-frame decoder keeps every frame)
 #else
     constexpr bool no_defer = false;
 #endif
-    a.defer = no_defer ? nullptr : reinterpret_cast<uint32_t*>(ws + w.defer + trpx::kDeferFront);
-    const int route = g_decode_path;                                          // trpx_set_decode_path / $TRPX_DECODE_PATH
-    const bool basic = route == 1, force_tiles = route == 2;
-    const bool bits32 = 8 * (uint64_t)trpx_worst_case_bytes(out_dtype, n_values, block) < 0xF0000000ull;   // 32-bit frame-relative bit offsets
+    point_into(a, ws, w, no_defer ? kSeg : kSeg | kDefer);
+    const bool basic = g_decode_path == kRouteBasic, force_tiles = g_decode_path == kRouteTiled;   // trpx_set_decode_path / $TRPX_DECODE_PATH
+    const bool bits32 = frame_bits_fit_32(out_dtype, n_values, block);
     // no offsets: the frames located by trpx_locate_frames' position-parallel route into walk_offsets, its scratch laid over the
     // regions behind them (nothing the decode writes exists yet), and then the routes a caller with offsets takes.  Elsewhere
     // (the basic or serial route asked for, other sizes, scratch too small): the decode's own serial walk, launch_decode.
-    const uint32_t max_w = 8u * (uint32_t)trpx_dtype_size(out_dtype);
-    const bool located = !frame_offsets && !basic && bits32 && block == (unsigned)trpx::kBlock &&
-                         trpx::locate_parallel(g, terse_bytes, n_frames, max_w) &&
+    const uint32_t max_w = 8u * (uint32_t)es;
+    const bool located = !frame_offsets && !basic && bits32 && block == kBlock && trpx::locate_parallel(g, terse_bytes, n_frames, max_w) &&
                          w.total - w.tile_off >= trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
     if (located) {
-        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, a.walk_offsets, status, ws + w.tile_off,
-                                    static_cast<hipStream_t>(stream)));
-        frame_offsets = a.walk_offsets;
-        a.frame_offsets = frame_offsets;
+        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, a.walk_offsets, status, ws + w.tile_off, hs));
+        a.frame_offsets = frame_offsets = a.walk_offsets;
     }
-    const bool fast_ok = frame_offsets && !basic && bits32 && block == (unsigned)trpx::kBlock;
-    // frames whose worst case fits 2^26 bits: one workgroup per frame, the walk and the extraction overlap inside it -- whatever
+    const bool fast_ok = frame_offsets && !basic && bits32 && block == kBlock;
+    // frames that fit the per-frame decoder: one workgroup per frame, the walk and the extraction overlap inside it -- whatever
     // the number of frames (since the round-3 walker a single 512^2 frame takes 0.10 ms this way against 0.24 ms through the
     // position-parallel walk + tiled extraction, eight 1024^2 frames 0.37 against 0.73 ms); larger frames: the tiled kernels
-    // (the per-frame decoder packs a block's bit position with its width into 32 bits: frames of < 2^26 bits less the
-    // walker's ring offset and one step's overshoot)
-    const bool frame26 = 8 * (uint64_t)trpx_worst_case_bytes(out_dtype, n_values, block) + (1u << 17) < (1ull << 26);
+    const bool frame26 = fits_per_frame_decoder(out_dtype, n_values, block);
     // larger frames, or frames of more than 32 K blocks: cut into parts of the size of a 512 x 512 frame first (decode_part.hip);
     // a part's positions are relative to its own first bit, so the 2^26 limit applies to the part
-    a.chain = route != 4 && route != 2 && bits32;                              // (frame-relative 32-bit positions; a forced tiled route walks large frames position-parallel, as build_index_impl does)
-    a.parts_per_frame = a.chain ? trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(out_dtype)) : trpx::parts_per_frame(g, n_frames);
+    a.chain = large_frames_by_index() && bits32;                               // (frame-relative 32-bit positions)
+    a.parts_per_frame = a.chain ? trpx::chain_parts_per_frame(g, n_frames, es) : trpx::parts_per_frame(g, n_frames);
     const bool parts_ok = a.parts_per_frame > 1u && n_frames * (uint64_t)a.parts_per_frame < 0x7FFFFFFFull && a.defer;
-    if (parts_ok) {
-        a.parts = reinterpret_cast<trpx::PartDesc*>(ws + w.parts);
-        a.part_ws = ws + w.part_ws;
-    } else a.parts_per_frame = 1;
+    if (parts_ok) point_into(a, ws, w, kParts);
+    else a.parts_per_frame = 1;
     if (fast_ok && (parts_ok || (frame26 && trpx::parts_per_frame(g, n_frames) == 1u)) && !force_tiles)
-        HIP_TRY(trpx::launch_decode_frames(out_dtype, a, static_cast<hipStream_t>(stream)));
+        HIP_TRY(trpx::launch_decode_frames(out_dtype, a, hs));
     else if (fast_ok)
-        HIP_TRY(trpx::launch_decode_fast(out_dtype, a, false, static_cast<hipStream_t>(stream)));
+        HIP_TRY(trpx::launch_decode_fast(out_dtype, a, false, hs));
     else
-        HIP_TRY(trpx::launch_decode(out_dtype, a, frame_offsets != nullptr, static_cast<hipStream_t>(stream)));
+        HIP_TRY(trpx::launch_decode(out_dtype, a, frame_offsets != nullptr, hs));
     if (located)                                                               // (the decode cleared the status: the locate's verdict again)
-        HIP_TRY(trpx::launch_locate_status(a.walk_offsets, (uint32_t)n_frames, status, static_cast<hipStream_t>(stream)));
-    return TRPX_OK;
-}
-
-static int build_index_impl(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
-                            size_t n_values, size_t n_frames, unsigned block, void* index, uint32_t* status,
-                            bool clear_status, void* stream) {
-    trpx::FrameGeom g;
-    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_build_index: the decode index needs block=12");
-    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_build_index: no decode index for 64-bit containers (generic kernels)");
-    if (!trpx_dtype_size(dtype) || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || !terse_bytes)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_build_index: bad dtype/sizes");
-    if (!terse || !frame_offsets || !index || !status) return fail(TRPX_ERR_INVALID_ARG, "trpx_build_index: null pointer");
-    if ((uintptr_t)terse % 4 || (uintptr_t)index % 16 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_build_index: misaligned pointer");
-    if (8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block) >= 0xF0000000ull)
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_build_index: frames of >= 2^32 bits");
-    const IdxLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
-    trpx::DecodeArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.status = status;
-    a.tile_off = reinterpret_cast<uint64_t*>(static_cast<char*>(index) + il.group_off);
-    a.widths = reinterpret_cast<uint8_t*>(static_cast<char*>(index) + il.widths);
-    a.seg_ws = static_cast<char*>(index) + il.seg;
-    a.defer = reinterpret_cast<uint32_t*>(static_cast<char*>(index) + il.defer + trpx::kDeferFront);
-    // frames of < 2^26 bits: the per-frame decoder's walker writes the index (the conditions of trpx_decode's per-frame route)
-    a.index_per_frame = 8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block) + (1u << 17) < (1ull << 26) && g_decode_path != 2;
-    // frames of more than 32 K blocks: the index route's one walk of many short parts (decode_part.hip), unless the tiled route is forced
-    a.parts_per_frame = trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(dtype));
-    a.chain = a.parts_per_frame > 1u && n_frames * (uint64_t)a.parts_per_frame < 0x7FFFFFFFull && g_decode_path != 2 && g_decode_path != 4;
-    if (a.chain) {
-        a.parts = reinterpret_cast<trpx::PartDesc*>(static_cast<char*>(index) + il.parts);
-        a.part_ws = static_cast<char*>(index) + il.part_ws;
-    } else a.parts_per_frame = 1;
-    HIP_TRY(trpx::launch_walk_only(a, (uint32_t)(8 * trpx_dtype_size(dtype)), clear_status, static_cast<hipStream_t>(stream)));
+        HIP_TRY(trpx::launch_locate_status(a.walk_offsets, (uint32_t)n_frames, status, hs));
     return TRPX_OK;
 }
 
@@ -431,34 +495,18 @@ int trpx_decode_indexed(int stream_signed, int out_dtype, const uint8_t* terse, 
                         const uint64_t* frame_offsets, const void* index, size_t n_values, size_t n_frames,
                         unsigned block, void* pixels_out, uint32_t* status, void* stream) {
     trpx::FrameGeom g;
-    if (!trpx_dtype_size(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_indexed: unknown dtype %d", out_dtype);
-    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_indexed: block=%u", block);
-    if (is64(out_dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_indexed: no decode index for 64-bit containers (generic kernels)");
-    if ((stream_signed != 0) != (trpx_dtype_is_signed(out_dtype) != 0))
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_indexed: only same-signedness decode (Terse.hpp:356-357)");
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_indexed: bad sizes");
-    if (!terse || !pixels_out || !status || !index || !frame_offsets)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_indexed: null pointer");
-    if ((uintptr_t)terse % 4 || (uintptr_t)index % 16 || (uintptr_t)frame_offsets % 8 ||
-        (uintptr_t)pixels_out % trpx_dtype_size(out_dtype) || (uintptr_t)status % 8)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_indexed: misaligned pointer (terse needs 4 B, index 16 B)");
-    const IdxLayout il = idx_layout(g, n_frames, trpx_dtype_size(out_dtype));
-    trpx::DecodeArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.pixels_out = pixels_out;
-    a.status = status;
-    a.tile_off = reinterpret_cast<uint64_t*>(const_cast<char*>(static_cast<const char*>(index)) + il.group_off);
-    a.widths = reinterpret_cast<uint8_t*>(const_cast<char*>(static_cast<const char*>(index)) + il.widths);
+    const size_t es = trpx_dtype_size(out_dtype);
+    if (const int rc = check_args("trpx_decode_indexed", kDtypeFirst | kIndexOnly | kSameSign | kHasStream, out_dtype, es, stream_signed, terse_bytes,
+                                  n_values, n_frames, block, {{terse, 4}, {index, 16}, {frame_offsets, 8}, {pixels_out, es}, {status, 8}}, &g))
+        return rc;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
+    point_into(a, index, idx_layout(g, n_frames, es));
     // a thousand frames and more: one workgroup per frame; fewer: the tiled kernel spreads a frame's tiles over the whole GPU
     // (512^2 u16 frames, tiled / per-frame: 128 frames 0.023 / 0.121 ms, 600 frames 0.092 / 0.137, 1000 frames 0.148 / 0.142, 2000
     // frames 0.30 / 0.21 -- both scale with the blocks per frame, so the frame count alone decides)
-    const bool frame26 = 8 * (uint64_t)trpx_worst_case_bytes(out_dtype, n_values, block) + (1u << 17) < (1ull << 26);
-    const bool per_frame = frame26 && g_decode_path != 2 && (g_decode_path == 3 || n_frames >= 1024);
+    const bool per_frame = fits_per_frame_decoder(out_dtype, n_values, block) && g_decode_path != kRouteTiled &&
+                           (g_decode_path == kRouteFrames || n_frames >= 1024);
     // Frames that start inside a cache line (513 x 511 u16: most detectors): the indexed extraction's 16-byte stores are then
     // misaligned and it LOSES to the walking decoder, whose extraction waves write line images (2000 frames: 0.33 against 0.27 ms).
     // Such stacks take the walking decoder, and the frames it hands over -- header-dense ones, where the walk is what costs --
@@ -466,38 +514,33 @@ int trpx_decode_indexed(int stream_signed, int out_dtype, const uint8_t* terse, 
     // hand-over list needs a few KB of scratch, which this entry point has no argument for: one grow-only buffer per calling
     // thread, device and stream (calls on one stream are ordered; a call that is being captured into a graph takes the plain indexed
     // route: a graph would keep the buffer's address, and a later, larger call frees it).
-    const bool misaligned = (g.n_values * trpx_dtype_size(out_dtype)) % 128u != 0u || (uintptr_t)pixels_out % 128u != 0u;
-    if (per_frame && misaligned && g_decode_path == 0 && trpx::parts_per_frame(g, n_frames) == 1u) {
-        void* scratch = indexed_scratch(trpx::defer_bytes(n_frames), static_cast<hipStream_t>(stream));
+    const bool misaligned = (g.n_values * es) % 128u != 0u || (uintptr_t)pixels_out % 128u != 0u;
+    if (per_frame && misaligned && g_decode_path == kRouteAuto && trpx::parts_per_frame(g, n_frames) == 1u) {
+        void* scratch = indexed_scratch(trpx::defer_bytes(n_frames), hs);
         if (scratch) {
             a.defer = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + trpx::kDeferFront);
             a.seg_ws = scratch;                                               // (not used: no walk of the listed frames)
             a.index_given = true;
-            HIP_TRY(trpx::launch_decode_frames(out_dtype, a, static_cast<hipStream_t>(stream)));
+            HIP_TRY(trpx::launch_decode_frames(out_dtype, a, hs));
             return TRPX_OK;
         }
     }
-    HIP_TRY(trpx::launch_decode_fast(out_dtype, a, true, static_cast<hipStream_t>(stream), per_frame));
+    HIP_TRY(trpx::launch_decode_fast(out_dtype, a, true, hs, per_frame));
     return TRPX_OK;
 }
 
 size_t trpx_group_count(size_t n_values, unsigned block) {
     trpx::FrameGeom g;
-    if (block != (unsigned)trpx::kBlock || !geom_of(n_values, block, &g)) return 0;
+    if (block != kBlock || !geom_of(n_values, block, &g)) return 0;
     return g.n_tiles;
 }
 
 int trpx_index_group_states(const void* index, size_t n_values, size_t n_frames, unsigned block, uint64_t* states, void* stream) {
     trpx::FrameGeom g;
-    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_index_group_states: the decode index needs block=12");
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_index_group_states: bad sizes");
-    if (!index || !states || (uintptr_t)index % 16 || (uintptr_t)states % 8) return fail(TRPX_ERR_INVALID_ARG, "trpx_index_group_states: null / misaligned pointer");
-    const IdxLayout il = idx_layout(g, n_frames);
-    trpx::DecodeArgs a{};
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.tile_off = reinterpret_cast<uint64_t*>(const_cast<char*>(static_cast<const char*>(index)) + il.group_off);
-    a.widths = reinterpret_cast<uint8_t*>(const_cast<char*>(static_cast<const char*>(index)) + il.widths);
+    if (const int rc = check_args("trpx_index_group_states", kIndexOnly, TRPX_U8, 1, 0, 0, n_values, n_frames, block, {{index, 16}, {states, 8}}, &g))
+        return rc;
+    trpx::DecodeArgs a = decode_args(nullptr, 0, nullptr, g, n_frames, nullptr, nullptr);
+    point_into(a, index, idx_layout(g, n_frames));
     HIP_TRY(trpx::launch_index_group_states(a, states, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
@@ -506,25 +549,13 @@ int trpx_index_from_group_states(int dtype, const uint8_t* terse, size_t terse_b
                                  const uint64_t* states, size_t n_values, size_t n_frames, unsigned block, void* index,
                                  uint32_t* status, void* stream) {
     trpx::FrameGeom g;
-    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_index_from_group_states: the decode index needs block=12");
-    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_index_from_group_states: no decode index for 64-bit containers (generic kernels)");
-    if (!trpx_dtype_size(dtype) || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || !terse_bytes)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_index_from_group_states: bad dtype/sizes");
-    if (!terse || !frame_offsets || !states || !index || !status) return fail(TRPX_ERR_INVALID_ARG, "trpx_index_from_group_states: null pointer");
-    if ((uintptr_t)terse % 4 || (uintptr_t)index % 16 || ((uintptr_t)frame_offsets | (uintptr_t)states | (uintptr_t)status) % 8)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_index_from_group_states: misaligned pointer");
-    if (8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block) >= (1ull << 40))
+    if (const int rc = check_args("trpx_index_from_group_states", kIndexOnly | kHasStream, dtype, trpx_dtype_size(dtype), 0, terse_bytes, n_values,
+                                  n_frames, block, {{terse, 4}, {frame_offsets, 8}, {states, 8}, {index, 16}, {status, 8}}, &g))
+        return rc;
+    if (worst_frame_bits(dtype, n_values, block) >= (1ull << 40))              // (a group state keeps a bit offset in 40 bits)
         return fail(TRPX_ERR_UNSUPPORTED, "trpx_index_from_group_states: frames of >= 2^40 bits");
-    const IdxLayout il = idx_layout(g, n_frames);
-    trpx::DecodeArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.status = status;
-    a.tile_off = reinterpret_cast<uint64_t*>(static_cast<char*>(index) + il.group_off);
-    a.widths = reinterpret_cast<uint8_t*>(static_cast<char*>(index) + il.widths);
+    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, nullptr, status);
+    point_into(a, index, idx_layout(g, n_frames));
     HIP_TRY(trpx::launch_walk_groups(a, (uint32_t)(8 * trpx_dtype_size(dtype)), states, true, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
@@ -533,31 +564,16 @@ int trpx_decode_convert(int stream_signed, int out_dtype, const uint8_t* terse, 
                         const uint64_t* frame_offsets, size_t n_values, size_t n_frames, unsigned block, void* pixels_out,
                         uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     trpx::FrameGeom g;
-    const size_t es = out_dtype == TRPX_F32 ? 4 : out_dtype == TRPX_F64 ? 8 : trpx_dtype_size(out_dtype);
-    if (!es) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_convert: unknown dtype %d", out_dtype);
-    if (block == 0 || block > kMaxBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_convert: block=%u", block);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_convert: bad sizes");
-    if (!terse || !pixels_out || !status || !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_convert: null pointer");
-    if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8 ||
-        (uintptr_t)pixels_out % es)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_convert: misaligned pointer");
-    const DecWs w = dec_ws(g, n_frames, es);
+    const size_t es = convert_elem_size(out_dtype);
+    if (const int rc = check_args("trpx_decode_convert", kDtypeFirst | kHasStream, out_dtype, es, stream_signed, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {pixels_out, es}, {status, 8}, {workspace, 8}, {frame_offsets, 8, false}}, &g))
+        return rc;
+    const DecLayout w = dec_ws(g, n_frames, es);
     if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_convert: workspace %zu < %zu", workspace_bytes, w.total);
     trpx::fused_ws_forget(workspace, workspace_bytes);
-    trpx::DecodeArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = (uint32_t)n_frames;
-    a.pixels_out = pixels_out;
-    a.status = status;
-    char* ws = static_cast<char*>(workspace);
-    a.walk_offsets = reinterpret_cast<uint64_t*>(ws + w.walk_offsets);
-    a.tile_off = reinterpret_cast<uint64_t*>(ws + w.tile_off);
-    a.widths = reinterpret_cast<uint8_t*>(ws + w.widths);
-    a.seg_ws = ws + w.seg;
+    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
+    a.walk_offsets = static_cast<uint64_t*>(workspace);
+    point_into(a, workspace, w, kSeg);
     HIP_TRY(trpx::launch_decode_convert(out_dtype, a, stream_signed != 0, frame_offsets != nullptr, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
@@ -574,9 +590,9 @@ int trpx_set_encode_path(int path) {
 }
 
 int trpx_set_decode_path(int path) {
-    if (path < 0 || path > 5) return fail(TRPX_ERR_INVALID_ARG, "trpx_set_decode_path: 0 = auto, 1 = basic, 2 = tiled, 3 = per-frame, 4 = parts route for large frames, 5 = auto with the dense walk for listed frames");
-    trpx::set_dense_route(path == 5);
-    g_decode_path = path == 5 ? 0 : path;
+    if (path < kRouteAuto || path > kSelectDense) return fail(TRPX_ERR_INVALID_ARG, "trpx_set_decode_path: 0 = auto, 1 = basic, 2 = tiled, 3 = per-frame, 4 = parts route for large frames, 5 = auto with the dense walk for listed frames");
+    trpx::set_dense_route(path == kSelectDense);
+    g_decode_path = path == kSelectDense ? kRouteAuto : static_cast<DecodeRoute>(path);
     return TRPX_OK;
 }
 
@@ -604,11 +620,136 @@ int trpx_synth_fill(int dtype, uint64_t seed, uint64_t frame0, size_t n_frames, 
     return TRPX_OK;
 }
 
+size_t trpx_locate_workspace_bytes(size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    if (!terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return 0;
+    return trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
+}
+
+// (its own order of checks: the pointers and max_bits first, and any block size the geometry can be had for)
+int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned max_bits,
+                       uint64_t* frame_offsets, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    if (!terse || !terse_bytes || !frame_offsets || !status || !workspace || max_bits == 0 || max_bits > 64)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad argument");
+    if (!geom_of(n_values, block, &g)) return bad_geom("trpx_locate_frames", block);
+    if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                      // every frame is at least one byte (Terse.hpp:547)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: misaligned pointer (terse needs 4 B, workspace 8 B)");
+    const size_t need = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
+    if (workspace_bytes < need) return fail(TRPX_ERR_CAPACITY, "trpx_locate_frames: workspace %zu < %zu", workspace_bytes, need);
+    trpx::fused_ws_forget(workspace, workspace_bytes);
+    HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_bits, frame_offsets, status, workspace,
+                                static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+}  // extern "C"
+// ---- summing decode (decode_sum.hip) -------------------------------------------------------------------------------------
+namespace {
+bool sum_out_ok(int out_dtype) {
+    return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_I64 || out_dtype == TRPX_U64 ||
+           out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
+}
+size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
+// workspace: [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)] [partial slab]
+struct SumWs { size_t offsets, region, partial, total; };
+SumWs sum_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, size_t group, bool have_offsets, bool have_index) {
+    SumWs w;
+    w.offsets = 0;
+    w.region = have_offsets ? 0 : trpx::align_up(8 * (n_frames + 1), 256);
+    const size_t idx = have_index ? 0 : idx_layout(g, n_frames, trpx_dtype_size(dtype)).total;
+    const size_t loc = have_offsets ? 0 : trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
+    w.partial = w.region + trpx::align_up(std::max(idx, loc), 256);
+    w.total = w.partial + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes;
+    return w;
+}
+}  // namespace
+
+extern "C" {
+
+size_t trpx_decode_sum_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                       unsigned group) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !group || !terse_bytes ||
+        !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
+        return 0;
+    return sum_ws(dtype, g, terse_bytes, n_frames, group, false, false).total;
+}
+
+// (its own order of checks: a 64-bit dtype is UNSUPPORTED before an unknown one is INVALID_ARG, tests/test_decode_sum_args.py)
+int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                    const void* index, size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out,
+                    uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: no decode index for 64-bit containers");
+    if (dtype < TRPX_U8 || dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: unknown stream dtype %d", dtype);
+    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: out_dtype %d (I32, U32, I64, U64, F32, F64)", out_dtype);
+    if (block != kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: block=%u (the decode index needs 12)", block);
+    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
+        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: signed stream into an unsigned output (Terse.hpp:356-357)");
+    if (group == 0) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: group = 0");
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0 || n_frames > terse_bytes)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (!terse || !sums_out || !status) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null pointer");
+    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: an index needs its frame offsets");
+    if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 ||
+        (uintptr_t)workspace % 8 || (uintptr_t)sums_out % sum_out_size(out_dtype))
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: misaligned pointer (terse 4 B, offsets / workspace 8 B, index 16 B, sums their type)");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: frames of >= 2^32 bits");
+    const SumWs w = sum_ws(dtype, g, terse_bytes, n_frames, group, frame_offsets != nullptr, index != nullptr);
+    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sum: workspace %zu < %zu", workspace_bytes, w.total);
+    if (w.total && !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null workspace");
+    const trpx::SumPlan p = trpx::sum_plan(dtype, g, n_frames, group);
+    if (p.n_out * p.chunks * (uint64_t)p.tpf >= (1ull << 40)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes");
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);
+    const uint32_t max_w = 8u * (uint32_t)trpx_dtype_size(dtype);
+    bool clear = true;
+    if (!frame_offsets) {                                                       // index-free: locate the frames first (its scratch: the index region)
+        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
+        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, offs, status, ws + w.region, st));
+        frame_offsets = offs;
+        clear = false;                                                          // (the locator's verdict stays)
+    }
+    if (!index) {                                                               // the walk of trpx_build_index, into the workspace
+        const int rc = build_index_impl(dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, ws + w.region, status,
+                                        clear, stream);
+        if (rc) return rc;
+        index = ws + w.region;
+        clear = false;
+    }
+    const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
+    trpx::SumArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.geom = g;
+    a.n_frames = n_frames;
+    a.group = group;
+    a.n_out = p.n_out;
+    a.tpf = p.tpf;
+    a.chunks = p.chunks;
+    a.fpc = p.fpc;
+    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
+    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    a.out = sums_out;
+    a.out_code = out_dtype;
+    a.partial = p.chunks > 1 ? ws + w.partial : nullptr;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_sum(dtype, a, clear, st));
+    return TRPX_OK;
+}
+
 // ---- host-pointer convenience wrappers ---------------------------------------------------
 // The callers of the reference's API work frame by frame from host memory (src/terse.cpp:63-69 pushes one image at a
 // time, src/prolix.cpp:69-92 expands one frame at a time): a device allocation per call would cost more than the
 // codec.  Every thread keeps ONE grow-only set of device buffers per role (freed by trpx_host_release or at exit of the
-// process); the host wrappers carve their pixels / stream / offsets / status / workspace from it.
+// process); the host wrappers carve their pixels / stream / offsets / status / workspace from it.  Each wrapper reads:
+// enter, validate, stage, call the device-pointer entry point, read the status, copy back.
 }  // extern "C"
 namespace {
 struct Arena {
@@ -662,10 +803,72 @@ Arena& arena() {
     static thread_local Arena a;
     return a;
 }
-// copy on the caller's private stream and wait for that stream (never for the device)
-hipError_t copy_sync(hipStream_t hs, void* dst, const void* src, size_t n, hipMemcpyKind kind) {
-    const hipError_t e = hipMemcpyAsync(dst, src, n, kind, hs);
-    return e != hipSuccess ? e : hipStreamSynchronize(hs);
+
+// every host wrapper starts here: a device at all, the device asked for, this thread's private stream
+int enter(const char* fn, int device, hipStream_t* hs) {
+    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "%s: no HIP device", fn);
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    HIP_TRY(arena().get_stream(hs));
+    return TRPX_OK;
+}
+// The kernels read the stream in aligned 32-bit words and a little past its end, and rely on the bytes behind it reading as zero:
+// a device copy of a stream is padded_stream_bytes() long, and this is the one place that writes its zero tail.
+size_t padded_stream_bytes(size_t terse_bytes) { return trpx::align_up(terse_bytes, 4) + 8; }
+hipError_t copy_stream_zero_tail(hipStream_t hs, void* d_terse, const uint8_t* terse, size_t terse_bytes) {
+    const size_t whole = terse_bytes & ~size_t(3);
+    const hipError_t e = hipMemsetAsync(static_cast<char*>(d_terse) + whole, 0, padded_stream_bytes(terse_bytes) - whole, hs);
+    return e != hipSuccess ? e : copy_sync(hs, d_terse, terse, terse_bytes, hipMemcpyHostToDevice);
+}
+int upload_stream(hipStream_t hs, const uint8_t* terse, size_t terse_bytes, const uint8_t** d_terse) {
+    void* p = nullptr;
+    HIP_TRY(arena().get(Arena::kStream, padded_stream_bytes(terse_bytes), &p));
+    HIP_TRY(copy_stream_zero_tail(hs, p, terse, terse_bytes));
+    *d_terse = static_cast<const uint8_t*>(p);
+    return TRPX_OK;
+}
+// the offsets slot: n_frames + 1 offsets (uploaded where the caller has them) and `extra` bytes behind them
+int upload_offsets(hipStream_t hs, const uint64_t* frame_offsets, size_t n_frames, size_t extra, uint64_t** d_offs) {
+    void* p = nullptr;
+    HIP_TRY(arena().get(Arena::kOffsets, 8 * (n_frames + 1) + extra, &p));
+    if (frame_offsets) HIP_TRY(copy_sync(hs, p, frame_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
+    *d_offs = static_cast<uint64_t*>(p);
+    return TRPX_OK;
+}
+int status_slot(uint32_t** d_st) {
+    void* p = nullptr;
+    HIP_TRY(arena().get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &p));
+    *d_st = static_cast<uint32_t*>(p);
+    return TRPX_OK;
+}
+
+// Decode into any output type, everything on the device, the last status block in st.  Same signedness into <= 32 bits: the
+// tuned decoders.  They report CORRUPT for a block wider than the output type, which is also what a legitimately wider stream
+// looks like (e.g. u16 data into a u8 container, Bit_pointer.hpp:747-763; a stream of 64-bit pixels): those -- and every
+// cross-kind / float / double / 64-bit request -- take the converting decoder, whose verdict is final.
+int decode_any(int stream_signed, int out_dtype, const uint8_t* d_terse, size_t terse_bytes, const uint64_t* d_offs, size_t n_values,
+               size_t n_frames, unsigned block, void* d_out, uint32_t* d_st, void* d_ws, size_t ws_bytes, hipStream_t hs,
+               uint32_t st[TRPX_STATUS_WORDS]) {
+    for (bool convert = !tuned_type(stream_signed, out_dtype);; convert = true) {
+        int rc = convert ? trpx_decode_convert(stream_signed, out_dtype, d_terse, terse_bytes, d_offs, n_values, n_frames, block, d_out, d_st, d_ws, ws_bytes, hs)
+                         : trpx_decode(stream_signed, out_dtype, d_terse, terse_bytes, d_offs, n_values, n_frames, block, d_out, d_st, d_ws, ws_bytes, hs);
+        if (rc || (rc = read_status(hs, d_st, st))) return rc;
+        if (st[0] != TRPX_ERR_CORRUPT || convert) return TRPX_OK;
+    }
+}
+// Walk-free decode of frames whose group states came with the file: the decode index from the states, then the indexed decode.
+// The last status block in st; *decoded: the indexed decode ran.  It does not run when the index step reports CORRUPT (the
+// states do not describe this stream, or the data are wider than the output type) or, with stop_on_any, anything at all.
+int decode_walk_free(int stream_signed, int out_dtype, const uint8_t* d_terse, size_t terse_bytes, const uint64_t* d_offs,
+                     const uint64_t* d_states, size_t n_values, size_t n_frames, unsigned block, void* d_index, void* d_out,
+                     uint32_t* d_st, hipStream_t hs, bool stop_on_any, uint32_t st[TRPX_STATUS_WORDS], bool* decoded) {
+    *decoded = false;
+    int rc = trpx_index_from_group_states(out_dtype, d_terse, terse_bytes, d_offs, d_states, n_values, n_frames, block, d_index, d_st, hs);
+    if (rc || (rc = read_status(hs, d_st, st))) return rc;
+    if (st[0] == TRPX_ERR_CORRUPT || (stop_on_any && st[0])) return TRPX_OK;
+    rc = trpx_decode_indexed(stream_signed, out_dtype, d_terse, terse_bytes, d_offs, d_index, n_values, n_frames, block, d_out, d_st, hs);
+    if (rc || (rc = read_status(hs, d_st, st))) return rc;
+    *decoded = true;
+    return TRPX_OK;
 }
 }  // namespace
 extern "C" {
@@ -675,51 +878,34 @@ void trpx_host_release(void) { arena().release(); }
 int trpx_encode_host(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out,
                      size_t out_capacity, size_t* total_bytes, uint64_t* frame_offsets, uint32_t* prolix_bits,
                      int device) {
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_encode_host: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_encode_host", device, &hs)) return rc;
     const size_t es = trpx_dtype_size(dtype);
     if (!es || !pixels || !out || !total_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_host: bad argument");
-    {
-        trpx::FrameGeom g0;
-        if (!geom_of(n_values, block, &g0)) return fail(block == 0 || block > kMaxBlock ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "trpx_encode_host: unsupported sizes/block (block=%u)", block);
-        if (!sizes_ok(g0, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    }
+    trpx::FrameGeom g;
+    if (!geom_of(n_values, block, &g)) return fail(block == 0 || block > kMaxBlock ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "trpx_encode_host: unsupported sizes/block (block=%u)", block);
+    if (!sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
     const size_t in_bytes = n_values * n_frames * es;
     const size_t cap = trpx::align_up(n_frames * trpx_worst_case_bytes(dtype, n_values, block), 16);
-    const size_t ws_bytes = trpx_encode_workspace_bytes(dtype, n_values, n_frames, block);
-    if (!ws_bytes) return fail(block != 12 ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG,
-                               "trpx_encode_host: unsupported sizes/block (block=%u)", block);
-    struct { void* p; } d_px, d_out, d_off, d_st, d_ws;
+    const size_t ws_bytes = enc_ws(g, n_frames).total;
+    void *d_px = nullptr, *d_out = nullptr, *d_ws = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
     Arena& A = arena();
-    hipStream_t hs = nullptr;
-    HIP_TRY(A.get_stream(&hs));
-    HIP_TRY(A.get(Arena::kPixels, in_bytes, &d_px.p));
-    HIP_TRY(A.get(Arena::kStream, cap, &d_out.p));
-    HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1), &d_off.p));
-    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws.p, true));
-    HIP_TRY(copy_sync(hs, d_px.p, pixels, in_bytes, hipMemcpyHostToDevice));
-    int rc = trpx_encode(dtype, d_px.p, n_values, n_frames, block, static_cast<uint8_t*>(d_out.p), cap,
-                         static_cast<uint64_t*>(d_off.p), static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(hs));
+    HIP_TRY(A.get(Arena::kPixels, in_bytes, &d_px));
+    HIP_TRY(A.get(Arena::kStream, cap, &d_out));
+    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws, true));
+    int rc = upload_offsets(hs, nullptr, n_frames, 0, &d_off);
+    if (rc || (rc = status_slot(&d_st))) return rc;
+    HIP_TRY(copy_sync(hs, d_px, pixels, in_bytes, hipMemcpyHostToDevice));
     uint32_t st[TRPX_STATUS_WORDS];
-    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st[0] == TRPX_ERR_TIMEOUT && g_encode_path == 0) {   // never seen in practice; keeps the API total
-        t_force_two_pass = true;                             // (this thread's next call only: other threads are not affected)
-        rc = trpx_encode(dtype, d_px.p, n_values, n_frames, block, static_cast<uint8_t*>(d_out.p), cap,
-                         static_cast<uint64_t*>(d_off.p), static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs);
-        t_force_two_pass = false;
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(hs));
-        HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    }
-    if (st[0]) return fail((int)st[0], "trpx_encode_host: device status %u", st[0]);
+    rc = encode_retrying(dtype, d_px, n_values, n_frames, block, static_cast<uint8_t*>(d_out), cap, d_off, d_st, nullptr, d_ws, ws_bytes, hs, st);
+    if (rc || (rc = status_result("trpx_encode_host", st))) return rc;
     std::vector<uint64_t> offs(n_frames + 1);
-    HIP_TRY(copy_sync(hs, offs.data(), d_off.p, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(hs, offs.data(), d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
     const size_t total = (size_t)offs[n_frames];
     if (total > out_capacity) return fail(TRPX_ERR_CAPACITY, "trpx_encode_host: need %zu bytes, have %zu", total, out_capacity);
-    HIP_TRY(copy_sync(hs, out, d_out.p, total, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(hs, out, d_out, total, hipMemcpyDeviceToHost));
     *total_bytes = total;
     if (frame_offsets) memcpy(frame_offsets, offs.data(), 8 * (n_frames + 1));
     if (prolix_bits) *prolix_bits = st[1];
@@ -729,285 +915,107 @@ int trpx_encode_host(int dtype, const void* pixels, size_t n_values, size_t n_fr
 int trpx_decode_host(int stream_signed, int out_dtype, const uint8_t* terse, size_t terse_bytes,
                      const uint64_t* frame_offsets, size_t n_values, size_t n_frames, unsigned block,
                      void* pixels_out, int device) {
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_decode_host: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
-    const size_t es = out_dtype == TRPX_F32 ? 4 : out_dtype == TRPX_F64 ? 8 : trpx_dtype_size(out_dtype);
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_host", device, &hs)) return rc;
+    const size_t es = convert_elem_size(out_dtype);
     if (!es || !terse || !pixels_out || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host: bad argument");
-    {
-        trpx::FrameGeom g0;
-        if (geom_of(n_values, block, &g0) && !sizes_ok(g0, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host: bad sizes");
-    }
+    trpx::FrameGeom g;
+    if (!geom_of(n_values, block, &g)) return bad_geom("trpx_decode_host", block);
+    if (!sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host: bad sizes");
     const size_t out_bytes = n_values * n_frames * es;
     const size_t ws_bytes = trpx_decode_workspace_bytes(TRPX_U8, n_values, n_frames, block);
-    if (!ws_bytes) return fail(block != 12 ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG,
-                               "trpx_decode_host: unsupported sizes/block (block=%u)", block);
-    struct { void* p = nullptr; } d_in, d_out, d_off, d_st, d_ws;
-    Arena& A = arena();
-    hipStream_t hs = nullptr;
-    HIP_TRY(A.get_stream(&hs));
-    HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
-    HIP_TRY(A.get(Arena::kPixels, out_bytes, &d_out.p));
-    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws.p));
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));   // the bytes behind the stream read as zero
-    HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
-    if (frame_offsets) {
-        HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1), &d_off.p));
-        HIP_TRY(copy_sync(hs, d_off.p, frame_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
-    }
-    // Same signedness: the tuned decoders.  They report CORRUPT for a block wider than the output type, which is also
-    // what a legitimately wider stream looks like (e.g. u16 data into a u8 container, Bit_pointer.hpp:747-763): those
-    // -- and every cross-kind / float / double request -- take the converting decoder, whose verdict is final.
-    const uint64_t* offs_dev = frame_offsets ? static_cast<const uint64_t*>(d_off.p) : nullptr;
-    bool convert = !(out_dtype <= TRPX_I32 && (stream_signed != 0) == (trpx_dtype_is_signed(out_dtype) != 0));
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
+    void *d_out = nullptr, *d_ws = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
+    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
     uint32_t st[TRPX_STATUS_WORDS];
-    for (;;) {
-        const int rc = convert ? trpx_decode_convert(stream_signed, out_dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes,
-                                                     offs_dev, n_values, n_frames, block, d_out.p,
-                                                     static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs)
-                               : trpx_decode(stream_signed, out_dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes, offs_dev,
-                                             n_values, n_frames, block, d_out.p, static_cast<uint32_t*>(d_st.p), d_ws.p,
-                                             ws_bytes, hs);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(hs));
-        HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-        if (st[0] == TRPX_ERR_CORRUPT && !convert && es <= 4) { convert = true; continue; }   // (32-bit containers: a stream of 64-bit pixels)
-        break;
-    }
-    if (st[0]) return fail((int)st[0], "trpx_decode_host: corrupt or truncated stream (device status %u)", st[0]);
-    HIP_TRY(copy_sync(hs, pixels_out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
-}
-
-size_t trpx_locate_workspace_bytes(size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
-    trpx::FrameGeom g;
-    if (!terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return 0;
-    return trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-}
-
-int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned max_bits,
-                       uint64_t* frame_offsets, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    trpx::FrameGeom g;
-    if (!terse || !terse_bytes || !frame_offsets || !status || !workspace || max_bits == 0 || max_bits > 64)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad argument");
-    if (!geom_of(n_values, block, &g))
-        return fail(block != 12 ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "trpx_locate_frames: unsupported sizes/block (block=%u)", block);
-    if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                      // every frame is at least one byte (Terse.hpp:547)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: misaligned pointer (terse needs 4 B, workspace 8 B)");
-    const size_t need = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    if (workspace_bytes < need) return fail(TRPX_ERR_CAPACITY, "trpx_locate_frames: workspace %zu < %zu", workspace_bytes, need);
-    trpx::fused_ws_forget(workspace, workspace_bytes);
-    HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_bits, frame_offsets, status, workspace,
-                                static_cast<hipStream_t>(stream)));
+    rc = decode_any(stream_signed, out_dtype, d_in, terse_bytes, d_off, n_values, n_frames, block, d_out, d_st, d_ws, ws_bytes, hs, st);
+    if (rc || (rc = status_result("trpx_decode_host", st))) return rc;
+    HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
 int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_values, size_t n_frames,
                             unsigned block, unsigned max_bits, uint64_t* frame_offsets, int device) {
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_frame_offsets_host: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_frame_offsets_host", device, &hs)) return rc;
     trpx::FrameGeom g;
     if (!terse || !terse_bytes || !frame_offsets || !n_frames || max_bits == 0 || max_bits > 64)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_frame_offsets_host: bad argument");
-    if (!geom_of(n_values, block, &g))
-        return fail(block != 12 ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG,
-                    "trpx_frame_offsets_host: unsupported sizes/block (block=%u)", block);
+    if (!geom_of(n_values, block, &g)) return bad_geom("trpx_frame_offsets_host", block);
     if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                     // every frame is at least one byte (Terse.hpp:547)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_frame_offsets_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
     const size_t ws_bytes = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    struct { void* p = nullptr; } d_in, d_off, d_st, d_ws;
-    Arena& A = arena();
-    hipStream_t hs = nullptr;
-    HIP_TRY(A.get_stream(&hs));
-    HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
-    HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1), &d_off.p));
-    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws.p));
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));
-    HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
-    const int rc = trpx_locate_frames(static_cast<const uint8_t*>(d_in.p), terse_bytes, n_values, n_frames, block, max_bits,
-                                      static_cast<uint64_t*>(d_off.p), static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(hs));
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
+    void* d_ws = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = upload_offsets(hs, nullptr, n_frames, 0, &d_off)) || (rc = status_slot(&d_st))) return rc;
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
     uint32_t st[TRPX_STATUS_WORDS];
-    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st[0]) return fail((int)st[0], "trpx_frame_offsets_host: corrupt or truncated stack");
-    HIP_TRY(copy_sync(hs, frame_offsets, d_off.p, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
-    return TRPX_OK;
-}
-
-}  // extern "C"
-// ---- summing decode (decode_sum.hip) -------------------------------------------------------------------------------------
-namespace {
-bool sum_out_ok(int out_dtype) {
-    return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_I64 || out_dtype == TRPX_U64 ||
-           out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
-}
-size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
-// workspace: [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)] [partial slab]
-struct SumWs { size_t offsets, region, partial, total; };
-SumWs sum_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, size_t group, bool have_offsets, bool have_index) {
-    SumWs w;
-    w.offsets = 0;
-    w.region = have_offsets ? 0 : trpx::align_up(8 * (n_frames + 1), 256);
-    const size_t idx = have_index ? 0 : idx_layout(g, n_frames, trpx_dtype_size(dtype)).total;
-    const size_t loc = have_offsets ? 0 : trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    w.partial = w.region + trpx::align_up(std::max(idx, loc), 256);
-    w.total = w.partial + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes;
-    return w;
-}
-}  // namespace
-
-extern "C" {
-
-size_t trpx_decode_sum_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
-                                       unsigned group) {
-    trpx::FrameGeom g;
-    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != (unsigned)trpx::kBlock || !group || !terse_bytes ||
-        !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
-        return 0;
-    return sum_ws(dtype, g, terse_bytes, n_frames, group, false, false).total;
-}
-
-int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
-                    const void* index, size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out,
-                    uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    trpx::FrameGeom g;
-    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: no decode index for 64-bit containers");
-    if (dtype < TRPX_U8 || dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: unknown stream dtype %d", dtype);
-    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: out_dtype %d (I32, U32, I64, U64, F32, F64)", out_dtype);
-    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: block=%u (the decode index needs 12)", block);
-    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: signed stream into an unsigned output (Terse.hpp:356-357)");
-    if (group == 0) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: group = 0");
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0 || n_frames > terse_bytes)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    if (!terse || !sums_out || !status) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null pointer");
-    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: an index needs its frame offsets");
-    if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 ||
-        (uintptr_t)workspace % 8 || (uintptr_t)sums_out % sum_out_size(out_dtype))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: misaligned pointer (terse 4 B, offsets / workspace 8 B, index 16 B, sums their type)");
-    if (8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block) >= 0xF0000000ull)
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: frames of >= 2^32 bits");
-    const SumWs w = sum_ws(dtype, g, terse_bytes, n_frames, group, frame_offsets != nullptr, index != nullptr);
-    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sum: workspace %zu < %zu", workspace_bytes, w.total);
-    if (w.total && !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null workspace");
-    const trpx::SumPlan p = trpx::sum_plan(dtype, g, n_frames, group);
-    if (p.n_out * p.chunks * (uint64_t)p.tpf >= (1ull << 40)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes");
-
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);
-    const uint32_t max_w = 8u * (uint32_t)trpx_dtype_size(dtype);
-    bool clear = true;
-    if (!frame_offsets) {                                                       // index-free: locate the frames first (its scratch: the index region)
-        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
-        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, offs, status, ws + w.region, st));
-        frame_offsets = offs;
-        clear = false;                                                          // (the locator's verdict stays)
-    }
-    if (!index) {                                                               // the walk of trpx_build_index, into the workspace
-        const int rc = build_index_impl(dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, ws + w.region, status,
-                                        clear, stream);
-        if (rc) return rc;
-        index = ws + w.region;
-        clear = false;
-    }
-    const IdxLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
-    trpx::SumArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = n_frames;
-    a.group = group;
-    a.n_out = p.n_out;
-    a.tpf = p.tpf;
-    a.chunks = p.chunks;
-    a.fpc = p.fpc;
-    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.group_off);
-    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
-    a.out = sums_out;
-    a.out_code = out_dtype;
-    a.partial = p.chunks > 1 ? ws + w.partial : nullptr;
-    a.status = status;
-    HIP_TRY(trpx::launch_decode_sum(dtype, a, clear, st));
+    rc = trpx_locate_frames(d_in, terse_bytes, n_values, n_frames, block, max_bits, d_off, d_st, d_ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_frame_offsets_host", st))) return rc;
+    HIP_TRY(copy_sync(hs, frame_offsets, d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
 int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                          size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out, int device) {
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_decode_sum_host: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_sum_host", device, &hs)) return rc;
     trpx::FrameGeom g;
     if (!terse || !sums_out || !terse_bytes || !sum_out_ok(out_dtype) || !group)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad argument");
-    if (block != (unsigned)trpx::kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum_host: block=%u dtype=%d", block, dtype);
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum_host: block=%u dtype=%d", block, dtype);
     if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad sizes");
     const size_t ws_bytes = trpx_decode_sum_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group);
     if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad dtype/sizes");
     const size_t out_bytes = (n_frames + group - 1) / group * n_values * sum_out_size(out_dtype);
-    struct { void* p = nullptr; } d_in, d_out, d_off, d_st, d_ws;
-    Arena& A = arena();
-    hipStream_t hs = nullptr;
-    HIP_TRY(A.get_stream(&hs));
-    HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
-    HIP_TRY(A.get(Arena::kPixels, out_bytes, &d_out.p));
-    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws.p));
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));
-    HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
-    if (frame_offsets) {
-        HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1), &d_off.p));
-        HIP_TRY(copy_sync(hs, d_off.p, frame_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
-    }
-    const int rc = trpx_decode_sum(dtype, out_dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes,
-                                   frame_offsets ? static_cast<const uint64_t*>(d_off.p) : nullptr, nullptr, n_values, n_frames,
-                                   block, group, d_out.p, static_cast<uint32_t*>(d_st.p), d_ws.p, ws_bytes, hs);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(hs));
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
+    void *d_out = nullptr, *d_ws = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
+    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
     uint32_t st[TRPX_STATUS_WORDS];
-    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st[0]) return fail((int)st[0], "trpx_decode_sum_host: corrupt or truncated stream (device status %u)", st[0]);
-    HIP_TRY(copy_sync(hs, sums_out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    rc = trpx_decode_sum(dtype, out_dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, group, d_out, d_st, d_ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_sum_host", st))) return rc;
+    HIP_TRY(copy_sync(hs, sums_out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
-
 int trpx_group_states_host(const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                            size_t n_frames, unsigned block, unsigned max_bits, uint64_t* group_states, int device) {
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_group_states_host: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_group_states_host", device, &hs)) return rc;
     trpx::FrameGeom g;
     if (!terse || !terse_bytes || !frame_offsets || !group_states || max_bits == 0 || max_bits > 32)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_group_states_host: bad argument");
-    if (block != (unsigned)trpx::kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_group_states_host: block=%u", block);
+    if (block != kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_group_states_host: block=%u", block);
     if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || n_frames > terse_bytes)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_group_states_host: bad sizes");
     const int dtype = max_bits <= 8 ? TRPX_U8 : max_bits <= 16 ? TRPX_U16 : TRPX_U32;
     const size_t ib = trpx_index_bytes(dtype, n_values, n_frames, block), ng = n_frames * (size_t)g.n_tiles;
-    struct { void* p = nullptr; } d_in, d_off, d_st, d_idx;
-    Arena& A = arena();
-    hipStream_t hs = nullptr;
-    HIP_TRY(A.get_stream(&hs));
-    HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
-    HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1) + 8 * ng, &d_off.p));
-    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, ib, &d_idx.p));
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));
-    HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(copy_sync(hs, d_off.p, frame_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
-    uint64_t* d_states = static_cast<uint64_t*>(d_off.p) + (n_frames + 1);
-    int rc = trpx_build_index(dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes, static_cast<const uint64_t*>(d_off.p), n_values,
-                              n_frames, block, d_idx.p, static_cast<uint32_t*>(d_st.p), hs);
-    if (rc) return rc;
-    rc = trpx_index_group_states(d_idx.p, n_values, n_frames, block, d_states, hs);
-    if (rc) return rc;
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;                                                 // the offsets, then the states
+    uint32_t* d_st = nullptr;
+    void* d_idx = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = upload_offsets(hs, frame_offsets, n_frames, 8 * ng, &d_off)) || (rc = status_slot(&d_st))) return rc;
+    HIP_TRY(arena().get(Arena::kWorkspace, ib, &d_idx));
+    uint64_t* d_states = d_off + (n_frames + 1);
     uint32_t st[TRPX_STATUS_WORDS];
-    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st[0]) return fail((int)st[0], "trpx_group_states_host: corrupt or truncated stack (device status %u)", st[0]);
+    rc = trpx_build_index(dtype, d_in, terse_bytes, d_off, n_values, n_frames, block, d_idx, d_st, hs);
+    if (rc || (rc = trpx_index_group_states(d_idx, n_values, n_frames, block, d_states, hs)) || (rc = read_status(hs, d_st, st)) ||
+        (rc = status_result("trpx_group_states_host", st)))
+        return rc;
     HIP_TRY(copy_sync(hs, group_states, d_states, 8 * ng, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
@@ -1018,42 +1026,33 @@ int trpx_decode_host_grouped(int stream_signed, int out_dtype, const uint8_t* te
     // the tuned, walk-free route needs a same-signedness integer type; everything else (and a
     // state table that does not fit the stream) goes the general way
     trpx::FrameGeom g;
-    const bool tuned = group_states && frame_offsets && out_dtype <= TRPX_I32 && trpx_dtype_size(out_dtype) &&
-                       (stream_signed != 0) == (trpx_dtype_is_signed(out_dtype) != 0) && block == (unsigned)trpx::kBlock &&
+    const bool tuned = group_states && frame_offsets && tuned_type(stream_signed, out_dtype) && block == kBlock &&
                        geom_of(n_values, block, &g) && sizes_ok(g, n_frames);
     if (!tuned) return trpx_decode_host(stream_signed, out_dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, pixels_out, device);
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_decode_host_grouped: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
-    if (!terse || !terse_bytes || !pixels_out) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host_grouped: bad argument");
-    const size_t es = trpx_dtype_size(out_dtype), out_bytes = n_values * n_frames * es, ng = n_frames * (size_t)g.n_tiles;
-    const size_t ib = trpx_index_bytes(out_dtype, n_values, n_frames, block);
-    struct { void* p = nullptr; } d_in, d_out, d_off, d_st, d_idx;
-    Arena& A = arena();
     hipStream_t hs = nullptr;
-    HIP_TRY(A.get_stream(&hs));
-    HIP_TRY(A.get(Arena::kStream, trpx::align_up(terse_bytes, 4) + 8, &d_in.p));
-    HIP_TRY(A.get(Arena::kPixels, out_bytes, &d_out.p));
-    HIP_TRY(A.get(Arena::kOffsets, 8 * (n_frames + 1) + 8 * ng, &d_off.p));
-    HIP_TRY(A.get(Arena::kStatus, 4 * TRPX_STATUS_WORDS, &d_st.p));
-    HIP_TRY(A.get(Arena::kWorkspace, ib, &d_idx.p));
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(d_in.p) + (terse_bytes & ~size_t(3)), 0, trpx::align_up(terse_bytes, 4) + 8 - (terse_bytes & ~size_t(3)), hs));
-    HIP_TRY(copy_sync(hs, d_in.p, terse, terse_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(copy_sync(hs, d_off.p, frame_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
-    uint64_t* d_states = static_cast<uint64_t*>(d_off.p) + (n_frames + 1);
+    if (const int rc = enter("trpx_decode_host_grouped", device, &hs)) return rc;
+    if (!terse || !terse_bytes || !pixels_out) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host_grouped: bad argument");
+    const size_t out_bytes = n_values * n_frames * trpx_dtype_size(out_dtype), ng = n_frames * (size_t)g.n_tiles;
+    const size_t ib = trpx_index_bytes(out_dtype, n_values, n_frames, block);
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;                                                 // the offsets, then the states
+    uint32_t* d_st = nullptr;
+    void *d_out = nullptr, *d_idx = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = upload_offsets(hs, frame_offsets, n_frames, 8 * ng, &d_off)) || (rc = status_slot(&d_st))) return rc;
+    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ib, &d_idx));
+    uint64_t* d_states = d_off + (n_frames + 1);
     HIP_TRY(copy_sync(hs, d_states, group_states, 8 * ng, hipMemcpyHostToDevice));
-    int rc = trpx_index_from_group_states(out_dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes, static_cast<const uint64_t*>(d_off.p),
-                                          d_states, n_values, n_frames, block, d_idx.p, static_cast<uint32_t*>(d_st.p), hs);
-    if (rc) return rc;
     uint32_t st[TRPX_STATUS_WORDS];
-    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st[0] == TRPX_ERR_CORRUPT)     // the states do not describe this stream (or the data are wider than the output type): general route
-        return trpx_decode_host(stream_signed, out_dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, pixels_out, device);
-    rc = trpx_decode_indexed(stream_signed, out_dtype, static_cast<const uint8_t*>(d_in.p), terse_bytes, static_cast<const uint64_t*>(d_off.p),
-                             d_idx.p, n_values, n_frames, block, d_out.p, static_cast<uint32_t*>(d_st.p), hs);
+    bool decoded = false;
+    rc = decode_walk_free(stream_signed, out_dtype, d_in, terse_bytes, d_off, d_states, n_values, n_frames, block, d_idx, d_out, d_st, hs,
+                          false, st, &decoded);
     if (rc) return rc;
-    HIP_TRY(copy_sync(hs, st, d_st.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st[0]) return fail((int)st[0], "trpx_decode_host_grouped: corrupt or truncated stream (device status %u)", st[0]);
-    HIP_TRY(copy_sync(hs, pixels_out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    if (!decoded)                      // the states do not describe this stream (or the data are wider than the output type): general route
+        return trpx_decode_host(stream_signed, out_dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, pixels_out, device);
+    if ((rc = status_result("trpx_decode_host_grouped", st))) return rc;
+    HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -1062,7 +1061,7 @@ struct trpx_stack {
     int device = 0;
     int stream_signed = 0;
     size_t n_values = 0, n_frames = 0, terse_bytes = 0;
-    unsigned block = 12;
+    unsigned block = kBlock;
     void* d_terse = nullptr;       // the stack (+ zero tail)
     void* d_offs = nullptr;        // u64[n_frames + 1]
     void* d_status = nullptr;
@@ -1087,8 +1086,8 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
                     const uint64_t* group_states, size_t n_values, size_t n_frames, unsigned block, unsigned max_bits, int device) {
     if (!handle) return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_open: null handle");
     *handle = nullptr;
-    if (trpx_device_count() == 0) return fail(TRPX_ERR_NO_DEVICE, "trpx_stack_open: no HIP device");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    hipStream_t hs = nullptr;                                                  // the calling thread's private stream (see Arena)
+    if (const int rc = enter("trpx_stack_open", device, &hs)) return rc;
     trpx::FrameGeom g;
     if (!terse || !terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || n_frames > terse_bytes)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_open: bad argument / sizes");
@@ -1101,8 +1100,6 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
     } else if (max_bits > 64) {
         return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_open: max_bits=%u", max_bits);
     }
-    hipStream_t hs = nullptr;                                                  // the calling thread's private stream (see Arena)
-    HIP_TRY(arena().get_stream(&hs));
     trpx_stack* s = new trpx_stack;
     auto bail = [&](hipError_t e, const char* what) { stack_free(s); return fail(TRPX_ERR_HIP, "trpx_stack_open: %s: %s", what, hipGetErrorString(e)); };
     hipError_t e;
@@ -1113,28 +1110,25 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
     const size_t frame_bytes = n_values * 8;                                   // widest output (double)
     s->window_frames = std::max<size_t>(1, std::min<size_t>(n_frames, (size_t(64) << 20) / frame_bytes));   // <= 64 MB of decoded frames
     s->ws_bytes = trpx_decode_workspace_bytes(TRPX_U8, n_values, s->window_frames, block);
-    if ((e = hipMalloc(&s->d_terse, trpx::align_up(terse_bytes, 4) + 8)) != hipSuccess) return bail(e, "hipMalloc(stack)");
+    if ((e = hipMalloc(&s->d_terse, padded_stream_bytes(terse_bytes))) != hipSuccess) return bail(e, "hipMalloc(stack)");
     if ((e = hipMalloc(&s->d_offs, 8 * (n_frames + 1))) != hipSuccess) return bail(e, "hipMalloc(offsets)");
     if ((e = hipMalloc(&s->d_status, 4 * TRPX_STATUS_WORDS)) != hipSuccess) return bail(e, "hipMalloc(status)");
     if ((e = hipMalloc(&s->d_ws, s->ws_bytes ? s->ws_bytes : 256)) != hipSuccess) return bail(e, "hipMalloc(workspace)");
-    if ((e = hipMemsetAsync(s->d_terse, 0, trpx::align_up(terse_bytes, 4) + 8, hs)) != hipSuccess) return bail(e, "hipMemset");
-    if ((e = copy_sync(hs, s->d_terse, terse, terse_bytes, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(stack)");
+    if ((e = copy_stream_zero_tail(hs, s->d_terse, terse, terse_bytes)) != hipSuccess) return bail(e, "upload of the stack");
     if (frame_offsets) {
         if ((e = copy_sync(hs, s->d_offs, s->offs.data(), 8 * (n_frames + 1), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
     } else {                                                                   // no index: the frames are located on the stack just uploaded
         const size_t lb = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
         void* d_lws = nullptr;
         if ((e = arena().get(Arena::kWorkspace, lb, &d_lws)) != hipSuccess) return bail(e, "locate workspace");
-        const int rc = trpx_locate_frames(static_cast<const uint8_t*>(s->d_terse), terse_bytes, n_values, n_frames, block,
-                                          max_bits ? max_bits : 32, static_cast<uint64_t*>(s->d_offs),
-                                          static_cast<uint32_t*>(s->d_status), d_lws, lb, hs);
-        if (rc) { stack_free(s); return rc; }
         uint32_t st[TRPX_STATUS_WORDS];
-        if ((e = copy_sync(hs, st, s->d_status, sizeof st, hipMemcpyDeviceToHost)) != hipSuccess) return bail(e, "hipMemcpy(status)");
-        if (st[0]) { stack_free(s); return fail((int)st[0], "trpx_stack_open: corrupt or truncated stack"); }
+        int rc = trpx_locate_frames(static_cast<const uint8_t*>(s->d_terse), terse_bytes, n_values, n_frames, block,
+                                    max_bits ? max_bits : 32, static_cast<uint64_t*>(s->d_offs),
+                                    static_cast<uint32_t*>(s->d_status), d_lws, lb, hs);
+        if (rc || (rc = read_status(hs, static_cast<uint32_t*>(s->d_status), st)) || (rc = status_result("trpx_stack_open", st))) { stack_free(s); return rc; }
         if ((e = copy_sync(hs, s->offs.data(), s->d_offs, 8 * (n_frames + 1), hipMemcpyDeviceToHost)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
     }
-    if (group_states && block == (unsigned)trpx::kBlock) {   // row f1: the file carried its group states
+    if (group_states && block == kBlock) {   // row f1: the file carried its group states
         s->groups = g.n_tiles;
         if ((e = hipMalloc(&s->d_states, 8 * n_frames * s->groups)) != hipSuccess) return bail(e, "hipMalloc(states)");
         if ((e = copy_sync(hs, s->d_states, group_states, 8 * n_frames * s->groups, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(states)");
@@ -1146,7 +1140,7 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
 
 int trpx_stack_read(trpx_stack* s, size_t frame, int out_dtype, void* pixels_out) {
     if (!s || !pixels_out || frame >= s->n_frames) return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_read: bad argument");
-    const size_t es = out_dtype == TRPX_F32 ? 4 : out_dtype == TRPX_F64 ? 8 : trpx_dtype_size(out_dtype);
+    const size_t es = convert_elem_size(out_dtype);
     if (!es) return fail(TRPX_ERR_INVALID_ARG, "trpx_stack_read: unknown dtype %d", out_dtype);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t hs = nullptr;                                                  // the calling thread's private stream
@@ -1164,39 +1158,25 @@ int trpx_stack_read(trpx_stack* s, size_t frame, int out_dtype, void* pixels_out
         s->win_count = 0;
         const uint64_t first_byte = s->offs[frame] & ~uint64_t(3);            // trpx_decode wants a 4-byte aligned stream
         const uint8_t* base = static_cast<const uint8_t*>(s->d_terse) + first_byte;
+        uint64_t* d_offs = static_cast<uint64_t*>(s->d_offs);
+        uint32_t* d_st = static_cast<uint32_t*>(s->d_status);
         std::vector<uint64_t> rel(count + 1);
         for (size_t i = 0; i <= count; ++i) rel[i] = s->offs[frame + i] - first_byte;
-        HIP_TRY(copy_sync(hs, static_cast<uint64_t*>(s->d_offs), rel.data(), 8 * (count + 1), hipMemcpyHostToDevice));
+        HIP_TRY(copy_sync(hs, d_offs, rel.data(), 8 * (count + 1), hipMemcpyHostToDevice));
         const size_t bytes = (size_t)rel[count];
-        bool convert = !(out_dtype <= TRPX_I32 && (s->stream_signed != 0) == (trpx_dtype_is_signed(out_dtype) != 0));
         uint32_t st[TRPX_STATUS_WORDS];
         bool done = false;
-        if (s->d_states && !convert) {                                         // walk-free: index from the file's group states
-            int rc = trpx_index_from_group_states(out_dtype, base, bytes, static_cast<const uint64_t*>(s->d_offs),
-                                                  static_cast<const uint64_t*>(s->d_states) + frame * s->groups, s->n_values, count,
-                                                  s->block, s->d_index, static_cast<uint32_t*>(s->d_status), hs);
-            if (rc) return rc;
-            HIP_TRY(copy_sync(hs, st, s->d_status, sizeof st, hipMemcpyDeviceToHost));
-            if (st[0] == 0) {
-                rc = trpx_decode_indexed(s->stream_signed, out_dtype, base, bytes, static_cast<const uint64_t*>(s->d_offs), s->d_index,
-                                         s->n_values, count, s->block, s->d_window, static_cast<uint32_t*>(s->d_status), hs);
-                if (rc) return rc;
-                HIP_TRY(copy_sync(hs, st, s->d_status, sizeof st, hipMemcpyDeviceToHost));
-                done = st[0] == 0;
-            }                                                                  // (states that do not fit the stream: the general route decides)
+        if (s->d_states && tuned_type(s->stream_signed, out_dtype)) {          // walk-free: index from the file's group states
+            if (const int rc = decode_walk_free(s->stream_signed, out_dtype, base, bytes, d_offs, static_cast<const uint64_t*>(s->d_states) + frame * s->groups,
+                                                s->n_values, count, s->block, s->d_index, s->d_window, d_st, hs, true, st, &done))
+                return rc;
+            done = done && st[0] == 0;                                         // (states that do not fit the stream: the general route decides)
         }
-        for (; !done;) {                                                       // (same routing as trpx_decode_host)
-            const int rc = convert ? trpx_decode_convert(s->stream_signed, out_dtype, base, bytes, static_cast<const uint64_t*>(s->d_offs),
-                                                         s->n_values, count, s->block, s->d_window, static_cast<uint32_t*>(s->d_status),
-                                                         s->d_ws, s->ws_bytes, hs)
-                                   : trpx_decode(s->stream_signed, out_dtype, base, bytes, static_cast<const uint64_t*>(s->d_offs), s->n_values,
-                                                 count, s->block, s->d_window, static_cast<uint32_t*>(s->d_status), s->d_ws, s->ws_bytes, hs);
-            if (rc) return rc;
-            HIP_TRY(copy_sync(hs, st, s->d_status, sizeof st, hipMemcpyDeviceToHost));
-            if (st[0] == TRPX_ERR_CORRUPT && !convert && es <= 4) { convert = true; continue; }   // (32-bit containers: a stream of 64-bit pixels)
-            break;
-        }
-        if (st[0]) return fail((int)st[0], "trpx_stack_read: corrupt or truncated stream (device status %u)", st[0]);
+        if (!done)
+            if (const int rc = decode_any(s->stream_signed, out_dtype, base, bytes, d_offs, s->n_values, count, s->block, s->d_window, d_st,
+                                          s->d_ws, s->ws_bytes, hs, st))
+                return rc;
+        if (const int rc = status_result("trpx_stack_read", st)) return rc;
         s->win_first = frame; s->win_count = count; s->win_dtype = out_dtype;
     }
     const size_t fb = s->n_values * es;
