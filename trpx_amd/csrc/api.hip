@@ -14,7 +14,7 @@
 
 #include "../../include/trpx_hip.h"
 #include "decode_sum.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 
 namespace trpx {
@@ -207,7 +207,7 @@ DecodeRoute g_decode_path = [] {
 // alike for the same stack: both ask here.
 bool large_frames_by_index() { return g_decode_path != kRouteTiled && g_decode_path != kRouteParts; }
 // $TRPX_SINGLE_PART = "frames,blocks": stacks of that many frames and more keep frames of up to that many blocks on the per-frame
-// route (encode_kernels.hpp: single_part_blocks; tuning runs -- the built-in rule otherwise)
+// route (launchers.hpp: single_part_blocks; tuning runs -- the built-in rule otherwise)
 [[maybe_unused]] const int g_single_part_env = [] {
     const char* e = getenv("TRPX_SINGLE_PART");
     unsigned f = 0, b = 0;

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "trpx_hip.h"
 
 namespace trpx {
 
@@ -24,15 +25,30 @@ struct FrameGeom {
 };
 
 template <typename T> struct PixelTraits;
-template <> struct PixelTraits<uint8_t>  { using U = uint8_t;  static constexpr int bits = 8;  static constexpr bool is_signed = false; };
-template <> struct PixelTraits<int8_t>   { using U = uint8_t;  static constexpr int bits = 8;  static constexpr bool is_signed = true;  };
-template <> struct PixelTraits<uint16_t> { using U = uint16_t; static constexpr int bits = 16; static constexpr bool is_signed = false; };
-template <> struct PixelTraits<int16_t>  { using U = uint16_t; static constexpr int bits = 16; static constexpr bool is_signed = true;  };
-template <> struct PixelTraits<uint32_t> { using U = uint32_t; static constexpr int bits = 32; static constexpr bool is_signed = false; };
-template <> struct PixelTraits<int32_t>  { using U = uint32_t; static constexpr int bits = 32; static constexpr bool is_signed = true;  };
+template <> struct PixelTraits<uint8_t>  { using U = uint8_t;  static constexpr int bits = 8;  static constexpr bool is_signed = false; static constexpr int dtype = TRPX_U8; };
+template <> struct PixelTraits<int8_t>   { using U = uint8_t;  static constexpr int bits = 8;  static constexpr bool is_signed = true;  static constexpr int dtype = TRPX_I8; };
+template <> struct PixelTraits<uint16_t> { using U = uint16_t; static constexpr int bits = 16; static constexpr bool is_signed = false; static constexpr int dtype = TRPX_U16; };
+template <> struct PixelTraits<int16_t>  { using U = uint16_t; static constexpr int bits = 16; static constexpr bool is_signed = true;  static constexpr int dtype = TRPX_I16; };
+template <> struct PixelTraits<uint32_t> { using U = uint32_t; static constexpr int bits = 32; static constexpr bool is_signed = false; static constexpr int dtype = TRPX_U32; };
+template <> struct PixelTraits<int32_t>  { using U = uint32_t; static constexpr int bits = 32; static constexpr bool is_signed = true;  static constexpr int dtype = TRPX_I32; };
 // 64-bit containers (what src/terse.cpp:120-123 makes of float / double images): generic correct-first kernels only
-template <> struct PixelTraits<uint64_t> { using U = uint64_t; static constexpr int bits = 64; static constexpr bool is_signed = false; };
-template <> struct PixelTraits<int64_t>  { using U = uint64_t; static constexpr int bits = 64; static constexpr bool is_signed = true;  };
+template <> struct PixelTraits<uint64_t> { using U = uint64_t; static constexpr int bits = 64; static constexpr bool is_signed = false; static constexpr int dtype = TRPX_U64; };
+template <> struct PixelTraits<int64_t>  { using U = uint64_t; static constexpr int bits = 64; static constexpr bool is_signed = true;  static constexpr int dtype = TRPX_I64; };
+
+// Host side: calls f.template operator()<T>() with the pixel type `dtype` (include/trpx_hip.h) names -- the six 8/16/32-bit types
+// every tuned kernel is instantiated for; anything else is hipErrorInvalidValue.  (Launchers that also take the 64-bit containers
+// or the converting decode's output types handle those by name and leave the six to this.)
+template <class F> inline hipError_t for_pixel_type(int dtype, F&& f) {
+    switch (dtype) {
+    case TRPX_U8:  return f.template operator()<uint8_t>();
+    case TRPX_I8:  return f.template operator()<int8_t>();
+    case TRPX_U16: return f.template operator()<uint16_t>();
+    case TRPX_I16: return f.template operator()<int16_t>();
+    case TRPX_U32: return f.template operator()<uint32_t>();
+    case TRPX_I32: return f.template operator()<int32_t>();
+    }
+    return hipErrorInvalidValue;
+}
 
 // Worst-case bits of one block: 12-bit header + 12 full-width values.
 template <typename T> constexpr int max_block_bits() { return 12 + kBlock * PixelTraits<T>::bits; }
@@ -48,6 +64,24 @@ __device__ __forceinline__ uint32_t header_val(uint32_t w, uint32_t w_prev) {
     if (w < 7u) return w << 1;                               // 0, then 3 bits     (:523)
     if (w < 10u) return (7u + ((w - 7u) << 3)) << 1;         // 0, 111, 2 bits     (:527)
     return (31u + ((w - 10u) << 5)) << 1;                    // 0, 111, 11, 6 bits (:531)
+}
+// The decoders' side of it: an explicit header (Terse.hpp:362-370) from the stream bits that start at it, bit 0 = the "same
+// width" flag (:361, clear here).  Every walker parses with one of these two; what follows the parse (w against max_w, the
+// last block's value count, bad) is the walker's own.
+struct ExplicitHeader { uint32_t w, len; };                  // width, header length in bits (flag included)
+__device__ __forceinline__ ExplicitHeader parse_explicit_header(uint32_t bits) {
+    uint32_t w = (bits >> 1) & 7u, len = 4;                  // 3 bits                       (:362)
+    if (w == 7u) {
+        w += (bits >> 4) & 3u; len = 6;                      // they read 7: 2 more          (:365)
+        if (w == 10u) { w += (bits >> 6) & 63u; len = 12; }  // the sum reads 10: 6 more     (:368)
+    }
+    return {w, len};
+}
+// The same as selects, for steps in which every lane parses the header at its own candidate and nothing may branch (walk_lds.hpp,
+// seg_common.hpp).  ext_mask < 63 drops high bits of the 6-bit extension (seg_common.hpp's counting passes).
+__device__ __forceinline__ ExplicitHeader parse_explicit_header_select(uint32_t bits, uint32_t ext_mask = 63u) {
+    const uint32_t w3 = (bits >> 1) & 7u, wa = 7u + ((bits >> 4) & 3u), wb = 10u + ((bits >> 6) & ext_mask);
+    return {w3 != 7u ? w3 : (wa != 10u ? wa : wb), w3 != 7u ? 4u : (wa != 10u ? 6u : 12u)};
 }
 
 // Significant-bit width from the OR-reduction of a block (Terse.hpp:508-515, :551-560).

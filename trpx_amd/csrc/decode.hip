@@ -12,7 +12,7 @@
 //   k_unpack                 fully parallel: widths -> header/payload lengths -> workgroup scan
 //                            -> every lane extracts its 12 fields and sign/zero-extends them.
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 #include "walk_serial.hpp"
 #include <type_traits>
@@ -235,15 +235,7 @@ hipError_t launch_walk_serial(const DecodeArgs& a, uint32_t max_w, hipStream_t s
 }
 
 hipError_t launch_decode(int dtype, const DecodeArgs& a, bool have_offsets, hipStream_t st) {
-    switch (dtype) {
-    case 0: return launch_decode_t<uint8_t>(a, have_offsets, st);
-    case 1: return launch_decode_t<int8_t>(a, have_offsets, st);
-    case 2: return launch_decode_t<uint16_t>(a, have_offsets, st);
-    case 3: return launch_decode_t<int16_t>(a, have_offsets, st);
-    case 4: return launch_decode_t<uint32_t>(a, have_offsets, st);
-    case 5: return launch_decode_t<int32_t>(a, have_offsets, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_t<T>(a, have_offsets, st); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -335,21 +327,15 @@ static hipError_t launch_decode_convert_t(const DecodeArgs& a, int stream_signed
     return hipGetLastError();
 }
 
-// dtype: 0..5 = the 8/16/32-bit integral pixel types, 6 = float, 7 = double, 8 / 9 = uint64 / int64
+// dtype: the OUTPUT type -- the six 8/16/32-bit integral pixel types, float, double, uint64 / int64
 hipError_t launch_decode_convert(int dtype, const DecodeArgs& a, int stream_signed, bool have_offsets, hipStream_t st) {
     switch (dtype) {
-    case 0: return launch_decode_convert_t<uint8_t>(a, stream_signed, have_offsets, st);
-    case 1: return launch_decode_convert_t<int8_t>(a, stream_signed, have_offsets, st);
-    case 2: return launch_decode_convert_t<uint16_t>(a, stream_signed, have_offsets, st);
-    case 3: return launch_decode_convert_t<int16_t>(a, stream_signed, have_offsets, st);
-    case 4: return launch_decode_convert_t<uint32_t>(a, stream_signed, have_offsets, st);
-    case 5: return launch_decode_convert_t<int32_t>(a, stream_signed, have_offsets, st);
-    case 6: return launch_decode_convert_t<float>(a, stream_signed, have_offsets, st);
-    case 7: return launch_decode_convert_t<double>(a, stream_signed, have_offsets, st);
-    case 8: return launch_decode_convert_t<uint64_t>(a, stream_signed, have_offsets, st);
-    case 9: return launch_decode_convert_t<int64_t>(a, stream_signed, have_offsets, st);
+    default: return for_pixel_type(dtype, [&]<class T>() { return launch_decode_convert_t<T>(a, stream_signed, have_offsets, st); });
+    case TRPX_F32: return launch_decode_convert_t<float>(a, stream_signed, have_offsets, st);
+    case TRPX_F64: return launch_decode_convert_t<double>(a, stream_signed, have_offsets, st);
+    case TRPX_U64: return launch_decode_convert_t<uint64_t>(a, stream_signed, have_offsets, st);
+    case TRPX_I64: return launch_decode_convert_t<int64_t>(a, stream_signed, have_offsets, st);
     }
-    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -379,9 +365,9 @@ hipError_t launch_synth(int dtype, uint64_t seed, uint64_t frame0, size_t n_fram
     const uint64_t total = (uint64_t)n_frames * n_values;
     const uint32_t grid = (uint32_t)((total + kThreads - 1) / kThreads < 65536 ? (total + kThreads - 1) / kThreads : 65536);
     if (total == 0) return hipSuccess;
-    if (dtype == 2) hipLaunchKernelGGL(k_synth<uint16_t>, dim3(grid), dim3(kThreads), 0, st, seed, frame0,
+    if (dtype == TRPX_U16) hipLaunchKernelGGL(k_synth<uint16_t>, dim3(grid), dim3(kThreads), 0, st, seed, frame0,
                                        (uint64_t)n_values, total, static_cast<uint16_t*>(out));
-    else if (dtype == 5) hipLaunchKernelGGL(k_synth<int32_t>, dim3(grid), dim3(kThreads), 0, st, seed, frame0,
+    else if (dtype == TRPX_I32) hipLaunchKernelGGL(k_synth<int32_t>, dim3(grid), dim3(kThreads), 0, st, seed, frame0,
                                             (uint64_t)n_values, total, static_cast<int32_t*>(out));
     else return hipErrorInvalidValue;
     return hipGetLastError();

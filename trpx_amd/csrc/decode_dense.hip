@@ -32,7 +32,7 @@
 // Dependent steps per 512 x 512 frame (W = 2, 128 segments of ~170 blocks): 170 (spec) + ~320 (the longest of 127 links: a guess
 // chain merges at ~1.5 % per block) + 170 (write) against 3.5 x 341, at four wavefronts per SIMD instead of two.
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 #include "seg_common.hpp"
 

@@ -15,7 +15,7 @@
 // HBM traffic per frame: S (stream, read twice: walk + unpack) + n_blocks (widths, written+read)
 // + N*sizeof(T) (pixels, written once).  Algorithmic bytes: S + N*sizeof(T).
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 #include "unpack_common.hpp"
 #include "unpack_tile.hpp"
@@ -109,12 +109,9 @@ __global__ __launch_bounds__(kThreads) void k_walk_groups(const uint8_t* __restr
         const uint64_t two = (uint64_t)(d < n_dw ? s32[d] : 0u) | ((uint64_t)(d + 1 < n_dw ? s32[d + 1] : 0u) << 32);
         const uint32_t bits = (uint32_t)(two >> (abit & 31u));
         uint32_t hl = 1;
-        if (!(bits & 1u)) {                                  // Terse.hpp:361-370
-            w = (bits >> 1) & 7u; hl = 4;
-            if (w == 7u) {
-                w += (bits >> 4) & 3u; hl = 6;
-                if (w == 10u) { w += (bits >> 6) & 63u; hl = 12; }
-            }
+        if (!(bits & 1u)) {                                  // Terse.hpp:361
+            const ExplicitHeader h = parse_explicit_header(bits);
+            w = h.w; hl = h.len;
         }
         if (w > max_w) { bad = true; break; }
         widths[frame * g.n_blocks + b] = (uint8_t)w;
@@ -162,17 +159,14 @@ static hipError_t launch_decode_fast_t(const DecodeArgs& a, bool have_index, boo
     }
     prof.mark(st);
     if (have_index && per_frame) {                              // many small frames: the per-frame decoder with the widths given
-        constexpr int dtype = PixelTraits<T>::bits == 8 ? (PixelTraits<T>::is_signed ? 1 : 0)
-                              : PixelTraits<T>::bits == 16 ? (PixelTraits<T>::is_signed ? 3 : 2) : (PixelTraits<T>::is_signed ? 5 : 4);
-        const hipError_t e = launch_decode_frames_indexed(dtype, a, nullptr, st);
+        const hipError_t e = launch_decode_frames_indexed(PixelTraits<T>::dtype, a, nullptr, st);
         prof.mark(st);
         return e;
     }
 #ifndef TRPX_INDEXED_LARGE_TILES
     if (have_index && sizeof(T) < 4 && g.n_blocks >= (1u << 18) &&
         8 * (uint64_t)g.n_blocks * (12u + 12u * max_w) < (1ull << 31)) {   // large frames of 8/16-bit pixels with their index: units of the per-frame decoder, as the index route extracts them (decode_frame.hip)
-        constexpr int dtype = PixelTraits<T>::bits == 8 ? (PixelTraits<T>::is_signed ? 1 : 0) : (PixelTraits<T>::is_signed ? 3 : 2);
-        const hipError_t e = launch_decode_units_indexed(dtype, a, st, nullptr);
+        const hipError_t e = launch_decode_units_indexed(PixelTraits<T>::dtype, a, st, nullptr);
         prof.mark(st);
         return e;
     }
@@ -193,15 +187,7 @@ static hipError_t launch_unpack_tiles_t(const DecodeArgs& a, hipStream_t st, con
     return hipGetLastError();
 }
 hipError_t launch_unpack_tiles(int dtype, const DecodeArgs& a, hipStream_t st, const uint32_t* frame_mode) {
-    switch (dtype) {
-    case 0: return launch_unpack_tiles_t<uint8_t>(a, st, frame_mode);
-    case 1: return launch_unpack_tiles_t<int8_t>(a, st, frame_mode);
-    case 2: return launch_unpack_tiles_t<uint16_t>(a, st, frame_mode);
-    case 3: return launch_unpack_tiles_t<int16_t>(a, st, frame_mode);
-    case 4: return launch_unpack_tiles_t<uint32_t>(a, st, frame_mode);
-    case 5: return launch_unpack_tiles_t<int32_t>(a, st, frame_mode);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_unpack_tiles_t<T>(a, st, frame_mode); });
 }
 
 hipError_t launch_walk_lds_only(const DecodeArgs& a, uint32_t max_w, const uint32_t* only, hipStream_t st, const uint32_t* list = nullptr);
@@ -238,15 +224,7 @@ hipError_t launch_walk_lds_only(const DecodeArgs& a, uint32_t max_w, const uint3
 }
 
 hipError_t launch_decode_fast(int dtype, const DecodeArgs& a, bool have_index, hipStream_t st, bool per_frame) {
-    switch (dtype) {
-    case 0: return launch_decode_fast_t<uint8_t>(a, have_index, per_frame, st);
-    case 1: return launch_decode_fast_t<int8_t>(a, have_index, per_frame, st);
-    case 2: return launch_decode_fast_t<uint16_t>(a, have_index, per_frame, st);
-    case 3: return launch_decode_fast_t<int16_t>(a, have_index, per_frame, st);
-    case 4: return launch_decode_fast_t<uint32_t>(a, have_index, per_frame, st);
-    case 5: return launch_decode_fast_t<int32_t>(a, have_index, per_frame, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_fast_t<T>(a, have_index, per_frame, st); });
 }
 
 }  // namespace trpx

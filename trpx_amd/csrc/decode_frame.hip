@@ -20,7 +20,7 @@
 // Best for many small frames (one workgroup each); few huge frames are better served by the tiled
 // kernels of decode_fast.hip.
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 #include "unpack_common.hpp"
 
@@ -75,7 +75,7 @@ __device__ __forceinline__ void lds_dma16(const uint32_t* src_uniform, uint32_t 
 }
 
 // MODE 0: decode.  MODE 1: the block widths are known (a decode index: widths[] and the bit offset of every 256th block,
-// encode_kernels.hpp) and wave 0 turns them into the position entries with a prefix sum instead of walking the header chain --
+// launchers.hpp) and wave 0 turns them into the position entries with a prefix sum instead of walking the header chain --
 // everything else is the same kernel; used for trpx_decode_indexed on stacks of small frames and for the frames k_decode_frames
 // hands to the position-parallel walk, once that has written their index.  MODE 2: the walker walks, and the other waves write
 // the index (widths, group offsets) instead of pixels: trpx_build_index on stacks of small frames (header-dense frames are
@@ -118,7 +118,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
     const uint32_t lane = (uint32_t)lane_id();
     const int hw_wave = wave_id();
     // The unit of work: a whole frame (item = frame) or, with a part table, the blocks [b0, b1) of a frame with the chain state
-    // in front of them (encode_kernels.hpp: PartDesc).  Below, everything is relative to the unit: block numbers, bit positions
+    // in front of them (launchers.hpp: PartDesc).  Below, everything is relative to the unit: block numbers, bit positions
     // (`limit` = the frame's bits behind the unit's first), the output pointer.
     uint64_t frame = item;
     uint32_t pb0 = 0, pb1 = g.n_blocks, ppos0 = 0, pw0 = 0, ppos1 = 0, pw1 = 0;
@@ -460,12 +460,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
                     const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
                     uint32_t e_w = w_prev, new_pos, new_b;
                     if (first < left && first < 64u) {                                // explicit header at block b + first
-                        const uint32_t eb = (uint32_t)__builtin_amdgcn_readlane((int)bits, first);
-                        uint32_t w = (eb >> 1) & 7u, hl = 4;                          // Terse.hpp:362-370
-                        if (w == 7u) {
-                            w += (eb >> 4) & 3u; hl = 6;
-                            if (w == 10u) { w += (eb >> 6) & 63u; hl = 12; }
-                        }
+                        const auto [w, hl] = parse_explicit_header((uint32_t)__builtin_amdgcn_readlane((int)bits, first));
                         if (w > kMaxW) { bad = true; break; }
                         e_w = w;
                         const uint32_t nbv = b + first + 1 == n_blocks ? nb_last : (uint32_t)kBlock;
@@ -837,15 +832,7 @@ static uint32_t units_choose(const DecodeArgs& a, uint64_t* cost_out) {
     return unit_blocks;
 }
 hipError_t launch_decode_units_indexed(int dtype, const DecodeArgs& a, hipStream_t st, const uint32_t* frame_mode) {
-    switch (dtype) {
-    case 0: return launch_decode_units_indexed_t<uint8_t>(a, st, frame_mode);
-    case 1: return launch_decode_units_indexed_t<int8_t>(a, st, frame_mode);
-    case 2: return launch_decode_units_indexed_t<uint16_t>(a, st, frame_mode);
-    case 3: return launch_decode_units_indexed_t<int16_t>(a, st, frame_mode);
-    case 4: return launch_decode_units_indexed_t<uint32_t>(a, st, frame_mode);
-    case 5: return launch_decode_units_indexed_t<int32_t>(a, st, frame_mode);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_units_indexed_t<T>(a, st, frame_mode); });
 }
 
 // The index of every frame of a stack of small frames (MODE 2 above); T stands for the width limit only.
@@ -895,15 +882,7 @@ static hipError_t launch_decode_frames_indexed_t(const DecodeArgs& a, const uint
 
 // Per-frame decode of frames whose index (a.widths, a.tile_off) is known; same preconditions as launch_decode_frames.
 hipError_t launch_decode_frames_indexed(int dtype, const DecodeArgs& a, const uint32_t* list, hipStream_t st) {
-    switch (dtype) {
-    case 0: return launch_decode_frames_indexed_t<uint8_t>(a, list, st);
-    case 1: return launch_decode_frames_indexed_t<int8_t>(a, list, st);
-    case 2: return launch_decode_frames_indexed_t<uint16_t>(a, list, st);
-    case 3: return launch_decode_frames_indexed_t<int16_t>(a, list, st);
-    case 4: return launch_decode_frames_indexed_t<uint32_t>(a, list, st);
-    case 5: return launch_decode_frames_indexed_t<int32_t>(a, list, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_frames_indexed_t<T>(a, list, st); });
 }
 
 template <typename T>
@@ -927,8 +906,7 @@ static hipError_t launch_decode_frames_t(const DecodeArgs& a, hipStream_t st) {
         // where that does not work out are listed and get theirs from the position-parallel walk, then every frame's tiles are
         // extracted with the widths given.
         if (!defer) return hipErrorInvalidValue;
-        constexpr int dt = PixelTraits<T>::bits == 8 ? (PixelTraits<T>::is_signed ? 1 : 0)
-                           : PixelTraits<T>::bits == 16 ? (PixelTraits<T>::is_signed ? 3 : 2) : (PixelTraits<T>::is_signed ? 5 : 4);
+        constexpr int dt = PixelTraits<T>::dtype;
         constexpr bool narrow = sizeof(T) < 4;
         const uint32_t* frame_mode = nullptr;
         hipError_t e = launch_build_index_chain(a, (uint32_t)PixelTraits<T>::bits, narrow, &frame_mode, st);
@@ -968,9 +946,7 @@ static hipError_t launch_decode_frames_t(const DecodeArgs& a, hipStream_t st) {
                            a.frame_offsets, a.geom, static_cast<T*>(a.pixels_out), defer, a.status);
     prof.mark(st);
     if (defer) {
-        const hipError_t e = launch_decode_deferred(PixelTraits<T>::bits == 8 ? (PixelTraits<T>::is_signed ? 1 : 0)
-                                                    : PixelTraits<T>::bits == 16 ? (PixelTraits<T>::is_signed ? 3 : 2)
-                                                                                 : (PixelTraits<T>::is_signed ? 5 : 4), a, st);
+        const hipError_t e = launch_decode_deferred(PixelTraits<T>::dtype, a, st);
         prof.mark(st);
         if (e != hipSuccess) return e;
     }
@@ -980,15 +956,7 @@ static hipError_t launch_decode_frames_t(const DecodeArgs& a, hipStream_t st) {
 // Preconditions (checked by the caller): block = 12, frame offsets known, frames of < 2^26 bits (less one step's overshoot);
 // pixels_out aligned to the pixel type, any pixel count per frame.
 hipError_t launch_decode_frames(int dtype, const DecodeArgs& a, hipStream_t st) {
-    switch (dtype) {
-    case 0: return launch_decode_frames_t<uint8_t>(a, st);
-    case 1: return launch_decode_frames_t<int8_t>(a, st);
-    case 2: return launch_decode_frames_t<uint16_t>(a, st);
-    case 3: return launch_decode_frames_t<int16_t>(a, st);
-    case 4: return launch_decode_frames_t<uint32_t>(a, st);
-    case 5: return launch_decode_frames_t<int32_t>(a, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_frames_t<T>(a, st); });
 }
 
 }  // namespace trpx

@@ -28,7 +28,7 @@
 #include <cstring>
 
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "walk_serial.hpp"
 
 namespace trpx {
@@ -180,12 +180,8 @@ __device__ ChainHit chain_walk(Rd& rd, uint64_t& pos, uint32_t& w, uint64_t nblk
             pos = readlane64(cpos, end);
             return {b + end, kMode == 1 || kMode == 3 ? readlane64(cpv, end) : 0ull};
         }
-        if (first < 64u) {                                                 // explicit header (Terse.hpp:362-369)
-            uint32_t nw = (bits >> 1) & 7u, hl = 4;
-            if (nw == 7u) {
-                nw += (bits >> 4) & 3u; hl = 6;
-                if (nw == 10u) { nw += (bits >> 6) & 63u; hl = 12; }
-            }
+        if (first < 64u) {                                                 // explicit header
+            auto [nw, hl] = parse_explicit_header(bits);
             if (nw > max_w) nw = 0;
             const uint64_t npos = cpos + hl + 12ull * nw;
             pos = readlane64(npos, first);
@@ -328,11 +324,7 @@ __global__ __launch_bounds__(kWave) void k_loc_chase(const uint32_t* __restrict_
             uint64_t fin;
             if (bits & 1u) fin = pos + 1 + (uint64_t)nb_last * w;
             else {
-                uint32_t nw = (bits >> 1) & 7u, hl = 4;
-                if (nw == 7u) {
-                    nw += (bits >> 4) & 3u; hl = 6;
-                    if (nw == 10u) { nw += (bits >> 6) & 63u; hl = 12; }
-                }
+                const auto [nw, hl] = parse_explicit_header(bits);
                 fin = pos + hl + (uint64_t)nb_last * nw;
             }
             s += 1 + (fin - 8 * s) / 8;

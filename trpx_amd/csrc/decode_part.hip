@@ -35,7 +35,7 @@
 //
 // HBM traffic: the stream once more (walk only: no pixels), 0.2 of the algorithmic bytes of a u16 stack.
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include <stdlib.h>
 
 namespace trpx {
@@ -668,12 +668,7 @@ __device__ __forceinline__ void part_walk(PartWin& W, uint32_t* __restrict__ s_c
             if (lane < n_done) ent[b + lane < capm1 ? b + lane : capm1] = (uint8_t)w_prev;
         }
         if (first < kT) {                                                     // explicit header at candidate `first`
-            const uint32_t eb = (uint32_t)__builtin_amdgcn_readlane((int)bits, (int)first);
-            uint32_t w = (eb >> 1) & 7u, hl = 4;                              // Terse.hpp:362-370
-            if (w == 7u) {
-                w += (eb >> 4) & 3u; hl = 6;
-                if (w == 10u) { w += (eb >> 6) & 63u; hl = 12; }
-            }
+            auto [w, hl] = parse_explicit_header((uint32_t)__builtin_amdgcn_readlane((int)bits, (int)first));
             if (w > max_w) {
                 if (!tolerant) { bad = true; break; }
                 if (abort_illegal) {                                          // (stops behind the illegal header, as the fast steps do)
@@ -732,12 +727,7 @@ __device__ __forceinline__ uint32_t part_rewalk(PartWin& W, uint32_t* __restrict
             ++ci; c = ci < n_ck ? ck[ci] : PartCk{0xFFFFFFFFu, 0u, 0u};
         }
         if (first < kT) {                                                     // explicit header at candidate `first` (Terse.hpp:362-370)
-            const uint32_t eb = (uint32_t)__builtin_amdgcn_readlane((int)bits, (int)first);
-            uint32_t w = (eb >> 1) & 7u, hl = 4;
-            if (w == 7u) {
-                w += (eb >> 4) & 3u; hl = 6;
-                if (w == 10u) { w += (eb >> 6) & 63u; hl = 12; }
-            }
+            auto [w, hl] = parse_explicit_header((uint32_t)__builtin_amdgcn_readlane((int)bits, (int)first));
             if (w > max_w) return 3u;
             pos += first * stride + hl + (uint32_t)kBlock * w;
             w_prev = w;
@@ -999,7 +989,7 @@ hipError_t launch_build_parts(const DecodeArgs& a, uint32_t max_w, hipStream_t s
 // part's pixels cannot be placed before the blocks in front of it are counted.  Here the counting walk leaves what it saw: per
 // block one byte, the width in front of it, in a per-part entry array (relative block numbers: the part's first block is not
 // known yet).  Once k_chain_resolve has the block numbers, k_chain_index turns the entries into the decode index the extraction
-// kernels consume (widths[] by absolute block, bit offset of every 256th block: encode_kernels.hpp) -- 35 vector instructions per
+// kernels consume (widths[] by absolute block, bit offset of every 256th block: launchers.hpp) -- 35 vector instructions per
 // 64 BLOCKS, no dependent chain -- and the frames are extracted as if the caller had brought the index (k_unpack_tiles /
 // k_decode_frames_indexed).  With the decoder's grain out of the way the walk's parts are SMALL (about kChainBlocks blocks): a
 // serial walker is a latency chain, ~130 ns per run of equal widths whatever else runs on the SIMD, so the walk's time is the
@@ -1592,12 +1582,7 @@ __device__ __forceinline__ bool chain_walk_abs(PartWin& W, uint32_t* __restrict_
         const uint32_t first = stop ? (uint32_t)__builtin_ctzll(stop) : 64u;
         uint32_t e_w = w_prev, new_pos, new_b;
         if (first < left && first < 64u) {                                    // explicit header at block b + first
-            const uint32_t eb = (uint32_t)__builtin_amdgcn_readlane((int)bits, (int)first);
-            uint32_t w = (eb >> 1) & 7u, hl = 4;                              // Terse.hpp:362-370
-            if (w == 7u) {
-                w += (eb >> 4) & 3u; hl = 6;
-                if (w == 10u) { w += (eb >> 6) & 63u; hl = 12; }
-            }
+            auto [w, hl] = parse_explicit_header((uint32_t)__builtin_amdgcn_readlane((int)bits, (int)first));
             if (w > max_w) return false;
             e_w = w;
             const uint32_t nbv = at_end && b + first + 1u == nb ? nb_last : (uint32_t)kBlock;

@@ -43,7 +43,7 @@
 // the current one is walked (windows of 256 bytes advancing by 1792 bits since round 6).  A run of zero-width blocks (header bits 1, 1 bit per block: empty detector
 // regions) is consumed 32 blocks per step.
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 #include "unpack_tile.hpp"
 #include "walk_lds.hpp"
@@ -843,9 +843,7 @@ static hipError_t launch_decode_deferred_t(const DecodeArgs& a, hipStream_t st) 
         return hipGetLastError();
     }
     // the listed frames' pixels: the per-frame decoder again, with the widths just written in place of its walker
-    constexpr int dtype = PixelTraits<T>::bits == 8 ? (PixelTraits<T>::is_signed ? 1 : 0)
-                          : PixelTraits<T>::bits == 16 ? (PixelTraits<T>::is_signed ? 3 : 2) : (PixelTraits<T>::is_signed ? 5 : 4);
-    const hipError_t e = launch_decode_frames_indexed(dtype, a, static_cast<const uint32_t*>(a.defer), st);
+    const hipError_t e = launch_decode_frames_indexed(PixelTraits<T>::dtype, a, static_cast<const uint32_t*>(a.defer), st);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
@@ -854,15 +852,7 @@ bool seg_single_wave(const FrameGeom& g, size_t n_frames) { return seg_waves_per
 
 // Decodes the frames flagged in a.defer (see k_decode_frames); needs seg_single_wave(a.geom).
 hipError_t launch_decode_deferred(int dtype, const DecodeArgs& a, hipStream_t st) {
-    switch (dtype) {
-    case 0: return launch_decode_deferred_t<uint8_t>(a, st);
-    case 1: return launch_decode_deferred_t<int8_t>(a, st);
-    case 2: return launch_decode_deferred_t<uint16_t>(a, st);
-    case 3: return launch_decode_deferred_t<int16_t>(a, st);
-    case 4: return launch_decode_deferred_t<uint32_t>(a, st);
-    case 5: return launch_decode_deferred_t<int32_t>(a, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_deferred_t<T>(a, st); });
 }
 
 }  // namespace trpx

@@ -320,7 +320,7 @@ SumPlan sum_plan(int dtype, const FrameGeom& g, uint64_t n_frames, uint64_t grou
     p.tpf = (g.n_blocks + kSub * kThreads - 1) / (kSub * kThreads);
     p.n_out = (n_frames + group - 1) / group;
     const uint64_t per_group = group < n_frames ? group : n_frames;
-    const uint64_t max_fpc = dtype >= 4 ? 0xFFFFFFFFull : 65535ull;   // 32-bit accumulators: 65 535 frames of 8/16-bit values
+    const uint64_t max_fpc = dtype >= TRPX_U32 ? 0xFFFFFFFFull : 65535ull;   // 32-bit accumulators: 65 535 frames of 8/16-bit values
     const uint64_t units = p.n_out * p.tpf;
     uint64_t chunks = units < kSumTargetUnits ? (kSumTargetUnits + units - 1) / units : 1;
     if (chunks > per_group) chunks = per_group;
@@ -328,7 +328,7 @@ SumPlan sum_plan(int dtype, const FrameGeom& g, uint64_t n_frames, uint64_t grou
     if (fpc > max_fpc) fpc = max_fpc;
     p.fpc = (uint32_t)fpc;
     p.chunks = (uint32_t)((per_group + fpc - 1) / fpc);
-    p.partial_bytes = p.chunks > 1 ? align_up((uint64_t)p.chunks * p.n_out * g.n_values * (dtype >= 4 ? 8 : 4), 256) : 0;
+    p.partial_bytes = p.chunks > 1 ? align_up((uint64_t)p.chunks * p.n_out * g.n_values * (dtype >= TRPX_U32 ? 8 : 4), 256) : 0;
     return p;
 }
 
@@ -342,20 +342,12 @@ static hipError_t launch_sum_t(const SumArgs& a, hipStream_t st) {
 
 hipError_t launch_decode_sum(int dtype, const SumArgs& a, bool clear_status, hipStream_t st) {
     if (clear_status) zero_status(a.status, st);
-    hipError_t e = hipErrorInvalidValue;
-    switch (dtype) {
-    case 0: e = launch_sum_t<uint8_t>(a, st); break;
-    case 1: e = launch_sum_t<int8_t>(a, st); break;
-    case 2: e = launch_sum_t<uint16_t>(a, st); break;
-    case 3: e = launch_sum_t<int16_t>(a, st); break;
-    case 4: e = launch_sum_t<uint32_t>(a, st); break;
-    case 5: e = launch_sum_t<int32_t>(a, st); break;
-    }
+    const hipError_t e = for_pixel_type(dtype, [&]<class T>() { return launch_sum_t<T>(a, st); });
     if (e != hipSuccess || !a.partial) return e;
     const uint64_t n = a.n_out * a.geom.n_values;
     const uint64_t blocks = (n + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(k_sum_reduce, dim3((uint32_t)(blocks < 8192 ? blocks : 8192)), dim3(kThreads), 0, st, a.partial,
-                       dtype >= 4 ? 1 : 0, dtype & 1, a.chunks, n, a.out, a.out_code);
+                       dtype >= TRPX_U32 ? 1 : 0, dtype & 1, a.chunks, n, a.out, a.out_code);
     return hipGetLastError();
 }
 

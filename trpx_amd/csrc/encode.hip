@@ -12,7 +12,7 @@
 // Data layout in HBM: pixels [frame][value] contiguous; output = the compact reference stack;
 // workspace = tile_bits u32[F*T], tile_off u64[F*T], frame_size u64[F].
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 
 namespace trpx {
@@ -487,28 +487,14 @@ static hipError_t launch_encode_generic_t(const EncodeArgs& a, hipStream_t st) {
 
 hipError_t launch_encode_generic(int dtype, const EncodeArgs& a, hipStream_t st) {
     switch (dtype) {
-    case 0: return launch_encode_generic_t<uint8_t>(a, st);
-    case 1: return launch_encode_generic_t<int8_t>(a, st);
-    case 2: return launch_encode_generic_t<uint16_t>(a, st);
-    case 3: return launch_encode_generic_t<int16_t>(a, st);
-    case 4: return launch_encode_generic_t<uint32_t>(a, st);
-    case 5: return launch_encode_generic_t<int32_t>(a, st);
-    case 8: return launch_encode_generic_t<uint64_t>(a, st);
-    case 9: return launch_encode_generic_t<int64_t>(a, st);
+    default: return for_pixel_type(dtype, [&]<class T>() { return launch_encode_generic_t<T>(a, st); });
+    case TRPX_U64: return launch_encode_generic_t<uint64_t>(a, st);             // the 64-bit containers: these kernels only
+    case TRPX_I64: return launch_encode_generic_t<int64_t>(a, st);
     }
-    return hipErrorInvalidValue;
 }
 
 hipError_t launch_encode(int dtype, const EncodeArgs& a, hipStream_t st) {
-    switch (dtype) {
-    case 0: return launch_encode_t<uint8_t>(a, st);
-    case 1: return launch_encode_t<int8_t>(a, st);
-    case 2: return launch_encode_t<uint16_t>(a, st);
-    case 3: return launch_encode_t<int16_t>(a, st);
-    case 4: return launch_encode_t<uint32_t>(a, st);
-    case 5: return launch_encode_t<int32_t>(a, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_encode_t<T>(a, st); });
 }
 
 }  // namespace trpx

@@ -28,7 +28,7 @@
 // TRPX_ERR_HIP-class timeout (7) instead of hanging, in which case the host API re-runs the
 // stack through the two-pass pipeline (encode.hip).
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 #include "profile.hpp"
 #include <stdlib.h>
 #include <mutex>
@@ -1111,15 +1111,7 @@ static hipError_t launch_fused_t(const EncodeArgs& e, void* ws, hipStream_t st) 
 }
 
 hipError_t launch_encode_fused(int dtype, const EncodeArgs& e, void* ws, hipStream_t st) {
-    switch (dtype) {
-    case 0: return launch_fused_t<uint8_t>(e, ws, st);
-    case 1: return launch_fused_t<int8_t>(e, ws, st);
-    case 2: return launch_fused_t<uint16_t>(e, ws, st);
-    case 3: return launch_fused_t<int16_t>(e, ws, st);
-    case 4: return launch_fused_t<uint32_t>(e, ws, st);
-    case 5: return launch_fused_t<int32_t>(e, ws, st);
-    }
-    return hipErrorInvalidValue;
+    return for_pixel_type(dtype, [&]<class T>() { return launch_fused_t<T>(e, ws, st); });
 }
 
 }  // namespace trpx

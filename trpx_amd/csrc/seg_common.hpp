@@ -3,7 +3,7 @@
 // (counting / writing steps, hand-scheduled), the run guess.  See the head of decode_seg.hip for the scheme.
 #pragma once
 #include "codec_common.hpp"
-#include "encode_kernels.hpp"
+#include "launchers.hpp"
 
 namespace trpx {
 
@@ -399,9 +399,7 @@ __device__ __forceinline__ void seg_walk(const SegCtx& c, uint32_t* __restrict__
             const uint32_t* row = win + lane * kSegRow + dw;
             const uint32_t bits = __builtin_amdgcn_alignbit(row[1], row[0], li);          // 32 stream bits from pos
             const bool same = (bits & 1u) != 0u;                                          // Terse.hpp:361
-            const uint32_t w3 = (bits >> 1) & 7u, wa = 7u + ((bits >> 4) & 3u), wb = 10u + ((bits >> 6) & (WRITE ? 63u : wb_mask));
-            const uint32_t wx = w3 != 7u ? w3 : (wa != 10u ? wa : wb);                    // Terse.hpp:362-370
-            const uint32_t hx = w3 != 7u ? 4u : (wa != 10u ? 6u : 12u);
+            const auto [wx, hx] = parse_explicit_header_select(bits, WRITE ? 63u : wb_mask);
             uint32_t wn = same ? w : wx;
             const bool wide = WRITE && wn > c.max_w;                                       // (counting passes take any width: see above)
             wn = wide ? 0u : wn;

@@ -60,9 +60,8 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
                 const bool run = first >= 64u;
                 uint32_t e_w = w_prev, adv = 0;
                 if (!run) {                                                     // (wave-uniform branch)
-                    const uint32_t w3 = (bits >> 1) & 7u, wa = 7u + ((bits >> 4) & 3u), wb = 10u + ((bits >> 6) & 63u);
-                    const uint32_t wk = w3 != 7u ? w3 : (wa != 10u ? wa : wb);
-                    const uint32_t advk = (w3 != 7u ? 4u : (wa != 10u ? 6u : 12u)) + kBlock * wk;
+                    const auto [wk, hlk] = parse_explicit_header_select(bits);
+                    const uint32_t advk = hlk + kBlock * wk;
                     e_w = (uint32_t)__builtin_amdgcn_readlane((int)wk, (int)first);
                     adv = (uint32_t)__builtin_amdgcn_readlane((int)advk, (int)first);
                 }
@@ -131,12 +130,7 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
         const bool explicit_hdr = first < left && first < 64u;             // block b + first has an explicit header
         uint32_t new_pos, new_b;
         if (explicit_hdr) {
-            const uint32_t eb = (uint32_t)__builtin_amdgcn_readlane((int)bits, first);   // scalar parse (Terse.hpp:362-370)
-            uint32_t w = (eb >> 1) & 7u, hl = 4;
-            if (w == 7u) {
-                w += (eb >> 4) & 3u; hl = 6;
-                if (w == 10u) { w += (eb >> 6) & 63u; hl = 12; }
-            }
+            const auto [w, hl] = parse_explicit_header((uint32_t)__builtin_amdgcn_readlane((int)bits, first));   // scalar parse
             if (w > max_w) { bad = true; break; }
             e_w = w;
             const uint32_t nbv = b + first + 1 == n_blocks ? nb_last : (uint32_t)kBlock;

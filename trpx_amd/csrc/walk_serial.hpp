@@ -51,11 +51,7 @@ __device__ uint64_t walk_frame(const uint32_t* __restrict__ s32, uint64_t n_dw, 
         bool lane_bad = false;
         if (lane == first && in_range) {                                 // explicit header
             if (!readable) lane_bad = true;
-            uint32_t w = (bits >> 1) & 7u, hl = 4;                       // Terse.hpp:362
-            if (w == 7u) {
-                w += (bits >> 4) & 3u; hl = 6;                           // :365
-                if (w == 10u) { w += (bits >> 6) & 63u; hl = 12; }       // :368
-            }
+            auto [w, hl] = parse_explicit_header(bits);
             if (w > max_w) { lane_bad = true; w = 0; }
             const uint32_t nbv = cb + 1 == g.n_blocks ? nb_last : g.block;
             npos = cpos + hl + (uint64_t)nbv * w;
