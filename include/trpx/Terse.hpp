@@ -211,6 +211,42 @@ public:
                                            (unsigned)group, out, -1), "Terse::prolix_sum");
     }
 
+    /// The rectangle [y0, y0 + h) x [x0, x0 + w) of frames [first_frame, first_frame + n_frames) to `out` (n_frames x h x w
+    /// values, frame by frame, row by row) in one device call, without expanding whole frames (trpx_decode_roi_host).
+    /// dim() = {width, height} must be set.  The value type of `out` is the narrowest integer type that holds the object's
+    /// values: (u)int8_t for bits_per_val() <= 8, (u)int16_t for <= 16, (u)int32_t for <= 32, signed as is_signed().
+    template <typename Iterator>
+        requires requires(Iterator& i) { *i; }
+    void prolix_roi(Iterator out, std::size_t y0, std::size_t x0, std::size_t h, std::size_t w, std::size_t first_frame = 0,
+                    std::size_t n_frames = std::size_t(-1)) {
+        using V = typename std::iterator_traits<Iterator>::value_type;
+        static_assert(std::is_integral_v<V> && sizeof(V) <= 4, "prolix_roi: an integer type of at most 32 bits");
+        if (d_dim.size() != 2 || d_dim[0] * d_dim[1] != d_size) throw std::invalid_argument("prolix_roi: dim() must be {width, height} of the frames");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_roi: values of more than 32 bits are not supported");
+        const unsigned bits = d_prolix_bits <= 8 ? 8 : d_prolix_bits <= 16 ? 16 : 32;
+        if (8 * sizeof(V) != bits || std::is_signed_v<V> != d_signed)
+            throw std::invalid_argument("prolix_roi: the output type must be the narrowest integer type that holds the values");
+        if (first_frame > number_of_frames()) throw std::invalid_argument("prolix_roi: frame index out of range");
+        n_frames = std::min(n_frames, number_of_frames() - first_frame);
+        const std::size_t width = d_dim[0], height = d_dim[1];
+        if (h == 0 || w == 0 || y0 > height || h > height - y0 || x0 > width || w > width - x0)
+            throw std::invalid_argument("prolix_roi: the rectangle leaves the frame");
+        if (n_frames == 0) return;
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        std::vector<std::uint32_t> boxes;
+        for (std::size_t f = 0; f < n_frames; ++f) boxes.insert(boxes.end(), {std::uint32_t(first_frame + f), std::uint32_t(y0), std::uint32_t(x0)});
+        std::vector<V> tmp;
+        V* dst;
+        if constexpr (std::is_pointer_v<Iterator>) dst = out;
+        else { tmp.resize(n_frames * h * w); dst = tmp.data(); }
+        detail::check(trpx_decode_roi_host(detail::dtype_of<V>(), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                           d_frame_sizes.size(), d_block, width, boxes.data(), n_frames, (unsigned)h, (unsigned)w, dst, -1),
+                      "Terse::prolix_roi");
+        if constexpr (!std::is_pointer_v<Iterator>) std::copy(tmp.begin(), tmp.end(), out);
+    }
+
     std::size_t size() const { return d_size; }                                   // Terse.hpp:396
     std::size_t number_of_frames() const { return d_frame_sizes.size(); }         // :403
     std::vector<std::size_t> const& dim() const { return d_dim; }                 // :410

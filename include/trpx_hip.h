@@ -266,6 +266,47 @@ int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t 
                          unsigned group, void* sums_out, int device);
 
 /*
+ * Box decode: boxes of pixels straight from the stream and its decode index, without expanding the frames.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32; the output has the same type
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_sum: index given -- the kernel runs alone, no workspace is used;
+ *                  offsets only -- the index is built in the workspace by trpx_build_index's walk; offsets NULL -- the frames
+ *                  are located in the workspace first.  workspace: DEVICE, 8-byte aligned, >=
+ *                  trpx_decode_roi_workspace_bytes() (the need with offsets and index both NULL), may be NULL with an index
+ *   width          row length of a frame: n_values % width == 0, height = n_values / width
+ *   boxes          DEVICE const uint32_t[n_boxes][3] = {frame, y0, x0}, 4-byte aligned (a device list: a picker on the GPU can
+ *                  feed it, a captured graph is replayed with new boxes).  All boxes are box_h x box_w, 1 <= box_h <= height,
+ *                  1 <= box_w <= width; they may overlap, repeat and come in any order
+ *   pixels_out     DEVICE T[n_boxes][box_h][box_w], compact, aligned to T: [i][r][c] = pixel (y0 + r) * width + x0 + c of
+ *                  frame boxes[i].frame
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT when a 256-block group the kernel walks does
+ *                  not end where the next group's offset (the last group: the frame's size) says, a block is wider than dtype
+ *                  allows, or a read would leave the frame; TRPX_ERR_INVALID_ARG when a box has frame >= n_frames, y0 + box_h
+ *                  > height or x0 + box_w > width -- that box's output is unspecified, the other boxes are still correct.  With
+ *                  errors of both kinds either is reported.  ONLY THE GROUPS THE BOXES TOUCH ARE READ AND VALIDATED: status 0
+ *                  says nothing about the rest of the stack (with offsets or index NULL the locator's / the walk's verdict on
+ *                  the whole stack is reported as by trpx_decode_sum).
+ * The stream is read in aligned 32-bit words, as by every decoder here: nothing outside terse[0 .. align4(terse_bytes)) is read,
+ * nothing outside pixels_out is written.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL; box frame numbers are relative to a.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits;
+ * TRPX_ERR_INVALID_ARG for an unknown dtype, width 0 or not dividing n_values, box_h / box_w 0 or larger than the frame,
+ * n_boxes 0, null or misaligned pointers, an index without offsets; TRPX_ERR_CAPACITY for a workspace that is too small.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the
+ * host from n_boxes, box_h, box_w, width and n_values alone, never from the boxes' contents.
+ * trpx_decode_roi_host: host terse / frame_offsets (or NULL) / boxes / pixels_out; checks the boxes on the host
+ * (TRPX_ERR_INVALID_ARG for one that leaves the stack), stages, calls trpx_decode_roi and synchronises.
+ */
+size_t trpx_decode_roi_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block);
+int trpx_decode_roi(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                    size_t n_values, size_t n_frames, unsigned block, size_t width, const uint32_t* boxes, size_t n_boxes,
+                    unsigned box_h, unsigned box_w, void* pixels_out, uint32_t* status, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                         size_t n_frames, unsigned block, size_t width, const uint32_t* boxes, size_t n_boxes,
+                         unsigned box_h, unsigned box_w, void* pixels_out, int device);
+
+/*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
  * box regenerates exactly the pixels the oracle anchors were computed on.  dtype U16 or I32.
  */

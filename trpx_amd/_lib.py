@@ -58,6 +58,9 @@ SYMBOLS = {
     "trpx_decode_sum_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _U]),
     "trpx_decode_sum": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _U, _P, _P, _P, _SZ, _P]),
     "trpx_decode_sum_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _U, _P, _I]),
+    "trpx_decode_roi_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
+    "trpx_decode_roi": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _SZ, _P, _SZ, _U, _U, _P, _P, _P, _SZ, _P]),
+    "trpx_decode_roi_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _SZ, _P, _SZ, _U, _U, _P, _I]),
     "trpx_gather_workspace_bytes": (_SZ, [_SZ, _I]),
     "trpx_gather_frame_offsets": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P, _SZ, _P]),
     "trpx_encode_sharded_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _I]),

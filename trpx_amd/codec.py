@@ -260,3 +260,46 @@ def decode_sum(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
                                     index.data_ptr() if index is not None else None, n_values, n_frames, block, group,
                                     out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
     return out, status
+
+
+def decode_roi_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, block: int = BLOCK) -> int:
+    return lib().trpx_decode_roi_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block)
+
+
+def decode_roi(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, width: int,
+               boxes: torch.Tensor, box_shape, index: torch.Tensor | None = None, out: torch.Tensor | None = None,
+               workspace: Workspace | None = None, status: torch.Tensor | None = None, block: int = BLOCK):
+    """Boxes of pixels of a stack resident on the GPU (trpx_decode_roi), without decoding its frames to memory.
+
+    ``dtype`` is the stream's pixel type and the output's; ``width`` the row length of a frame; ``boxes`` a contiguous
+    ``[n, 3]`` device tensor of int32 / uint32 rows ``(frame, y0, x0)``; ``box_shape = (box_h, box_w)`` for all of them.
+    Returns (out [n, box_h, box_w], status); asynchronous on the current stream, like ``decode``.  status[0] is 1 when a box
+    leaves the stack (the other boxes are still right) and 5 for a corrupt stream or index; only the parts of the stack the
+    boxes touch are validated.  ``frame_offsets = None``: the frames are located first; ``index = None``: the decode index is
+    built on the way (both in ``workspace``)."""
+    tdt = torch_dtype(dtype)
+    code = dtype_code(tdt)
+    dev = terse.device
+    if boxes.dtype not in (torch.int32, torch.uint32) or boxes.dim() != 2 or boxes.shape[1] != 3 or not boxes.is_contiguous():
+        raise TypeError("decode_roi: boxes must be a contiguous [n, 3] tensor of int32 / uint32")
+    if boxes.device != dev:
+        raise ValueError("decode_roi: boxes must live on the stack's device")
+    box_h, box_w = (int(x) for x in box_shape)
+    n_boxes = boxes.shape[0]
+    if out is None:
+        out = torch.empty((n_boxes, box_h, box_w), dtype=tdt, device=dev)
+    elif out.dtype != tdt or out.numel() != n_boxes * box_h * box_w or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_roi: out must be a contiguous {tdt} tensor of {n_boxes} x {box_h} x {box_w} elements on {dev}")
+    if status is None:
+        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    ws_ptr, ws_bytes = None, 0
+    if index is None or frame_offsets is None:
+        ws = (workspace or Workspace(dev)).get(lib().trpx_decode_roi_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_roi(code, terse.data_ptr(), terse.numel(),
+                                    frame_offsets.data_ptr() if frame_offsets is not None else None,
+                                    index.data_ptr() if index is not None else None, n_values, n_frames, block, width,
+                                    boxes.data_ptr(), n_boxes, box_h, box_w, out.data_ptr(), status.data_ptr(), ws_ptr, ws_bytes,
+                                    _stream_ptr(terse)))
+    return out, status

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/trpx_hip.h"
+#include "decode_roi.hpp"
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -653,15 +654,47 @@ bool sum_out_ok(int out_dtype) {
            out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
 }
 size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
-// workspace: [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)] [partial slab]
-struct SumWs { size_t offsets, region, partial, total; };
-SumWs sum_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, size_t group, bool have_offsets, bool have_index) {
-    SumWs w;
+// The consumers of a decode index (trpx_decode_sum, trpx_decode_roi) take three input forms: index given; offsets only -- the
+// index is built by trpx_build_index's walk; neither -- the frames are located first.  Their workspace starts with what the
+// missing inputs need: [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)].
+struct IndexWs { size_t offsets, region, total; };
+IndexWs index_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, bool have_offsets, bool have_index) {
+    IndexWs w;
     w.offsets = 0;
     w.region = have_offsets ? 0 : trpx::align_up(8 * (n_frames + 1), 256);
     const size_t idx = have_index ? 0 : idx_layout(g, n_frames, trpx_dtype_size(dtype)).total;
     const size_t loc = have_offsets ? 0 : trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    w.partial = w.region + trpx::align_up(std::max(idx, loc), 256);
+    w.total = w.region + trpx::align_up(std::max(idx, loc), 256);
+    return w;
+}
+// Makes *frame_offsets and *index valid, in the workspace where the caller gave none.  *clear: the consumer still has to clear
+// the status block (false once the locator or the walk has written its verdict there).
+int index_in_workspace(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t** frame_offsets, const void** index,
+                       size_t n_values, size_t n_frames, unsigned block, const trpx::FrameGeom& g, uint32_t* status, char* ws,
+                       const IndexWs& w, void* stream, bool* clear) {
+    *clear = true;
+    if (!*frame_offsets) {                                                      // index-free: locate the frames first (its scratch: the index region)
+        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
+        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, 8u * (uint32_t)trpx_dtype_size(dtype), offs, status,
+                                    ws + w.region, static_cast<hipStream_t>(stream)));
+        *frame_offsets = offs;
+        *clear = false;                                                         // (the locator's verdict stays)
+    }
+    if (!*index) {                                                              // the walk of trpx_build_index, into the workspace
+        const int rc = build_index_impl(dtype, terse, terse_bytes, *frame_offsets, n_values, n_frames, block, ws + w.region, status,
+                                        *clear, stream);
+        if (rc) return rc;
+        *index = ws + w.region;
+        *clear = false;
+    }
+    return TRPX_OK;
+}
+// trpx_decode_sum's workspace: the above, then [partial slab]
+struct SumWs { IndexWs front; size_t partial, total; };
+SumWs sum_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, size_t group, bool have_offsets, bool have_index) {
+    SumWs w;
+    w.front = index_ws(dtype, g, terse_bytes, n_frames, have_offsets, have_index);
+    w.partial = w.front.total;
     w.total = w.partial + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes;
     return w;
 }
@@ -707,21 +740,10 @@ int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);
-    const uint32_t max_w = 8u * (uint32_t)trpx_dtype_size(dtype);
     bool clear = true;
-    if (!frame_offsets) {                                                       // index-free: locate the frames first (its scratch: the index region)
-        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
-        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, offs, status, ws + w.region, st));
-        frame_offsets = offs;
-        clear = false;                                                          // (the locator's verdict stays)
-    }
-    if (!index) {                                                               // the walk of trpx_build_index, into the workspace
-        const int rc = build_index_impl(dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, ws + w.region, status,
-                                        clear, stream);
-        if (rc) return rc;
-        index = ws + w.region;
-        clear = false;
-    }
+    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
+                                          w.front, stream, &clear))
+        return rc;
     const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
     trpx::SumArgs a{};
     a.terse = terse;
@@ -741,6 +763,76 @@ int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse
     a.partial = p.chunks > 1 ? ws + w.partial : nullptr;
     a.status = status;
     HIP_TRY(trpx::launch_decode_sum(dtype, a, clear, st));
+    return TRPX_OK;
+}
+
+// ---- box decode (decode_roi.hip) -----------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// the geometry checks the device-pointer and the host-pointer entry point share (sizes from the frame: < 2^29 values, see
+// frame_bits_fit_32); 0 = fine
+int roi_geometry(const char* fn, size_t n_values, size_t width, size_t n_boxes, unsigned box_h, unsigned box_w) {
+    if (width == 0 || n_values % width) return fail(TRPX_ERR_INVALID_ARG, "%s: width %zu does not divide n_values %zu", fn, width, n_values);
+    if (box_h == 0 || box_w == 0 || box_h > n_values / width || box_w > width)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: box %u x %u in frames of %zu x %zu", fn, box_h, box_w, n_values / width, width);
+    if (n_boxes == 0) return fail(TRPX_ERR_INVALID_ARG, "%s: no boxes", fn);
+    return TRPX_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t trpx_decode_roi_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
+        return 0;
+    return index_ws(dtype, g, terse_bytes, n_frames, false, false).total;
+}
+
+int trpx_decode_roi(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                    size_t n_values, size_t n_frames, unsigned block, size_t width, const uint32_t* boxes, size_t n_boxes,
+                    unsigned box_h, unsigned box_w, void* pixels_out, uint32_t* status, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_roi", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {boxes, 4}, {pixels_out, es}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
+                                   {workspace, 8, false}}, &g))
+        return rc;
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_roi: frames of >= 2^32 bits");
+    if (n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (const int rc = roi_geometry("trpx_decode_roi", n_values, width, n_boxes, box_h, box_w)) return rc;
+    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: an index needs its frame offsets");
+    const uint32_t units = trpx::roi_units_per_box(g, (uint32_t)width, box_h, box_w);
+    if ((unsigned __int128)n_boxes * units >= ((unsigned __int128)1 << 40) || (unsigned __int128)n_boxes * box_h * box_w * es >= ((unsigned __int128)1 << 62))
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: bad sizes n_boxes=%zu", n_boxes);
+    const IndexWs w = index_ws(dtype, g, terse_bytes, n_frames, frame_offsets != nullptr, index != nullptr);
+    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_roi: workspace %zu < %zu", workspace_bytes, w.total);
+    if (w.total && !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: null workspace");
+
+    if (w.total) trpx::fused_ws_forget(workspace, workspace_bytes);
+    bool clear = true;
+    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status,
+                                          static_cast<char*>(workspace), w, stream, &clear))
+        return rc;
+    const DecLayout il = idx_layout(g, n_frames, es);
+    trpx::RoiArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.geom = g;
+    a.n_frames = n_frames;
+    a.width = (uint32_t)width;
+    a.height = (uint32_t)(n_values / width);
+    a.boxes = boxes;
+    a.n_boxes = n_boxes;
+    a.box_h = box_h;
+    a.box_w = box_w;
+    a.units_per_box = units;
+    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
+    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    a.out = pixels_out;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_roi(dtype, a, clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -988,6 +1080,44 @@ int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t 
     rc = trpx_decode_sum(dtype, out_dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, group, d_out, d_st, d_ws, ws_bytes, hs);
     if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_sum_host", st))) return rc;
     HIP_TRY(copy_sync(hs, sums_out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                         size_t n_frames, unsigned block, size_t width, const uint32_t* boxes, size_t n_boxes, unsigned box_h,
+                         unsigned box_w, void* pixels_out, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (!terse || !boxes || !pixels_out || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad argument");
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_roi_host: block=%u dtype=%d", block, dtype);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad sizes");
+    if (const int rc = roi_geometry("trpx_decode_roi_host", n_values, width, n_boxes, box_h, box_w)) return rc;
+    const size_t ws_bytes = trpx_decode_roi_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
+    if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad dtype/sizes");
+    if ((unsigned __int128)n_boxes * box_h * box_w * trpx_dtype_size(dtype) >= ((unsigned __int128)1 << 62) || n_boxes >= ((size_t)1 << 40))
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad sizes n_boxes=%zu", n_boxes);
+    for (size_t i = 0; i < n_boxes; ++i)
+        if (boxes[3 * i] >= n_frames || (uint64_t)boxes[3 * i + 1] + box_h > n_values / width || (uint64_t)boxes[3 * i + 2] + box_w > width)
+            return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: box %zu (frame %u, y0 %u, x0 %u) leaves the stack", i, boxes[3 * i],
+                        boxes[3 * i + 1], boxes[3 * i + 2]);
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_roi_host", device, &hs)) return rc;
+    const size_t out_bytes = n_boxes * box_h * box_w * trpx_dtype_size(dtype);
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;                                                 // the offsets, then the boxes
+    uint32_t* d_st = nullptr;
+    void *d_out = nullptr, *d_ws = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = status_slot(&d_st)) || (rc = upload_offsets(hs, frame_offsets, n_frames, 12 * n_boxes, &d_off))) return rc;
+    uint32_t* d_boxes = reinterpret_cast<uint32_t*>(d_off + (n_frames + 1));
+    HIP_TRY(copy_sync(hs, d_boxes, boxes, 12 * n_boxes, hipMemcpyHostToDevice));
+    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_roi(dtype, d_in, terse_bytes, frame_offsets ? d_off : nullptr, nullptr, n_values, n_frames, block, width, d_boxes,
+                         n_boxes, box_h, box_w, d_out, d_st, d_ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_roi_host", st))) return rc;
+    HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

@@ -1,0 +1,178 @@
+// Box decode (trpx_decode_roi): a stack with its decode index -> boxes of pixels, without expanding the frames.  The work unit
+// is (box, 256-block group) on ONE wavefront; a box gets roi_units_per_box() units, the groups between its first and its last
+// pixel at most, and the units behind its last group exit.
+//
+//   per unit   the box (wave-uniform) -> does any row segment of the box meet the group? (frames wider than a group: most
+//              units of a box do not, and exit before loading anything) -> the group's 256 widths and the width in front of
+//              it, four blocks per lane (block = group * 256 + r * 64 + lane) -> header_len + 12 * w -> wave scans from the
+//              group's offset -> the group is validated: it ends where the next group's offset, or the frame's size, says, no
+//              block is wider than the type, nothing lies outside the frame -> for the blocks that hold box pixels ONLY: the
+//              payload dwords straight from the stream into registers, the width-specialised register extraction of
+//              unpack_common.hpp, and the values inside the box stored to their place (rows of a box are short: no line images).
+// Only the groups the boxes touch are read and validated.  HBM traffic: 256 widths + 2 offsets per unit, the payload of the
+// box's blocks, the boxes' pixels.
+#include "codec_common.hpp"
+#include "decode_roi.hpp"
+#include "unpack_common.hpp"
+
+namespace trpx {
+
+namespace {
+
+constexpr int kRoiRows = kTileBlocks / kWave;               // blocks per lane
+
+__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint32_t pick(const uint32_t (&v)[kRoiRows], int r) {   // (the extraction loop stays rolled: one copy of the width dispatch)
+    return r == 0 ? v[0] : r == 1 ? v[1] : r == 2 ? v[2] : v[3];
+}
+
+template <typename T>
+__device__ __forceinline__ T packed_value(const uint32_t (&o)[PackedDwords<T>::n], int k) {
+    if constexpr (sizeof(T) == 4) return (T)o[k];
+    else if constexpr (sizeof(T) == 2) return (T)(o[k >> 1] >> (16 * (k & 1)));
+    else return (T)(o[k >> 2] >> (8 * (k & 3)));
+}
+
+template <typename T>
+__device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
+    constexpr uint32_t bits = (uint32_t)PixelTraits<T>::bits;
+    constexpr int kRaw = 4 * RawQuads<T>::n;
+    const FrameGeom& g = a.geom;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t box = unit / a.units_per_box;
+    const uint32_t k_unit = (uint32_t)(unit - box * a.units_per_box);
+    const uint32_t frame = uniform32(a.boxes[3 * box]), y0 = uniform32(a.boxes[3 * box + 1]), x0 = uniform32(a.boxes[3 * box + 2]);
+    const uint32_t width = a.width;
+    if (frame >= a.n_frames || (uint64_t)y0 + a.box_h > a.height || (uint64_t)x0 + a.box_w > width) {
+        if (k_unit == 0 && lane == 0) atomicMax(&a.status[0], kRoiInvalid);
+        return;
+    }
+    const uint32_t y1 = y0 + a.box_h, x1 = x0 + a.box_w;
+    // ---- the unit's group, and whether a row segment of the box meets it (pixel indices < n_values < 2^29)
+    const uint32_t grp = (y0 * width + x0) / kTileValues + k_unit;
+    if (grp > ((y1 - 1) * width + x1 - 1) / kTileValues) return;
+    const uint32_t p_lo = grp * kTileValues;
+    const uint32_t p_hi = (uint64_t)p_lo + kTileValues < g.n_values ? p_lo + kTileValues : (uint32_t)g.n_values;
+    uint32_t ya = y0;                                       // the first row whose segment ends behind p_lo
+    if (p_lo >= x1) {
+        const uint32_t q = (p_lo - x1) / width + 1;
+        ya = q > ya ? q : ya;
+    }
+    if (ya >= y1 || ya * width + x0 >= p_hi) return;
+
+    // ---- widths -> bit offsets inside the group
+    const uint64_t ti = (uint64_t)frame * g.n_tiles + grp;
+    const bool last = grp + 1 == g.n_tiles;
+    const uint64_t fo = a.frame_offsets[frame], fe = a.frame_offsets[frame + 1];
+    const uint64_t t_off = a.tile_off[ti], t_next = last ? 0 : a.tile_off[ti + 1];
+    const uint8_t* __restrict__ wf = a.widths + (uint64_t)frame * g.n_blocks;
+    uint32_t w[kRoiRows], off[kRoiRows], nb[kRoiRows];      // off: the block's first PAYLOAD bit, group-relative
+    uint32_t total = 0;
+    bool wide = false;
+#pragma unroll
+    for (int r = 0; r < kRoiRows; ++r) {
+        const uint32_t b = grp * kTileBlocks + r * kWave + lane;
+        uint32_t wp = 0;
+        w[r] = 0; nb[r] = 0;
+        if (b < g.n_blocks) {
+            w[r] = wf[b];
+            if (lane == 0) wp = b ? wf[b - 1] : 0u;         // significant_bits = 0 at frame start (Terse.hpp:359)
+            const uint64_t first = (uint64_t)b * kBlock;
+            nb[r] = first + kBlock <= g.n_values ? kBlock : (uint32_t)(g.n_values - first);
+        }
+        const uint32_t left = (uint32_t)__shfl_up((int)w[r], 1, kWave);   // the width in front: the neighbour lane's, one more byte for lane 0
+        if (lane != 0) wp = left;
+        const uint32_t hl = header_len(w[r], wp);
+        const uint32_t len = nb[r] ? hl + nb[r] * w[r] : 0u;
+        const uint32_t inc = wave_inclusive_scan(len);
+        off[r] = total + inc - len + hl;
+        total += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        wide = wide || (nb[r] && w[r] > bits);
+    }
+    // ---- the group against the frame and the next group
+    const uint64_t frame_bits = 8 * (fe - fo);
+    bool bad = __ballot(wide) != 0ull || fe > a.terse_bytes || fe <= fo || frame_bits >= 0xFFFF0000ull ||
+               t_off > frame_bits || total > frame_bits - t_off;
+    const uint64_t end = t_off + total;
+    bad = bad || (last ? 1 + end / 8 != fe - fo : end != t_next);   // S_f = 1 + bits / 8 (Terse.hpp:547)
+    if (bad) {
+        if (lane == 0) atomicMax(&a.status[0], kRoiCorrupt);
+        return;
+    }
+
+    // ---- the blocks that hold box pixels: payload dwords -> registers -> fields -> the box
+    const uint64_t d_frame = fo >> 2;                       // (terse is 4-byte aligned: dwords)
+    const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(a.terse) + d_frame;
+    const uint64_t avail_dw = (a.terse_bytes + 3) / 4 - d_frame;
+    const uint32_t bit0 = 8u * (uint32_t)(fo & 3u) + (uint32_t)t_off;
+    T* __restrict__ out = static_cast<T*>(a.out) + box * a.box_h * a.box_w;
+#pragma unroll 1
+    for (int r = 0; r < kRoiRows; ++r) {
+        const uint32_t wr = pick(w, r), nr = pick(nb, r);
+        const uint32_t p0 = (grp * kTileBlocks + r * kWave + lane) * kBlock;
+        const uint32_t by = p0 / width, bx = p0 - by * width;
+        uint32_t mask = 0;                                  // the block's values inside the box
+        {
+            uint32_t x = bx, y = by;
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) {
+                if ((uint32_t)k < nr && y >= y0 && y < y1 && x >= x0 && x < x1) mask |= 1u << k;
+                if (++x == width) { x = 0; ++y; }
+            }
+        }
+        if (__ballot(mask != 0u) == 0ull) continue;
+        const uint32_t q = bit0 + pick(off, r), d = q >> 5, s = q & 31u;
+        const uint32_t nd = (s + nr * wr + 31u) >> 5;       // dwords that hold the block's fields
+        uint32_t raw[kRaw];
+#pragma unroll
+        for (int j = 0; j < kRaw; ++j) raw[j] = mask && (uint32_t)j < nd && (uint64_t)d + j < avail_dw ? s32[d + j] : 0u;
+        uint32_t o[PackedDwords<T>::n];
+#pragma unroll
+        for (int j = 0; j < PackedDwords<T>::n; ++j) o[j] = 0u;   // w == 0 -> zeros (Terse.hpp:373-374)
+        uint64_t todo = __ballot(mask != 0u && wr != 0u);
+        while (todo) {
+            const int l0 = __builtin_ctzll(todo);
+            uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)wr, l0);
+            const bool mine = mask != 0u && wr == w0;
+            asm volatile("" : "+s"(w0));                    // (the dispatch stays scalar)
+            if (mine) UnpackRegsDispatch<T, 1, PixelTraits<T>::bits>::run(raw, s, w0, o);
+            todo &= ~__ballot(mine);
+        }
+        {
+            uint32_t x = bx, y = by;
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) {
+                if (mask & (1u << k)) out[(uint64_t)(y - y0) * a.box_w + (x - x0)] = packed_value<T>(o, k);
+                if (++x == width) { x = 0; ++y; }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_decode_roi(RoiArgs a) {
+    const uint64_t units = a.n_boxes * a.units_per_box;
+    const uint64_t stride = (uint64_t)gridDim.x * (kThreads / kWave);
+    for (uint64_t unit = (uint64_t)blockIdx.x * (kThreads / kWave) + (uint32_t)wave_id(); unit < units; unit += stride)
+        roi_unit<T>(a, unit);
+}
+
+uint32_t roi_units_per_box(const FrameGeom& g, uint32_t width, uint32_t box_h, uint32_t box_w) {
+    const uint64_t span = (uint64_t)(box_h - 1) * width + box_w;             // first to last pixel of a box
+    const uint64_t units = (span + 2 * kTileValues - 2) / kTileValues + 1;   // ceil((span + 3071) / 3072) + 1
+    return (uint32_t)(units < g.n_tiles ? units : g.n_tiles);
+}
+
+hipError_t launch_decode_roi(int dtype, const RoiArgs& a, bool clear_status, hipStream_t st) {
+    if (clear_status) zero_status(a.status, st);
+    const uint64_t groups = (a.n_boxes * a.units_per_box + kThreads / kWave - 1) / (kThreads / kWave);
+    const uint32_t grid = (uint32_t)(groups < (1ull << 22) ? groups : (1ull << 22));
+    return for_pixel_type(dtype, [&]<class T>() {
+        hipLaunchKernelGGL((k_decode_roi<T>), dim3(grid), dim3(kThreads), 0, st, a);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace trpx

@@ -192,10 +192,7 @@ class Terse:
             raise ValueError("group must be >= 1")
         if self._signed and np.dtype(dtype).kind == "u":
             raise ValueError("signed data cannot be decompressed into unsigned data")            # Terse.hpp:356-357
-        if self._prolix_bits > 32:
-            raise ValueError("prolix_sum: values of more than 32 bits are not supported")
-        bits = 8 if self._prolix_bits <= 8 else 16 if self._prolix_bits <= 16 else 32
-        stream = {8: _lib.U8, 16: _lib.U16, 32: _lib.U32}[bits] + int(self._signed)
+        stream, _ = self._stream_type("prolix_sum")
         out = np.empty((-(-f // group) if f else 0, self._size), np.dtype(dtype))
         if f == 0:
             return out
@@ -204,6 +201,43 @@ class Terse:
         check(lib().trpx_decode_sum_host(stream, _code(dtype, True), buf.ctypes.data, buf.size, offs.ctypes.data, self._size,
                                          f, self._block, group, out.ctypes.data, self._device))
         return out
+
+    def _stream_type(self, what: str):
+        """The narrowest stream type that holds the object's values: (dtype code, numpy dtype)."""
+        if self._prolix_bits > 32:
+            raise ValueError(f"{what}: values of more than 32 bits are not supported")
+        bits = 8 if self._prolix_bits <= 8 else 16 if self._prolix_bits <= 16 else 32
+        code = {8: _lib.U8, 16: _lib.U16, 32: _lib.U32}[bits] + int(self._signed)
+        return code, np.dtype(f"{'i' if self._signed else 'u'}{bits // 8}")
+
+    def prolix_boxes(self, boxes, shape) -> np.ndarray:
+        """Boxes of pixels in ONE GPU call (trpx_decode_roi_host), without decoding whole frames to memory.  ``boxes``: rows
+        ``(frame, y0, x0)``, in any order, overlapping or repeated; ``shape = (h, w)`` for all of them.  ``dim()`` =
+        {width, height} must be set.  Returns [len(boxes), h, w] of the narrowest integer type that holds the object's values."""
+        if len(self._dim) != 2 or self._dim[0] * self._dim[1] != self._size:
+            raise ValueError("prolix_boxes: dim() must be set to {width, height} of the frames")
+        width, height = self._dim
+        h, w = (int(x) for x in shape)
+        b = np.asarray(boxes, dtype=np.int64).reshape(-1, 3)
+        if not (1 <= h <= height and 1 <= w <= width):
+            raise ValueError("prolix_boxes: the box shape does not fit the frame")
+        if b.size and (b.min() < 0 or (b[:, 0] >= self.number_of_frames()).any() or (b[:, 1] + h > height).any() or (b[:, 2] + w > width).any()):
+            raise ValueError("prolix_boxes: a box leaves the stack")
+        code, dt = self._stream_type("prolix_boxes")
+        out = np.empty((b.shape[0], h, w), dt)
+        if b.shape[0] == 0:
+            return out
+        b32 = np.ascontiguousarray(b, dtype=np.uint32)
+        buf = np.frombuffer(self._data, np.uint8)
+        offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+        check(lib().trpx_decode_roi_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, self.number_of_frames(),
+                                         self._block, width, b32.ctypes.data, b32.shape[0], h, w, out.ctypes.data, self._device))
+        return out
+
+    def prolix_roi(self, y0: int, x0: int, h: int, w: int, frames=None) -> np.ndarray:
+        """The same rectangle of every frame in ``frames`` (default: all): [len(frames), h, w] (see ``prolix_boxes``)."""
+        frames = range(self.number_of_frames()) if frames is None else frames
+        return self.prolix_boxes([(int(f), y0, x0) for f in frames], (h, w))
 
     # ---- accessors (Terse.hpp:396-444) --------------------------------------------------------
     def size(self) -> int:
