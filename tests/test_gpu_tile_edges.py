@@ -1,0 +1,84 @@
+"""GPU tests: stream edges of the tiled decoders -- k_unpack_tiles and k_sum_tiles, which are assembled from the tile front end of
+unpack_tile.hpp, and k_decode_roi, which keeps a front end of its own and shares only the helpers of codec_common.hpp: a
+stream whose device base is 4-byte but not 16-byte aligned (the dword-by-dword window loads), and a stream whose buffer ends
+exactly at its last byte (the last 16-byte load of the last tile is the guarded one).  3 frames of 12 * 1024 + 5 values: one
+full tile of k_unpack_tiles, two of the summing kernel, and a partial last block.  The truth is the original pixels and their
+numpy int64 sums: the codec is lossless, so no decoder is trusted.
+
+What each case can tell: "base4" is the one that discriminates -- a decoder that took the 16-byte loads there would read
+misaligned and return wrong pixels.  "exact_end" runs the guarded last load on a buffer of exactly the stream's bytes and checks
+its values; it cannot tell a guarded load from an unguarded one, because the allocator rounds the block up and the bytes behind
+the stream are mapped (the same holds for every test that passes enc.stack())."""
+import numpy as np
+import pytest
+
+from test_gpu_decode_sum import _encode, _random, _to_np, truth
+
+pytestmark = pytest.mark.gpu
+
+FRAMES, WIDTH, HEIGHT = 3, 647, 19                       # 647 * 19 = 12 * 1024 + 5
+VALUES = WIDTH * HEIGHT
+ROUTE_TILED = 2                                          # trpx_set_decode_path: position-parallel walk + k_unpack_tiles
+assert VALUES == 12 * 1024 + 5
+
+
+@pytest.fixture(scope="module", params=[np.uint8, np.int16, np.int32], ids=lambda d: np.dtype(d).name)
+def stack(request):
+    """(pixels, encoded stack, {case: the stream as that case's device tensor}), made once per pixel type."""
+    import torch
+    px = _random(request.param, FRAMES, VALUES, seed=41)
+    enc = _encode(px)
+    s = enc.stack()
+    total = s.numel()
+    assert total == enc.total_bytes()
+    room = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
+    room[4:4 + total] = s
+    off4 = room[4:4 + total]                             # 4 bytes into a larger buffer
+    exact = s.clone()                                    # a buffer of its own that ends with the stream
+    assert off4.data_ptr() % 16 == 4 and exact.numel() == total
+    return px, enc, {"base4": off4, "exact_end": exact}
+
+
+CASES = ["base4", "exact_end"]
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_decode_indexed_tiled(stack, case):
+    from trpx_amd import _lib, codec
+    import torch
+    px, enc, streams = stack
+    assert _lib.lib().trpx_set_decode_path(ROUTE_TILED) == 0
+    try:
+        back, st = codec.decode(streams[case], enc.frame_offsets, VALUES, FRAMES, px.dtype, index=enc.index)
+        torch.cuda.synchronize()
+    finally:
+        _lib.lib().trpx_set_decode_path(0)
+    assert int(st[0].item()) == 0
+    assert np.array_equal(_to_np(back), px)
+
+
+@pytest.mark.parametrize("group", [1, FRAMES])
+@pytest.mark.parametrize("case", CASES)
+def test_decode_sum(stack, case, group):
+    from trpx_amd import codec
+    import torch
+    px, enc, streams = stack
+    sums, st = codec.decode_sum(streams[case], enc.frame_offsets, VALUES, FRAMES, px.dtype, group, out_dtype=torch.int64,
+                                index=enc.index)
+    torch.cuda.synchronize()
+    assert int(st[0].item()) == 0
+    assert np.array_equal(_to_np(sums), truth(px, group, np.int64))
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_decode_roi_last_rows(stack, case):
+    from trpx_amd import codec
+    import torch
+    px, enc, streams = stack
+    box_h = 3                                            # the last rows of the last frame, the frame's last pixel included
+    boxes = torch.tensor([[FRAMES - 1, HEIGHT - box_h, 0]], dtype=torch.int32, device="cuda")
+    out, st = codec.decode_roi(streams[case], enc.frame_offsets, VALUES, FRAMES, px.dtype, WIDTH, boxes, (box_h, WIDTH),
+                               index=enc.index)
+    torch.cuda.synchronize()
+    assert int(st[0].item()) == 0
+    assert np.array_equal(_to_np(out)[0], px[FRAMES - 1].reshape(HEIGHT, WIDTH)[HEIGHT - box_h:])

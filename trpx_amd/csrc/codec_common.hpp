@@ -50,6 +50,11 @@ template <class F> inline hipError_t for_pixel_type(int dtype, F&& f) {
     return hipErrorInvalidValue;
 }
 
+// What the kernels leave in word 0 of a call's status block (atomicMax: the gravest verdict stays).
+constexpr uint32_t kStatusInvalid = 1;               // a box that leaves its stack (trpx_decode_roi)
+constexpr uint32_t kStatusCorrupt = 5;               // chain, index or widths that do not fit the frame / the stream / the type
+static_assert(kStatusInvalid == TRPX_ERR_INVALID_ARG && kStatusCorrupt == TRPX_ERR_CORRUPT, "status words are trpx_status codes");
+
 // Worst-case bits of one block: 12-bit header + 12 full-width values.
 template <typename T> constexpr int max_block_bits() { return 12 + kBlock * PixelTraits<T>::bits; }
 
@@ -154,6 +159,45 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 // wave index as a SCALAR (readfirstlane): branches on it are uniform, so whatever a single wave computes from
 // wave-uniform values stays in SGPRs / on the scalar unit instead of being treated as divergent per-lane data
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// A wave-uniform value said to be one (readfirstlane): it lives in SGPRs, whatever the compiler can prove about it.
+__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    return (uint64_t)uniform32((uint32_t)v) | ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32);
+}
+
+// ---- reading the stream (a 4-byte aligned buffer of n_dw dwords; dwords past its end read as zero) -------------
+// An aligned dword that holds >= 1 valid byte never crosses into an unmapped page.
+__device__ __forceinline__ uint32_t ld_stream_dw(const uint32_t* __restrict__ s32, uint64_t idx, uint64_t n_dw) {
+    return idx < n_dw ? s32[idx] : 0u;
+}
+// 16 bytes at dword index d, dword by dword (V: uint4 or a site's own vector of four dwords)
+template <class V = uint4>
+__device__ __forceinline__ V load_stream16_guarded(const uint32_t* __restrict__ s32, uint64_t d, uint64_t n_dw) {
+    V x;
+    x.x = d < n_dw ? s32[d] : 0u; x.y = d + 1 < n_dw ? s32[d + 1] : 0u;
+    x.z = d + 2 < n_dw ? s32[d + 2] : 0u; x.w = d + 3 < n_dw ? s32[d + 3] : 0u;
+    return x;
+}
+// ... and in one load where the buffer is 16-byte aligned (base16), d % 4 == 0 and all four dwords exist (the tile kernels)
+__device__ __forceinline__ uint4 load_stream16(const uint32_t* __restrict__ s32, uint64_t d, uint64_t n_dw, bool base16) {
+    if (base16 && d + 4 <= n_dw) return *reinterpret_cast<const uint4*>(s32 + d);
+    return load_stream16_guarded(s32, d, n_dw);
+}
+// The bits from bit p on of the dwords ld(i) reads -- an LDS image, a guarded global load: 64 - p % 32 of them are valid.
+template <class Ld, class P>
+__device__ __forceinline__ uint64_t stream_bits(Ld&& ld, P p) {
+    return ((uint64_t)ld(p >> 5) | ((uint64_t)ld((p >> 5) + 1) << 32)) >> (p & 31u);
+}
+// One field of w bits (1 .. 32) at bit p as the pixel type's value in 32 bits: the generic read of a partial block's fields
+// (Bit_pointer.hpp:597-617; sign extension :784-789).
+__device__ __forceinline__ uint32_t field_mask(uint32_t w) { return w >= 32u ? 0xFFFFFFFFu : ((1u << w) - 1u); }
+template <typename T, class Ld, class P>
+__device__ __forceinline__ uint32_t stream_field(Ld&& ld, P p, uint32_t w, uint32_t mask) {
+    uint32_t f = (uint32_t)stream_bits(ld, p) & mask;
+    if (PixelTraits<T>::is_signed) f = (uint32_t)((int32_t)(f << (32u - w)) >> (32u - w));
+    return f;
+}
 
 // Workgroup-wide exclusive scan of one u32 per thread (256 threads = 4 waves).
 // `wave_tot` is a 4-entry LDS array.  Returns the exclusive prefix; *total gets the tile sum.

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(kWave) void k_walk(const uint8_t* __restrict__ ters
                           max_w, widths + frame * g.n_blocks, tile_off + frame * g.n_tiles);
         ok = bits != ~0ull && 1 + bits / 8 == fe - fo;      // S_f = 1 + bits/8 (Terse.hpp:547)
     }
-    if (!ok && lane_id() == 0) atomicMax(&status[0], 5u);   // TRPX_ERR_CORRUPT
+    if (!ok && lane_id() == 0) atomicMax(&status[0], kStatusCorrupt);
 }
 
 // No frame index available: frames are located one after the other (Terse.hpp:562-585).
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kWave) void k_walk_serial(const uint8_t* __restrict
     }
     if (lane_id() == 0) {
         walk_offsets[n_frames] = fo;
-        if (!ok) atomicMax(&status[0], 5u);
+        if (!ok) atomicMax(&status[0], kStatusCorrupt);
     }
 }
 
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_unpack(const uint8_t* __restrict__
 
     if (w) {
         if (pos + (uint64_t)nb * w > 8 * (fe - fo) || w > (uint32_t)PixelTraits<T>::bits) {
-            atomicMax(&status[0], 5u);
+            atomicMax(&status[0], kStatusCorrupt);
         } else {
             const uint32_t* s32 = reinterpret_cast<const uint32_t*>(terse);
             const uint64_t n_dw = (terse_bytes + 3) / 4;
@@ -181,17 +181,13 @@ __global__ __launch_bounds__(kThreads) void k_unpack_g(const uint8_t* __restrict
     const uint64_t pos = tile_off[tile] + excl + hl;
     T* dst = pixels_out + (uint64_t)frame * g.n_values + (uint64_t)b * g.block;
     if (w == 0) { for (uint32_t k = 0; k < nb; ++k) dst[k] = (T)0; return; }
-    if (pos + (uint64_t)nb * w > 8 * (fe - fo) || w > (uint32_t)PixelTraits<T>::bits) { atomicMax(&status[0], 5u); return; }
+    if (pos + (uint64_t)nb * w > 8 * (fe - fo) || w > (uint32_t)PixelTraits<T>::bits) { atomicMax(&status[0], kStatusCorrupt); return; }
     const uint32_t* s32 = reinterpret_cast<const uint32_t*>(terse);
     const uint64_t n_dw = (terse_bytes + 3) / 4;
-    const uint32_t mask = w >= 32u ? 0xFFFFFFFFu : ((1u << w) - 1u);
+    const uint32_t mask = field_mask(w);
     uint64_t abit = 8 * fo + pos;
-    for (uint32_t k = 0; k < nb; ++k, abit += w) {
-        const uint64_t two = (uint64_t)ld_stream_dw(s32, abit >> 5, n_dw) | ((uint64_t)ld_stream_dw(s32, (abit >> 5) + 1, n_dw) << 32);
-        uint32_t u = (uint32_t)(two >> (abit & 31)) & mask;
-        if (PixelTraits<T>::is_signed) u = (uint32_t)((int32_t)(u << (32u - w)) >> (32u - w));
-        dst[k] = (T)u;
-    }
+    for (uint32_t k = 0; k < nb; ++k, abit += w)
+        dst[k] = (T)stream_field<T>([&](uint64_t i) { return ld_stream_dw(s32, i, n_dw); }, abit, w, mask);
 }
 
 template <typename T>
@@ -291,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void k_unpack_conv(const uint8_t* __restr
     const uint64_t pos = tile_off[tile] + excl + hl;
     OutT* dst = pixels_out + (uint64_t)frame * g.n_values + (uint64_t)b * g.block;
     if (w == 0) { for (uint32_t k = 0; k < nb; ++k) dst[k] = (OutT)0; return; }
-    if (pos + (uint64_t)nb * w > 8 * (fe - fo) || w > 64u) { atomicMax(&status[0], 5u); return; }
+    if (pos + (uint64_t)nb * w > 8 * (fe - fo) || w > 64u) { atomicMax(&status[0], kStatusCorrupt); return; }
     const uint32_t* s32 = reinterpret_cast<const uint32_t*>(terse);
     const uint64_t n_dw = (terse_bytes + 3) / 4;
     const uint64_t mask = w >= 64u ? ~0ull : ((1ull << w) - 1ull);
@@ -299,8 +295,7 @@ __global__ __launch_bounds__(kThreads) void k_unpack_conv(const uint8_t* __restr
     for (uint32_t k = 0; k < nb; ++k, abit += w) {                       // fields of up to 64 bits: three dwords
         const uint64_t di = abit >> 5;
         const uint32_t sh = (uint32_t)(abit & 31);
-        const uint64_t two = (uint64_t)ld_stream_dw(s32, di, n_dw) | ((uint64_t)ld_stream_dw(s32, di + 1, n_dw) << 32);
-        uint64_t u = two >> sh;
+        uint64_t u = stream_bits([&](uint64_t i) { return ld_stream_dw(s32, i, n_dw); }, abit);
         if (sh && w > 64u - sh) u |= (uint64_t)ld_stream_dw(s32, di + 2, n_dw) << (64u - sh);
         u &= mask;
         const int64_t v = w >= 64u ? (int64_t)u : (int64_t)(u << (64u - w)) >> (64u - w);   // sign extension (Bit_pointer.hpp:784-789)

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
     const uint32_t g_eff = g.n_blocks / kDenseSegBlocks < G ? (g.n_blocks / kDenseSegBlocks ? g.n_blocks / kDenseSegBlocks : 1u) : G;
     SegCtx c;
     if (!seg_ctx(c, terse, terse_bytes, frame_offsets, frame, g, max_w, g_eff, status)) {
-        if (threadIdx.x == 0) atomicMax(&status[0], 5u);
+        if (threadIdx.x == 0) atomicMax(&status[0], kStatusCorrupt);
         return;
     }
     c.L = (c.L + kSegAdv - 1u) / kSegAdv * kSegAdv;            // (a multiple of the window advance -- and of 128 bits, like seg_len_bits': every region's window grid is the frame's)
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
         if (part && !last && (seg_pack(pos, w) != exit_state || n != my_base + my_cnt)) bad = true;
         if (part && last && !(n == g.n_blocks && pos <= c.limit && 1u + pos / 8u == c.limit / 8u)) bad = true;   // S_f = 1 + bits/8 (Terse.hpp:547)
         if (serial) {
-            if (__ballot(bad) && lane == 0u) atomicMax(&status[0], 5u);         // TRPX_ERR_CORRUPT: the serial walk's verdict
+            if (__ballot(bad) && lane == 0u) atomicMax(&status[0], kStatusCorrupt);         // TRPX_ERR_CORRUPT: the serial walk's verdict
         } else {
             if (__ballot(bad) && lane == 0u) s_bad = 1u;
             __syncthreads();

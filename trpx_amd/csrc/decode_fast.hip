@@ -105,9 +105,7 @@ __global__ __launch_bounds__(kThreads) void k_walk_groups(const uint8_t* __restr
     const uint32_t nb_last = (uint32_t)(g.n_values - (uint64_t)(g.n_blocks - 1) * kBlock);
     if (!bad) tile_off[i] = pos;
     for (uint32_t b = b0; b < b1 && !bad; ++b) {
-        const uint64_t abit = 8 * fo + pos, d = abit >> 5;
-        const uint64_t two = (uint64_t)(d < n_dw ? s32[d] : 0u) | ((uint64_t)(d + 1 < n_dw ? s32[d + 1] : 0u) << 32);
-        const uint32_t bits = (uint32_t)(two >> (abit & 31u));
+        const uint32_t bits = (uint32_t)stream_bits([&](uint64_t i) { return ld_stream_dw(s32, i, n_dw); }, 8 * fo + pos);
         uint32_t hl = 1;
         if (!(bits & 1u)) {                                  // Terse.hpp:361
             const ExplicitHeader h = parse_explicit_header(bits);
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void k_walk_groups(const uint8_t* __restr
         if (b1 < g.n_blocks) bad = ((pos & kStateOffMask) | ((uint64_t)w << 40)) != states[i + 1];   // lands in the next group's state
         else bad = 1 + pos / 8 != fe - fo;                                                           // S_f (Terse.hpp:547)
     }
-    if (bad) atomicMax(&status[0], 5u);                      // TRPX_ERR_CORRUPT
+    if (bad) atomicMax(&status[0], kStatusCorrupt);
 }
 
 hipError_t launch_index_group_states(const DecodeArgs& a, uint64_t* states, hipStream_t st) {

@@ -21,6 +21,7 @@
 // kernels of decode_fast.hip.
 #include "codec_common.hpp"
 #include "launchers.hpp"
+#include "lds_dma.hpp"
 #include "profile.hpp"
 #include "unpack_common.hpp"
 
@@ -64,15 +65,6 @@ struct FrameCfg {
     static constexpr int kOutDw = kWave * kBlock * (int)sizeof(T) / 4;   // an extraction wave's output row: 64 blocks of pixels
     static_assert(kChunkDw % (kWave * 4) == 0, "window = whole 1 KB pieces");
 };
-
-// One LDS-DMA piece: lane l's 16 bytes at `src` land at LDS byte address lds_base + 16 * l; no staging registers.  The
-// caller waits with s_waitcnt vmcnt(0) before it reads the bytes.  (An asm statement: with the builtin in the kernel's body
-// the host pass of hipcc 7.2 silently dropped the kernel's launch stubs.)
-__device__ __forceinline__ void lds_dma16(const uint32_t* src_uniform, uint32_t lane_byte_offset, uint32_t lds_base) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_byte_offset), "s"(src_uniform), "s"(lds_base) : "memory");
-}
 
 // MODE 0: decode.  MODE 1: the block widths are known (a decode index: widths[] and the bit offset of every 256th block,
 // launchers.hpp) and wave 0 turns them into the position entries with a prefix sum instead of walking the header chain --
@@ -165,7 +157,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
     walker_wave = __builtin_amdgcn_readfirstlane(walker_wave);
     const int wave = (hw_wave - walker_wave + kFrameWaves) % kFrameWaves;     // role: 0 walks, 1.. extract (wave-uniform scalar)
     if (s_err) {
-        if (threadIdx.x == 0) atomicMax(&status[0], 5u);
+        if (threadIdx.x == 0) atomicMax(&status[0], kStatusCorrupt);
         return;
     }
     const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(terse);
@@ -439,13 +431,8 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
                             // row, so that the next refill finds them in L2: 1.5 % faster right behind an encode, 16 % slower
                             // with the stream cache-resident: dropped.)
                         } else {
-                            for (uint32_t i = lane * 4; i < (uint32_t)kChunkDw; i += kWave * 4) {
-                                const uint64_t d = d0 + i;
-                                uint4 x;
-                                x.x = d < n_dw ? s32[d] : 0u; x.y = d + 1 < n_dw ? s32[d + 1] : 0u;
-                                x.z = d + 2 < n_dw ? s32[d + 2] : 0u; x.w = d + 3 < n_dw ? s32[d + 3] : 0u;
-                                *reinterpret_cast<uint4*>(&s_chunk[i]) = x;
-                            }
+                            for (uint32_t i = lane * 4; i < (uint32_t)kChunkDw; i += kWave * 4)
+                                *reinterpret_cast<uint4*>(&s_chunk[i]) = load_stream16_guarded(s32, d0 + i, n_dw);
                         }
                         if ((int32_t)b < fast_lim) continue;                          // go on with fast steps
                     }
@@ -688,19 +675,10 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
 #endif
                 }
                 if (blk + 1 == n_blocks && blk < step1 && !full) {                    // the frame's last, partial block
-                    const uint32_t mask = w >= 32u ? 0xFFFFFFFFu : ((1u << w) - 1u);
+                    const uint32_t mask = field_mask(w);
                     uint32_t p = q;
-                    for (uint32_t k = 0; k < nb_last; ++k) {
-                        uint32_t f = 0;
-                        if (w) {
-                            const uint64_t d = frame_dw + (p >> 5);
-                            const uint64_t two = (uint64_t)(d < n_dw ? s32[d] : 0u) | ((uint64_t)(d + 1 < n_dw ? s32[d + 1] : 0u) << 32);
-                            f = (uint32_t)(two >> (p & 31u)) & mask;
-                            if (PixelTraits<T>::is_signed) f = (uint32_t)((int32_t)(f << (32u - w)) >> (32u - w));
-                        }
-                        dst[k] = (T)f;
-                        p += w;
-                    }
+                    for (uint32_t k = 0; k < nb_last; ++k, p += w)
+                        dst[k] = (T)(w ? stream_field<T>([&](uint32_t i) { return ld_stream_dw(s32, frame_dw + i, n_dw); }, p, w, mask) : 0u);
                 }
             }
         }
@@ -735,7 +713,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
         asm volatile("" ::: "memory");                                     // (the LDS copies, not the registers they came from)
         uint32_t* const status_l = reinterpret_cast<uint32_t*>((uintptr_t)s_keep[0]);
         uint32_t* const defer_l = reinterpret_cast<uint32_t*>((uintptr_t)s_keep[1]);
-        if (s_err == 1u) atomicMax(&status_l[0], 5u);                      // TRPX_ERR_CORRUPT
+        if (s_err == 1u) atomicMax(&status_l[0], kStatusCorrupt);
         // listed: k_seg_listed + k_decode_frames_indexed do it (bit 31: so dense that a search for runs is a waste of time)
         if (s_err >= 2u) {
             defer_l[1u + atomicAdd(&defer_l[0], 1u)] = (uint32_t)s_keep[2] | (s_err == 3u ? 0x80000000u : 0u);

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(kWave) void k_locate_serial(const uint8_t* __restri
         fo += ok ? 1 + bits / 8 : 0;
         if (lane_id() == 0) offsets[f + 1] = fo;
     }
-    if (lane_id() == 0 && !ok) atomicMax(&status[0], 5u);                  // TRPX_ERR_CORRUPT
+    if (lane_id() == 0 && !ok) atomicMax(&status[0], kStatusCorrupt);
 }
 
 // 1. one wavefront per chunk: its chain from (first bit, 0) to the chunk's end, a checkpoint per window
@@ -376,14 +376,14 @@ __global__ __launch_bounds__(kWave) void k_loc_repair(const uint8_t* __restrict_
         prop = prop_next;
         fo = next;
     }
-    if (lane_id() == 0 && !ok) atomicMax(&status[0], 5u);                  // TRPX_ERR_CORRUPT
+    if (lane_id() == 0 && !ok) atomicMax(&status[0], kStatusCorrupt);
 }
 
 // trpx_decode(frame_offsets = NULL) on located offsets: the decode clears the status block, so the locate's verdict is re-read
 // from the offsets behind it -- every frame the serial walk accepts is at least one byte, and after a failure it adds none
 __global__ __launch_bounds__(kWave) void k_loc_status(const uint64_t* __restrict__ offsets, uint32_t n_frames,
                                                       uint32_t* __restrict__ status) {
-    if (threadIdx.x == 0 && offsets[n_frames] == offsets[n_frames - 1]) atomicMax(&status[0], 5u);   // TRPX_ERR_CORRUPT
+    if (threadIdx.x == 0 && offsets[n_frames] == offsets[n_frames - 1]) atomicMax(&status[0], kStatusCorrupt);
 }
 
 bool parallel_ok(const FrameGeom& g, uint64_t terse_bytes, uint64_t n_frames, uint32_t max_w) {

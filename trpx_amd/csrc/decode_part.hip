@@ -36,6 +36,7 @@
 // HBM traffic: the stream once more (walk only: no pixels), 0.2 of the algorithmic bytes of a u16 stack.
 #include "codec_common.hpp"
 #include "launchers.hpp"
+#include "lds_dma.hpp"
 #include <stdlib.h>
 
 namespace trpx {
@@ -139,18 +140,6 @@ size_t part_workspace_bytes(const FrameGeom& g, size_t n_frames) {
     return P > 1 ? part_ws_layout(n_frames, P).total : 0;
 }
 
-// One LDS-DMA piece (see decode_frame.hip): lane l's 16 bytes at `src` land at LDS byte address lds_base + 16 * l.
-__device__ __forceinline__ void part_lds_dma16(const uint32_t* src_uniform, uint32_t lane_byte_offset, uint32_t lds_base) {
-    uint32_t keep;
-    // (wave-uniform by construction; said again for the builds in which the compiler loses sight of it: "invalid operand")
-    const uint64_t a = (uint64_t)(uintptr_t)src_uniform;
-    const uint32_t* const src = reinterpret_cast<const uint32_t*>((uintptr_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a) |
-                                                                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32)));
-    const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_base);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_byte_offset), "s"(src), "s"(base) : "memory");
-}
-
 struct PartWin {                               // the frame's stream behind an LDS window
     const uint32_t* s32;
     uint64_t n_dw, frame_dw;                   // dwords of the stream; dword of the frame's first bit
@@ -175,17 +164,16 @@ __device__ __forceinline__ void part_fill(PartWin& W, uint32_t* __restrict__ s_c
     __builtin_amdgcn_wave_barrier();           // (every lane is through with the old window)
     if (W.base16 && (d0 & 3) == 0 && d0 + kPartChunkDw <= W.n_dw) {
 #pragma unroll
-        for (int it = 0; it < kPartChunkDw / (kWave * 4); ++it)
-            part_lds_dma16(W.s32 + d0 + it * kWave * 4, lane * 16u, (uint32_t)(uintptr_t)&s_chunk[it * kWave * 4]);
+        for (int it = 0; it < kPartChunkDw / (kWave * 4); ++it) {
+            // (wave-uniform by construction; said again for the builds in which the compiler loses sight of it: "invalid operand")
+            const uint64_t src = uniform64((uintptr_t)(W.s32 + d0 + it * kWave * 4));
+            const uint32_t lds_base = uniform32((uint32_t)(uintptr_t)&s_chunk[it * kWave * 4]);
+            lds_dma16(reinterpret_cast<const uint32_t*>((uintptr_t)src), lane * 16u, lds_base);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
-        for (uint32_t i = lane * 4; i < (uint32_t)kPartChunkDw; i += kWave * 4) {
-            const uint64_t d = d0 + i;
-            uint4 x;
-            x.x = d < W.n_dw ? W.s32[d] : 0u; x.y = d + 1 < W.n_dw ? W.s32[d + 1] : 0u;
-            x.z = d + 2 < W.n_dw ? W.s32[d + 2] : 0u; x.w = d + 3 < W.n_dw ? W.s32[d + 3] : 0u;
-            *reinterpret_cast<uint4*>(&s_chunk[i]) = x;
-        }
+        for (uint32_t i = lane * 4; i < (uint32_t)kPartChunkDw; i += kWave * 4)
+            *reinterpret_cast<uint4*>(&s_chunk[i]) = load_stream16_guarded(W.s32, d0 + i, W.n_dw);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -548,8 +536,7 @@ __device__ __forceinline__ void part_walk(PartWin& W, uint32_t* __restrict__ s_c
             uint32_t s_bad = 0, t_first, t_h, t_t, t_p, t_a, t_bits;
             // (the steps' state lives in scalar registers -- wave-uniform by construction, which the compiler cannot always see through
             // the callers' loops: "illegal VGPR to SGPR copy" in some builds, not in others)
-            auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-            pw = uni(pw); pw_end = uni(pw_end); pw_max = uni(pw_max); stride = uni(stride); b = uni(b); n_exp = uni(n_exp); w_prev = uni(w_prev);
+            pw = uniform32(pw); pw_end = uniform32(pw_end); pw_max = uniform32(pw_max); stride = uniform32(stride); b = uniform32(b); n_exp = uniform32(n_exp); w_prev = uniform32(w_prev);
 #define TRPX_PART_STEP_ASM(ST_STEP, ST_WIDTH)                                                                                  \
                 "s_cmp_lt_i32 %[pw], %[pwmax]\n\t"                                                                             \
                 "s_cbranch_scc0 9f\n"                                                                                          \
@@ -617,9 +604,8 @@ __device__ __forceinline__ void part_walk(PartWin& W, uint32_t* __restrict__ s_c
                 "9:\n"
             if constexpr (STORE) {
                 uint32_t t_eo, v_wv = w_prev;
-                const uint32_t capm1_u = uni(capm1), max_w_u = uni(max_w);
-                const uint64_t ent_a = (uint64_t)(uintptr_t)ent;
-                uint8_t* const ent_u = reinterpret_cast<uint8_t*>((uintptr_t)((uint64_t)uni((uint32_t)ent_a) | ((uint64_t)uni((uint32_t)(ent_a >> 32)) << 32)));
+                const uint32_t capm1_u = uniform32(capm1), max_w_u = uniform32(max_w);
+                uint8_t* const ent_u = reinterpret_cast<uint8_t*>((uintptr_t)uniform64((uintptr_t)ent));
                 asm volatile(TRPX_PART_STEP_ASM("v_add_u32 %[eo], %[b], %[lane]\n\t"
                                                 "v_min_u32 %[eo], %[capm1], %[eo]\n\t"
                                                 "global_store_byte %[eo], %[wv], %[ebase]\n\t",
@@ -630,7 +616,7 @@ __device__ __forceinline__ void part_walk(PartWin& W, uint32_t* __restrict__ s_c
                     : [lane] "v"(lane), [pwend] "s"(pw_end), [maxw] "s"(max_w_u), [capm1] "s"(capm1_u), [ebase] "s"(ent_u)
                     : "vcc", "scc", "memory", "v62", "v63");
             } else {
-                const uint32_t max_w_u = uni(max_w);
+                const uint32_t max_w_u = uniform32(max_w);
                 asm volatile(TRPX_PART_STEP_ASM("", "")
                     : [pw] "+s"(pw), [b] "+s"(b), [nexp] "+s"(n_exp), [w] "+s"(w_prev), [stride] "+s"(stride), [pwmax] "+s"(pw_max),
                       [ls] "+v"(v_ls), [bad] "+s"(s_bad), [first] "=&s"(t_first), [h] "=&s"(t_h), [t] "=&s"(t_t), [p] "=&v"(t_p),

@@ -21,7 +21,6 @@ namespace {
 
 constexpr int kRoiRows = kTileBlocks / kWave;               // blocks per lane
 
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint32_t pick(const uint32_t (&v)[kRoiRows], int r) {   // (the extraction loop stays rolled: one copy of the width dispatch)
     return r == 0 ? v[0] : r == 1 ? v[1] : r == 2 ? v[2] : v[3];
 }
@@ -44,7 +43,7 @@ __device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
     const uint32_t frame = uniform32(a.boxes[3 * box]), y0 = uniform32(a.boxes[3 * box + 1]), x0 = uniform32(a.boxes[3 * box + 2]);
     const uint32_t width = a.width;
     if (frame >= a.n_frames || (uint64_t)y0 + a.box_h > a.height || (uint64_t)x0 + a.box_w > width) {
-        if (k_unit == 0 && lane == 0) atomicMax(&a.status[0], kRoiInvalid);
+        if (k_unit == 0 && lane == 0) atomicMax(&a.status[0], kStatusInvalid);
         return;
     }
     const uint32_t y1 = y0 + a.box_h, x1 = x0 + a.box_w;
@@ -96,7 +95,7 @@ __device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
     const uint64_t end = t_off + total;
     bad = bad || (last ? 1 + end / 8 != fe - fo : end != t_next);   // S_f = 1 + bits / 8 (Terse.hpp:547)
     if (bad) {
-        if (lane == 0) atomicMax(&a.status[0], kRoiCorrupt);
+        if (lane == 0) atomicMax(&a.status[0], kStatusCorrupt);
         return;
     }
 

@@ -7,9 +7,6 @@
 
 namespace trpx {
 
-constexpr uint32_t kRoiCorrupt = 5;                  // TRPX_ERR_CORRUPT
-constexpr uint32_t kRoiInvalid = 1;                  // TRPX_ERR_INVALID_ARG: a box that leaves its stack
-
 // Work units (wavefronts) launched per box: the 256-block groups between a box's first and last pixel, at most -- from the
 // geometry alone, never from the boxes' contents; the surplus units of a box exit.
 uint32_t roi_units_per_box(const FrameGeom& g, uint32_t width, uint32_t box_h, uint32_t box_w);

@@ -200,7 +200,7 @@ __device__ __forceinline__ void seg_write(const SegCtx& c, uint32_t* __restrict_
     seg_walk<true>(c, win, 64u * k, part && !bad, last ? 0xFFFFFFFFu : end, last, pos, w, n, wf, tf, bad);
     if (part && !last && seg_pack(pos, w) != next_in) bad = true;                       // the chain the counts came from
     if (last && !(n == c.n_blocks && pos <= c.limit && 1u + pos / 8u == S_bytes)) bad = true;   // S_f = 1 + bits/8 (Terse.hpp:547)
-    if (__ballot(bad) && lane == 0u) atomicMax(&status[0], 5u);                         // TRPX_ERR_CORRUPT
+    if (__ballot(bad) && lane == 0u) atomicMax(&status[0], kStatusCorrupt);
 }
 
 struct SegWs {            // carve of seg_workspace_bytes()
@@ -234,7 +234,7 @@ __device__ __forceinline__ void seg_frame_walk(const uint8_t* __restrict__ terse
     const uint32_t lane = (uint32_t)lane_id();
     SegCtx c;
     if (!seg_ctx(c, terse, terse_bytes, frame_offsets, frame, g, max_w, kWave, status)) {
-        if (lane == 0) atomicMax(&status[0], 5u);
+        if (lane == 0) atomicMax(&status[0], kStatusCorrupt);
         return;
     }
     uint8_t* wf = widths + frame * g.n_blocks;
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(kWave * kSegWgWaves) void k_seg_groups(const uint8_
     const uint32_t k = (uint32_t)(wv % wpf) * (uint32_t)kWave + lane;                // this lane's group
     SegCtx c;
     if (!seg_ctx(c, terse, terse_bytes, frame_offsets, frame, g, max_w, kWave, status)) {
-        if (lane == 0) atomicMax(&status[0], 5u);
+        if (lane == 0) atomicMax(&status[0], kStatusCorrupt);
         return;
     }
     uint8_t* wf = widths + frame * g.n_blocks;
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(kWave * kSegWgWaves) void k_seg_groups(const uint8_
         if (b1 < g.n_blocks) bad = ((uint64_t)pos | ((uint64_t)w << 40)) != states[frame * g.n_tiles + k + 1u];   // lands in the next group's state
         else bad = !(n == g.n_blocks && pos <= c.limit && 1u + pos / 8u == c.limit / 8u);                          // S_f
     }
-    if (__ballot(bad) && lane == 0u) atomicMax(&status[0], 5u);                          // TRPX_ERR_CORRUPT
+    if (__ballot(bad) && lane == 0u) atomicMax(&status[0], kStatusCorrupt);
 }
 
 hipError_t launch_seg_groups(const DecodeArgs& a, uint32_t max_w, const uint64_t* states, hipStream_t st) {
@@ -411,7 +411,7 @@ __device__ __forceinline__ void seg_round_item(const uint8_t* __restrict__ terse
     const uint32_t k = item % K;
     SegCtx c;
     if (!seg_ctx(c, terse, terse_bytes, frame_offsets, frame, g, max_w, K * kWave, status)) {
-        if (threadIdx.x == 0 && k == 0) atomicMax(&status[0], 5u);
+        if (threadIdx.x == 0 && k == 0) atomicMax(&status[0], kStatusCorrupt);
         return;
     }
     if (first) seg_zero_widths(widths + frame * g.n_blocks, g.n_blocks, k, K);
@@ -640,7 +640,7 @@ __global__ __launch_bounds__(kWave * W) void k_seg_wg(const uint8_t* __restrict_
         const uint64_t frame = entry & 0x7FFFFFFFu;
         SegCtx c;
         if (!seg_ctx(c, terse, terse_bytes, frame_offsets, frame, g, max_w, G, status)) {
-            if (threadIdx.x == 0) atomicMax(&status[0], 5u);
+            if (threadIdx.x == 0) atomicMax(&status[0], kStatusCorrupt);
             continue;
         }
         uint8_t* wf = widths + frame * g.n_blocks;

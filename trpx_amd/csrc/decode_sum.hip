@@ -56,6 +56,7 @@ __device__ __forceinline__ int64_t acc_value(SumAcc<T> a) {
     else return (int64_t)a;
 }
 
+// The tile rule is unpack_tile.hpp's pieces; here: its steps spread over three frames.
 // what a frame's tile needs before its scan: the lanes' widths and the frame / tile positions
 template <typename T> struct SumPre {
     uint32_t w[sum_sub_tiles<T>()], wp[sum_sub_tiles<T>()];
@@ -74,17 +75,7 @@ __device__ __forceinline__ void sum_load_pre(SumPre<T>& p, const uint64_t* __res
                                              uint64_t frame, uint32_t t, const uint8_t* __restrict__ widths,
                                              const uint64_t* __restrict__ tile_off) {
     constexpr int kSub = sum_sub_tiles<T>();
-    const uint32_t b0 = t * kSub * kThreads;
-    const uint8_t* __restrict__ wf = widths + frame * g.n_blocks;
-#pragma unroll
-    for (int r = 0; r < kSub; ++r) {
-        const uint32_t b = b0 + r * kThreads + threadIdx.x;
-        p.w[r] = 0; p.wp[r] = 0;
-        if (b < g.n_blocks) {
-            p.w[r] = wf[b];
-            p.wp[r] = b ? wf[b - 1] : 0u;                   // significant_bits = 0 at frame start (Terse.hpp:359)
-        }
-    }
+    tile_load_widths<kSub>(p.w, p.wp, widths + frame * g.n_blocks, g, t);
     // vector loads (the index in a VGPR): a scalar load in flight shares lgkmcnt with LDS, and every LDS access of the frame
     // being extracted would wait for it
     uint64_t fi = frame, ti = frame * g.n_tiles + (uint64_t)t * kSub;   // (walk records every 256 blocks)
@@ -95,72 +86,26 @@ __device__ __forceinline__ void sum_load_pre(SumPre<T>& p, const uint64_t* __res
     p.t_off = tile_off[ti];
 }
 
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
-           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
-}
-
-// widths -> bit offsets inside the tile (unpack_tile's scan).  Returns false when the index does not fit the frame or the
-// LDS image (uniform over the workgroup: every lane sees the same positions and totals).
+// widths -> bit offsets inside the tile -> the window.  Returns false when the index does not fit the frame or the LDS image
+// (uniform over the workgroup: every lane sees the same positions and totals).
 template <typename T>
 __device__ __forceinline__ bool sum_scan(SumCur<T>& c, const SumPre<T>& p, const FrameGeom& g, uint32_t t, uint64_t terse_bytes,
                                          uint32_t* __restrict__ s_wtot) {
-    constexpr int kSub = sum_sub_tiles<T>();
-    const int lane = lane_id(), wave = wave_id();
-    const uint32_t b0 = t * kSub * kThreads;
-    uint32_t len[kSub], inc[kSub];
-#pragma unroll
-    for (int r = 0; r < kSub; ++r) {
-        const uint32_t b = b0 + r * kThreads + threadIdx.x;
-        c.w[r] = p.w[r];
-        c.nb[r] = 0; c.hl[r] = 0;
-        if (b < g.n_blocks) {
-            const uint64_t first = (uint64_t)b * kBlock;
-            c.nb[r] = first + kBlock <= g.n_values ? kBlock : (int)(g.n_values - first);
-            c.hl[r] = header_len(p.w[r], p.wp[r]);
-        }
-        len[r] = c.nb[r] ? c.hl[r] + (uint32_t)c.nb[r] * p.w[r] : 0u;
-        inc[r] = wave_inclusive_scan(len[r]);
-        if (lane == 63) s_wtot[r * 4 + wave] = inc[r];
-    }
-    __syncthreads();
-    {
-        const uint32_t tot = lane < kSub * 4 ? s_wtot[lane] : 0u;
-        const uint32_t incl = wave_inclusive_scan(tot);
-        const uint32_t excl = incl - tot;
-#pragma unroll
-        for (int r = 0; r < kSub; ++r) c.off[r] = (uint32_t)__shfl((int)excl, r * 4 + wave, 64) + inc[r] - len[r];
-        c.tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, kSub * 4 - 1);
-    }
-    const uint64_t fo = uniform64(p.fo), fe = uniform64(p.fe), t_off = uniform64(p.t_off);
-    if (fe > terse_bytes || fe <= fo || t_off > 8 * (fe - fo) || c.tile_bits > 8 * (fe - fo) - t_off)
-        return false;                                       // chain / index inconsistent with the frame
-    const uint64_t a0 = 8 * fo + t_off;
-    c.d_lo = (a0 >> 5) & ~3ull;                             // 16-byte aligned start (terse is 4-byte aligned: use dwords)
-    c.n_dw = (uint32_t)(((a0 + c.tile_bits + 31) >> 5) - c.d_lo) + 1;   // + 1: alignbit peeks one dword further
-    c.img_bit0 = (uint32_t)(a0 - 32 * c.d_lo);
+    tile_scan<sum_sub_tiles<T>()>(c.w, c.hl, c.off, c.nb, c.tile_bits,
+                                  [&](int r, uint32_t, uint32_t& w, uint32_t& w_prev) { w = p.w[r]; w_prev = p.wp[r]; }, g, t, s_wtot, lane_id(), wave_id());
+    uint64_t a0;
+    if (!tile_window(uniform64(p.fo), uniform64(p.fe), uniform64(p.t_off), c.tile_bits, terse_bytes, a0, c.d_lo, c.n_dw)) return false;
+    c.img_bit0 = tile_img_bit0(a0, c.d_lo);
     return c.n_dw <= (uint32_t)(sum_image_dwords<T>() - 8);   // (widths above the type's: more bits than the image holds)
 }
 
 template <typename T>
 __device__ __forceinline__ void sum_fetch(uint4 (&R)[sum_prefetch_loads<T>()], const SumCur<T>& c, const uint8_t* __restrict__ terse,
                                           uint64_t terse_bytes) {
-    const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(terse);
-    const uint64_t total_dw = (terse_bytes + 3) / 4;
-    const bool base16 = ((uintptr_t)terse & 15) == 0;
 #pragma unroll
     for (int k = 0; k < sum_prefetch_loads<T>(); ++k) {
         const uint32_t i = threadIdx.x * 4 + k * kThreads * 4;
-        if (i < c.n_dw) {
-            const uint64_t d = c.d_lo + i;
-            uint4 x;
-            if (base16 && d + 4 <= total_dw) x = *reinterpret_cast<const uint4*>(s32 + d);
-            else {
-                x.x = d < total_dw ? s32[d] : 0u; x.y = d + 1 < total_dw ? s32[d + 1] : 0u;
-                x.z = d + 2 < total_dw ? s32[d + 2] : 0u; x.w = d + 3 < total_dw ? s32[d + 3] : 0u;
-            }
-            R[k] = x;
-        }
+        if (i < c.n_dw) R[k] = tile_fetch16(c.d_lo, i, terse, terse_bytes);
     }
 }
 
@@ -177,39 +122,20 @@ __device__ __forceinline__ void sum_stage(uint32_t* __restrict__ s_image, const 
 template <typename T>
 __device__ __forceinline__ bool sum_extract(SumAcc<T> (&acc)[sum_sub_tiles<T>()][kBlock], const SumCur<T>& c,
                                             const uint32_t* __restrict__ s_image) {
-    constexpr int kSub = sum_sub_tiles<T>();
-    constexpr uint32_t bits = (uint32_t)PixelTraits<T>::bits;
     bool ok = true;
 #pragma unroll
-    for (int r = 0; r < kSub; ++r) {
+    for (int r = 0; r < sum_sub_tiles<T>(); ++r) {
         const uint32_t q = c.img_bit0 + c.off[r] + c.hl[r];  // first payload bit in the image
         uint32_t u[kBlock];
-#pragma unroll
-        for (int k = 0; k < kBlock; ++k) u[k] = 0u;         // w == 0 -> zeros (Terse.hpp:373-374)
-        if (c.nb[r] && c.w[r] > bits) ok = false;
-        uint64_t todo = __ballot(c.nb[r] == kBlock && c.w[r] != 0u);
-        while (todo) {
-            const int l0 = __builtin_ctzll(todo);
-            const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)c.w[r], l0);
-            const bool mine = c.nb[r] == kBlock && c.w[r] == w0;
-            uint32_t wd = w0 > bits ? bits : w0;
-            asm volatile("" : "+s"(wd));                    // (the dispatch stays scalar)
-            uint32_t qq = q;
-            asm volatile("" : "+v"(qq));                    // keep the specialised bodies out of LICM's reach
-            if (mine) UnpackDispatch<T, 1, PixelTraits<T>::bits>::run(s_image, qq, wd, u);
-            todo &= ~__ballot(mine);
-        }
-        if (c.nb[r] && c.nb[r] < kBlock) {                  // the frame's last, partial block: generic
-            const uint32_t ww = c.w[r] > bits ? 0u : c.w[r];
-            const uint32_t mask = ww >= 32u ? 0xFFFFFFFFu : ((1u << ww) - 1u);
+        if (c.nb[r] && tile_too_wide<T>(c.w[r])) ok = false;
+        tile_extract_full<T>(u, s_image, q, c.w[r], c.nb[r]);
+        if (c.nb[r] && c.nb[r] < kBlock) {              // the frame's last, partial block (unrolled: u stays in registers)
+            const uint32_t ww = tile_partial_width<T>(c.w[r]), mask = field_mask(ww);
             uint32_t p = q;
 #pragma unroll
             for (int k = 0; k < kBlock; ++k) {
                 if (k < c.nb[r] && ww) {
-                    const uint64_t two = (uint64_t)s_image[p >> 5] | ((uint64_t)s_image[(p >> 5) + 1] << 32);
-                    uint32_t f = (uint32_t)(two >> (p & 31u)) & mask;
-                    if (PixelTraits<T>::is_signed) f = (uint32_t)((int32_t)(f << (32u - ww)) >> (32u - ww));
-                    u[k] = f;
+                    u[k] = tile_partial_field<T>(s_image, p, ww, mask);
                     p += ww;
                 }
             }
@@ -269,10 +195,10 @@ __global__ __launch_bounds__(kThreads) void k_sum_tiles(SumArgs a) {
                 if (!bad) sum_fetch<T>(R, nxt, a.terse, a.terse_bytes);
                 if (f + 2 < f1) sum_load_pre(pn, a.frame_offsets, g, f + 2, t, a.widths, a.tile_off);
             }
-            if (!sum_extract<T>(acc, cur, s_image)) atomicMax(&a.status[0], (uint32_t)kSumCorrupt);
+            if (!sum_extract<T>(acc, cur, s_image)) atomicMax(&a.status[0], kStatusCorrupt);
             cur = nxt;
         }
-        if (bad && threadIdx.x == 0) atomicMax(&a.status[0], (uint32_t)kSumCorrupt);
+        if (bad && threadIdx.x == 0) atomicMax(&a.status[0], kStatusCorrupt);
 
         // ---- the sums leave once: per wavefront, its 64 blocks (768 values) as int64 through LDS, then consecutive elements
         // per lane (every store instruction writes whole lines)

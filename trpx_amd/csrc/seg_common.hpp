@@ -58,10 +58,7 @@ __device__ __forceinline__ uint32_t seg_len_bits(uint32_t limit, uint32_t G) {
 __device__ __forceinline__ seg_u4 seg_load16(const SegCtx& c, uint64_t d) {
     seg_u4 x;
     if (d + 4u <= c.n_dw) __builtin_memcpy(&x, c.s32 + d, 16);
-    else {
-        x.x = d < c.n_dw ? c.s32[d] : 0u; x.y = d + 1 < c.n_dw ? c.s32[d + 1] : 0u;
-        x.z = d + 2 < c.n_dw ? c.s32[d + 2] : 0u; x.w = d + 3 < c.n_dw ? c.s32[d + 3] : 0u;
-    }
+    else x = load_stream16_guarded<seg_u4>(c.s32, d, c.n_dw);
     return x;
 }
 

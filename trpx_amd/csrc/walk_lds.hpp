@@ -17,7 +17,7 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
     const uint32_t lane = (uint32_t)lane_id();
     const uint64_t fo = frame_offsets[frame], fe = frame_offsets[frame + 1];
     if (!(fe > fo && fe <= terse_bytes)) {
-        if (lane == 0) atomicMax(&status[0], 5u);
+        if (lane == 0) atomicMax(&status[0], kStatusCorrupt);
         return;
     }
     const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(terse);
@@ -102,13 +102,8 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
 #pragma unroll
                 for (int it = 0; it < kIt; ++it) *reinterpret_cast<uint4*>(&s_chunk[it * kWave * 4 + lane * 4]) = x[it];
             } else {
-                for (uint32_t i = lane * 4; i < (uint32_t)kWalkChunkDw; i += kWave * 4) {
-                    const uint64_t d = d0 + i;
-                    uint4 x;
-                    x.x = d < n_dw ? s32[d] : 0u; x.y = d + 1 < n_dw ? s32[d + 1] : 0u;
-                    x.z = d + 2 < n_dw ? s32[d + 2] : 0u; x.w = d + 3 < n_dw ? s32[d + 3] : 0u;
-                    *reinterpret_cast<uint4*>(&s_chunk[i]) = x;
-                }
+                for (uint32_t i = lane * 4; i < (uint32_t)kWalkChunkDw; i += kWave * 4)
+                    *reinterpret_cast<uint4*>(&s_chunk[i]) = load_stream16_guarded(s32, d0 + i, n_dw);
             }
 #ifdef TRPX_WALK_STATS
             __builtin_amdgcn_s_waitcnt(0); st_refill += __builtin_amdgcn_s_memtime() - rt0;
@@ -157,7 +152,7 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
         if (pos > limit + 64u * 400u) { bad = true; break; }               // ran away (corrupt stream): stop before wrapping
     }
     const bool ok = !bad && final_pos <= limit && 1 + (uint64_t)final_pos / 8 == fe - fo;   // S_f (Terse.hpp:547)
-    if (!ok && lane == 0) atomicMax(&status[0], 5u);                     // TRPX_ERR_CORRUPT
+    if (!ok && lane == 0) atomicMax(&status[0], kStatusCorrupt);
 #ifdef TRPX_WALK_STATS
     if (lane == 0) { atomicAdd(&status[2], st_steps); atomicAdd(&status[3], st_refills); atomicAdd(&status[4], (uint32_t)(st_refill >> 4)); atomicAdd(&status[5], (uint32_t)((__builtin_amdgcn_s_memtime() - st_t0) >> 4)); }
 #endif

@@ -5,17 +5,9 @@
 
 namespace trpx {
 
-// 64 bits of the stream starting at absolute bit `abit` of the (4-byte aligned) buffer.
-// Dwords with no valid byte read as zero (an aligned dword holding >= 1 valid byte never
-// crosses into an unmapped page).
-__device__ __forceinline__ uint32_t ld_stream_dw(const uint32_t* __restrict__ s32, uint64_t idx, uint64_t n_dw) {
-    return idx < n_dw ? s32[idx] : 0u;
-}
+// 32 bits of the stream starting at absolute bit `abit` of the (4-byte aligned) buffer (ld_stream_dw: codec_common.hpp).
 __device__ __forceinline__ uint32_t peek32(const uint32_t* __restrict__ s32, uint64_t n_dw, uint64_t abit) {
-    const uint64_t di = abit >> 5;
-    const uint32_t sh = (uint32_t)(abit & 31);
-    const uint64_t x = (uint64_t)ld_stream_dw(s32, di, n_dw) | ((uint64_t)ld_stream_dw(s32, di + 1, n_dw) << 32);
-    return (uint32_t)(x >> sh);
+    return (uint32_t)stream_bits([&](uint64_t i) { return ld_stream_dw(s32, i, n_dw); }, abit);
 }
 
 // Walk one frame with one wavefront (kStore = false: count only, widths_f / tile_off_f are not touched).  Returns the frame's total bit count, or ~0ull if the
