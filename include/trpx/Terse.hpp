@@ -247,6 +247,37 @@ public:
         if constexpr (!std::is_pointer_v<Iterator>) std::copy(tmp.begin(), tmp.end(), out);
     }
 
+    /// The pixels with value >= threshold of every frame, in CSR form, in two device calls (sizes, then events) without
+    /// expanding the frames (trpx_decode_sparse_host): row_offsets[f] = events in the frames < f (number_of_frames() + 1
+    /// entries), positions[i] = the pixel index of event i inside its frame, values[i] = its value; by frame, then by pixel.
+    /// T is the narrowest integer type that holds the object's values, as for prolix_roi.
+    template <typename T>
+    void prolix_sparse(std::int64_t threshold, std::vector<std::uint64_t>& row_offsets, std::vector<std::uint32_t>& positions,
+                       std::vector<T>& values) {
+        static_assert(std::is_integral_v<T> && sizeof(T) <= 4, "prolix_sparse: an integer type of at most 32 bits");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_sparse: values of more than 32 bits are not supported");
+        const unsigned bits = d_prolix_bits <= 8 ? 8 : d_prolix_bits <= 16 ? 16 : 32;
+        if (8 * sizeof(T) != bits || std::is_signed_v<T> != d_signed)
+            throw std::invalid_argument("prolix_sparse: the value type must be the narrowest integer type that holds the values");
+        row_offsets.assign(d_frame_sizes.size() + 1, 0);
+        positions.clear();
+        values.clear();
+        if (d_frame_sizes.empty()) return;
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        std::size_t found = 0;
+        int rc = trpx_decode_sparse_host(detail::dtype_of<T>(), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                         d_frame_sizes.size(), d_block, threshold, row_offsets.data(), nullptr, nullptr, 0, &found, -1);
+        if (rc != TRPX_ERR_CAPACITY) detail::check(rc, "Terse::prolix_sparse");   // (CAPACITY: there are events, `found` of them)
+        if (found == 0) return;
+        positions.resize(found);
+        values.resize(found);
+        detail::check(trpx_decode_sparse_host(detail::dtype_of<T>(), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                              d_frame_sizes.size(), d_block, threshold, row_offsets.data(), positions.data(), values.data(),
+                                              found, &found, -1), "Terse::prolix_sparse");
+    }
+
     std::size_t size() const { return d_size; }                                   // Terse.hpp:396
     std::size_t number_of_frames() const { return d_frame_sizes.size(); }         // :403
     std::vector<std::size_t> const& dim() const { return d_dim; }                 // :410

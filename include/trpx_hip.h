@@ -307,6 +307,54 @@ int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
                          unsigned box_h, unsigned box_w, void* pixels_out, int device);
 
 /*
+ * Threshold decode: the pixels at or above a threshold, in CSR form, straight from the stream and its decode index, without
+ * expanding the frames.  A block's width bounds its values: the payload of a block too narrow to hold the threshold is never read.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32; `values` has the same type
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_sum: index given; offsets only -- the index is built in the workspace by
+ *                  trpx_build_index's walk; offsets NULL -- the frames are located in the workspace first.  workspace: DEVICE,
+ *                  8-byte aligned, ALWAYS needed (the counts live there): trpx_decode_sparse_workspace_bytes() is the need with
+ *                  offsets and index both NULL; with offsets or index given less is used, and the call checks against what its
+ *                  own form needs.  The size is arithmetic on terse_bytes, n_frames and the number of 256-block groups
+ *   threshold      pixel p of frame f is an event iff (int64) value >= threshold, a mathematical comparison whatever the type.
+ *                  At or below the type's minimum every pixel is an event, above its maximum none is; both are legal.  The
+ *                  twelve zeros of a width-0 block are events, with value 0, when threshold <= 0
+ *   row_offsets    DEVICE uint64_t[n_frames + 1], 8-byte aligned: [f] = events in the frames < f, [n_frames] = the total
+ *   positions      DEVICE uint32_t[capacity]: the pixel index of event i inside its frame
+ *   values         DEVICE T[capacity], aligned to T: its value.  Events come by frame and, inside a frame, by ascending pixel
+ *                  index -- frame by frame what np.flatnonzero(px[f] >= threshold) and px[f][...] give -- bit-identical across
+ *                  runs, input forms and launch shapes
+ *   capacity       elements of positions / values.  A total above it: status word 0 = TRPX_ERR_CAPACITY, row_offsets is still
+ *                  complete and valid, positions / values [0 .. capacity) are unspecified and nothing at or behind capacity is
+ *                  touched (trpx_encode's convention); capacity == total is success.  A sizes-only query passes positions =
+ *                  values = NULL with capacity 0 (one NULL without the other, or NULL with capacity > 0: TRPX_ERR_INVALID_ARG)
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT when a 256-block group does not end where the
+ *                  next group's offset (the last group: the frame's size) says, a block is wider than dtype allows, a frame lies
+ *                  outside the stream or the index does not fit the offsets: EVERY group of EVERY frame is walked, so the whole
+ *                  stack is validated (unlike trpx_decode_roi).  The outputs are then unspecified.  TRPX_ERR_CORRUPT wins over
+ *                  TRPX_ERR_CAPACITY when both apply
+ * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)) is read, nothing outside
+ * row_offsets[0 .. n_frames], positions[0 .. capacity) and values[0 .. capacity) is written, whatever the status.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits (which
+ * is also what makes positions fit 32 bits); TRPX_ERR_INVALID_ARG for an unknown dtype, bad sizes, null or misaligned pointers,
+ * the NULL / capacity rule above, an index without offsets, a NULL workspace; TRPX_ERR_CAPACITY for a workspace that is too small.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the
+ * host from n_frames and n_values alone, never from the data or the threshold.
+ * trpx_decode_sparse_host: host terse / frame_offsets (or NULL) / outputs; checks its arguments before a device is looked for,
+ * stages, calls trpx_decode_sparse, synchronises and sets *n_found to the total.  With a capacity that is too small *n_found
+ * and row_offsets are still valid and it returns TRPX_ERR_CAPACITY: a caller sizes a second call from them.
+ */
+size_t trpx_decode_sparse_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block);
+int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                       size_t n_values, size_t n_frames, unsigned block, int64_t threshold, uint64_t* row_offsets,
+                       uint32_t* positions, void* values, size_t capacity, uint32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                            size_t n_frames, unsigned block, int64_t threshold, uint64_t* row_offsets, uint32_t* positions,
+                            void* values, size_t capacity, size_t* n_found, int device);
+
+/*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
  * box regenerates exactly the pixels the oracle anchors were computed on.  dtype U16 or I32.
  */

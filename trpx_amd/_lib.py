@@ -31,7 +31,7 @@ class trpx_header(C.Structure):
 
 
 # every symbol include/trpx_hip.h declares: (restype, argtypes)
-_P, _SZ, _U, _I, _U64 = C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_uint64
+_P, _SZ, _U, _I, _U64, _I64 = C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_uint64, C.c_int64
 SYMBOLS = {
     "trpx_abi_version": (_I, []),
     "trpx_last_error_string": (C.c_char_p, []),
@@ -61,6 +61,9 @@ SYMBOLS = {
     "trpx_decode_roi_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
     "trpx_decode_roi": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _SZ, _P, _SZ, _U, _U, _P, _P, _P, _SZ, _P]),
     "trpx_decode_roi_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _SZ, _P, _SZ, _U, _U, _P, _I]),
+    "trpx_decode_sparse_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
+    "trpx_decode_sparse": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _I64, _P, _P, _P, _SZ, _P, _P, _SZ, _P]),
+    "trpx_decode_sparse_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _I64, _P, _P, _P, _SZ, C.POINTER(_SZ), _I]),
     "trpx_gather_workspace_bytes": (_SZ, [_SZ, _I]),
     "trpx_gather_frame_offsets": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P, _SZ, _P]),
     "trpx_encode_sharded_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _I]),

@@ -303,3 +303,62 @@ def decode_roi(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
                                     boxes.data_ptr(), n_boxes, box_h, box_w, out.data_ptr(), status.data_ptr(), ws_ptr, ws_bytes,
                                     _stream_ptr(terse)))
     return out, status
+
+
+def decode_sparse_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, block: int = BLOCK) -> int:
+    return lib().trpx_decode_sparse_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block)
+
+
+def decode_sparse(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, threshold: int,
+                  index: torch.Tensor | None = None, capacity: int | None = None, row_offsets: torch.Tensor | None = None,
+                  positions: torch.Tensor | None = None, values: torch.Tensor | None = None, workspace: Workspace | None = None,
+                  status: torch.Tensor | None = None, block: int = BLOCK):
+    """The pixels with value >= ``threshold`` of a stack resident on the GPU (trpx_decode_sparse), in CSR form, without decoding
+    its frames to memory.
+
+    ``dtype`` is the stream's pixel type and that of the values.  Returns (row_offsets int64 [n_frames + 1], positions uint32,
+    values, status): event i of frame f, row_offsets[f] <= i < row_offsets[f + 1], is pixel positions[i] of that frame and has
+    value values[i]; events come by frame and, inside a frame, by ascending pixel index.
+
+    With ``capacity`` given: ONE call, asynchronous on the current stream like ``decode``, into tensors of ``capacity`` elements
+    (``positions`` / ``values`` if given, which must hold that many); status[0] is 3 when there are more events than that
+    (row_offsets is still complete) and 5 for a corrupt stream or index -- the whole stack is validated.  With
+    ``capacity=None`` the call SYNCHRONISES: a sizes-only call, one read of the total, exact-size tensors of its own (``positions`` /
+    ``values`` may not be given then: ValueError), a second call.
+    ``frame_offsets = None``: the frames are located first; ``index = None``: the decode index is built on the way (both in
+    ``workspace``)."""
+    tdt = torch_dtype(dtype)
+    code = dtype_code(tdt)
+    dev = terse.device
+    if row_offsets is None:
+        row_offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    ws = (workspace or Workspace(dev)).get(lib().trpx_decode_sparse_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+
+    def call(pos, val, cap):
+        with torch.cuda.device(dev):
+            check(lib().trpx_decode_sparse(code, terse.data_ptr(), terse.numel(),
+                                           frame_offsets.data_ptr() if frame_offsets is not None else None,
+                                           index.data_ptr() if index is not None else None, n_values, n_frames, block, int(threshold),
+                                           row_offsets.data_ptr(), pos.data_ptr() if pos is not None else None,
+                                           val.data_ptr() if val is not None else None, cap, status.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), _stream_ptr(terse)))
+
+    if capacity is None:
+        if positions is not None or values is not None:
+            raise ValueError("decode_sparse: positions / values need a capacity (capacity=None sizes and allocates them itself)")
+        call(None, None, 0)
+        capacity = int(row_offsets[-1].item())               # (synchronises)
+        if int(status[0].item()) not in (_lib.OK, _lib.ERR_CAPACITY):
+            empty = torch.empty(0, dtype=torch.uint32, device=dev), torch.empty(0, dtype=tdt, device=dev)
+            return row_offsets, empty[0], empty[1], status
+    if positions is None:
+        positions = torch.empty(capacity, dtype=torch.uint32, device=dev)
+    if values is None:
+        values = torch.empty(capacity, dtype=tdt, device=dev)
+    if positions.dtype not in (torch.uint32, torch.int32) or values.dtype != tdt or positions.numel() < capacity or values.numel() < capacity \
+            or not positions.is_contiguous() or not values.is_contiguous() or positions.device != dev or values.device != dev:
+        raise ValueError(f"decode_sparse: positions (uint32) and values ({tdt}) must be contiguous tensors of >= {capacity} elements on {dev}")
+    call(positions, values, capacity)
+    return row_offsets, positions, values, status

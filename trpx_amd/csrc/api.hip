@@ -14,6 +14,7 @@
 
 #include "../../include/trpx_hip.h"
 #include "decode_roi.hpp"
+#include "decode_sparse.hpp"
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -836,6 +837,87 @@ int trpx_decode_roi(int dtype, const uint8_t* terse, size_t terse_bytes, const u
     return TRPX_OK;
 }
 
+// ---- threshold decode (decode_sparse.hip) --------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// trpx_decode_sparse's workspace: what the missing inputs need (index_ws), then per (frame, group) [counts u32] [flags 4 x u64]
+// [base u32] and per frame [total u32]
+struct SparseWs { IndexWs front; size_t counts, flags, base, frame_total, total; };
+SparseWs sparse_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, bool have_offsets, bool have_index) {
+    SparseWs w;
+    const size_t groups = n_frames * (size_t)g.n_tiles;
+    w.front = index_ws(dtype, g, terse_bytes, n_frames, have_offsets, have_index);
+    w.counts = w.front.total;
+    w.flags = trpx::align_up(w.counts + 4 * groups, 8);
+    w.base = w.flags + 32 * groups;
+    w.frame_total = w.base + 4 * groups;
+    w.total = trpx::align_up(w.frame_total + 4 * n_frames, 8);
+    return w;
+}
+// the rule the device-pointer and the host-pointer entry point share: both outputs, or neither and no capacity (sizes only)
+int sparse_outputs(const char* fn, const void* positions, const void* values, size_t capacity) {
+    if ((positions == nullptr) != (values == nullptr)) return fail(TRPX_ERR_INVALID_ARG, "%s: positions and values go together", fn);
+    if (!positions && capacity) return fail(TRPX_ERR_INVALID_ARG, "%s: capacity %zu without outputs", fn, capacity);
+    return TRPX_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t trpx_decode_sparse_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
+        return 0;
+    return sparse_ws(dtype, g, terse_bytes, n_frames, false, false).total;
+}
+
+int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                       size_t n_values, size_t n_frames, unsigned block, int64_t threshold, uint64_t* row_offsets,
+                       uint32_t* positions, void* values, size_t capacity, uint32_t* status, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_sparse", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {row_offsets, 8}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
+                                   {workspace, 8, false}, {positions, 4, false}, {values, es, false}}, &g))
+        return rc;
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse: frames of >= 2^32 bits");
+    if (n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (const int rc = sparse_outputs("trpx_decode_sparse", positions, values, capacity)) return rc;
+    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse: an index needs its frame offsets");
+    if (!workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse: null workspace (the counts live there)");
+    const SparseWs w = sparse_ws(dtype, g, terse_bytes, n_frames, frame_offsets != nullptr, index != nullptr);
+    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sparse: workspace %zu < %zu", workspace_bytes, w.total);
+
+    trpx::fused_ws_forget(workspace, workspace_bytes);
+    char* ws = static_cast<char*>(workspace);
+    bool clear = true;
+    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
+                                          w.front, stream, &clear))
+        return rc;
+    const DecLayout il = idx_layout(g, n_frames, es);
+    trpx::SparseArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.geom = g;
+    a.n_frames = n_frames;
+    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
+    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    a.threshold = threshold;
+    a.min_width = trpx::sparse_min_width(threshold, trpx_dtype_is_signed(dtype) != 0);
+    a.counts = reinterpret_cast<uint32_t*>(ws + w.counts);
+    a.flags = reinterpret_cast<uint64_t*>(ws + w.flags);
+    a.base = reinterpret_cast<uint32_t*>(ws + w.base);
+    a.frame_total = reinterpret_cast<uint32_t*>(ws + w.frame_total);
+    a.row_offsets = row_offsets;
+    a.positions = positions;
+    a.values = values;
+    a.capacity = capacity;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_sparse(dtype, a, clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
 // ---- host-pointer convenience wrappers ---------------------------------------------------
 // The callers of the reference's API work frame by frame from host memory (src/terse.cpp:63-69 pushes one image at a
 // time, src/prolix.cpp:69-92 expands one frame at a time): a device allocation per call would cost more than the
@@ -1118,6 +1200,50 @@ int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
                          n_boxes, box_h, box_w, d_out, d_st, d_ws, ws_bytes, hs);
     if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_roi_host", st))) return rc;
     HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                            size_t n_frames, unsigned block, int64_t threshold, uint64_t* row_offsets, uint32_t* positions,
+                            void* values, size_t capacity, size_t* n_found, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (!terse || !row_offsets || !n_found || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad argument");
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse_host: block=%u dtype=%d", block, dtype);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad sizes");
+    const size_t ws_bytes = trpx_decode_sparse_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad dtype/sizes");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse_host: frames of >= 2^32 bits");
+    if (const int rc = sparse_outputs("trpx_decode_sparse_host", positions, values, capacity)) return rc;
+    const size_t es = trpx_dtype_size(dtype);
+    if ((unsigned __int128)capacity * (4 + es) >= ((unsigned __int128)1 << 62)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad capacity %zu", capacity);
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_sparse_host", device, &hs)) return rc;
+    // the outputs in one device block: [row_offsets] [positions] [values]
+    const size_t pos_at = trpx::align_up(8 * (n_frames + 1), 16), val_at = trpx::align_up(pos_at + 4 * capacity, 16);
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
+    void *d_out = nullptr, *d_ws = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
+    HIP_TRY(arena().get(Arena::kPixels, val_at + es * capacity, &d_out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
+    char* o = static_cast<char*>(d_out);
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_sparse(dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, threshold, reinterpret_cast<uint64_t*>(o),
+                            positions ? reinterpret_cast<uint32_t*>(o + pos_at) : nullptr, positions ? o + val_at : nullptr, capacity, d_st,
+                            d_ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d_st, st))) return rc;
+    if (st[0] && st[0] != TRPX_ERR_CAPACITY) return status_result("trpx_decode_sparse_host", st);
+    HIP_TRY(copy_sync(hs, row_offsets, o, 8 * (n_frames + 1), hipMemcpyDeviceToHost));   // (valid when the capacity is too small, too)
+    const size_t total = (size_t)row_offsets[n_frames];
+    *n_found = total;
+    if (st[0]) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sparse_host: %zu events, capacity %zu", total, capacity);
+    if (total) {
+        HIP_TRY(copy_sync(hs, positions, o + pos_at, 4 * total, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(hs, values, o + val_at, es * total, hipMemcpyDeviceToHost));
+    }
     return TRPX_OK;
 }
 

@@ -143,6 +143,18 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
     return v;
 }
 
+__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
+// The same for 64-bit values (shuffles: the scans over frames and groups, off the hot paths).
+__device__ __forceinline__ uint64_t wave_inclusive_scan64(uint64_t v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, off, 64);
+        uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), off, 64);
+        if (lane_id() >= off) v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
 // Maximum over the 64 lanes (same DPP ladder as the scan; every lane gets the result).
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
     auto step = [](uint32_t x, uint32_t y) { return x > y ? x : y; };
@@ -155,7 +167,6 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 // wave index as a SCALAR (readfirstlane): branches on it are uniform, so whatever a single wave computes from
 // wave-uniform values stays in SGPRs / on the scalar unit instead of being treated as divergent per-lane data
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }

@@ -13,29 +13,14 @@
 // box's blocks, the boxes' pixels.
 #include "codec_common.hpp"
 #include "decode_roi.hpp"
-#include "unpack_common.hpp"
+#include "group_front.hpp"
 
 namespace trpx {
 
 namespace {
 
-constexpr int kRoiRows = kTileBlocks / kWave;               // blocks per lane
-
-__device__ __forceinline__ uint32_t pick(const uint32_t (&v)[kRoiRows], int r) {   // (the extraction loop stays rolled: one copy of the width dispatch)
-    return r == 0 ? v[0] : r == 1 ? v[1] : r == 2 ? v[2] : v[3];
-}
-
-template <typename T>
-__device__ __forceinline__ T packed_value(const uint32_t (&o)[PackedDwords<T>::n], int k) {
-    if constexpr (sizeof(T) == 4) return (T)o[k];
-    else if constexpr (sizeof(T) == 2) return (T)(o[k >> 1] >> (16 * (k & 1)));
-    else return (T)(o[k >> 2] >> (8 * (k & 3)));
-}
-
 template <typename T>
 __device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
-    constexpr uint32_t bits = (uint32_t)PixelTraits<T>::bits;
-    constexpr int kRaw = 4 * RawQuads<T>::n;
     const FrameGeom& g = a.geom;
     const uint32_t lane = (uint32_t)lane_id();
     const uint64_t box = unit / a.units_per_box;
@@ -59,55 +44,20 @@ __device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
     }
     if (ya >= y1 || ya * width + x0 >= p_hi) return;
 
-    // ---- widths -> bit offsets inside the group
-    const uint64_t ti = (uint64_t)frame * g.n_tiles + grp;
-    const bool last = grp + 1 == g.n_tiles;
-    const uint64_t fo = a.frame_offsets[frame], fe = a.frame_offsets[frame + 1];
-    const uint64_t t_off = a.tile_off[ti], t_next = last ? 0 : a.tile_off[ti + 1];
-    const uint8_t* __restrict__ wf = a.widths + (uint64_t)frame * g.n_blocks;
-    uint32_t w[kRoiRows], off[kRoiRows], nb[kRoiRows];      // off: the block's first PAYLOAD bit, group-relative
-    uint32_t total = 0;
-    bool wide = false;
-#pragma unroll
-    for (int r = 0; r < kRoiRows; ++r) {
-        const uint32_t b = grp * kTileBlocks + r * kWave + lane;
-        uint32_t wp = 0;
-        w[r] = 0; nb[r] = 0;
-        if (b < g.n_blocks) {
-            w[r] = wf[b];
-            if (lane == 0) wp = b ? wf[b - 1] : 0u;         // significant_bits = 0 at frame start (Terse.hpp:359)
-            const uint64_t first = (uint64_t)b * kBlock;
-            nb[r] = first + kBlock <= g.n_values ? kBlock : (uint32_t)(g.n_values - first);
-        }
-        const uint32_t left = (uint32_t)__shfl_up((int)w[r], 1, kWave);   // the width in front: the neighbour lane's, one more byte for lane 0
-        if (lane != 0) wp = left;
-        const uint32_t hl = header_len(w[r], wp);
-        const uint32_t len = nb[r] ? hl + nb[r] * w[r] : 0u;
-        const uint32_t inc = wave_inclusive_scan(len);
-        off[r] = total + inc - len + hl;
-        total += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        wide = wide || (nb[r] && w[r] > bits);
-    }
-    // ---- the group against the frame and the next group
-    const uint64_t frame_bits = 8 * (fe - fo);
-    bool bad = __ballot(wide) != 0ull || fe > a.terse_bytes || fe <= fo || frame_bits >= 0xFFFF0000ull ||
-               t_off > frame_bits || total > frame_bits - t_off;
-    const uint64_t end = t_off + total;
-    bad = bad || (last ? 1 + end / 8 != fe - fo : end != t_next);   // S_f = 1 + bits / 8 (Terse.hpp:547)
-    if (bad) {
+    // ---- widths -> bit offsets inside the group -> the group against the frame and the next group (group_front.hpp)
+    uint32_t w[kGroupRows], off[kGroupRows], nb[kGroupRows];   // off: the block's first PAYLOAD bit, group-relative
+    uint64_t fo, t_off;
+    if (!group_front<T>(w, off, nb, fo, t_off, a.widths, a.tile_off, a.frame_offsets, g, a.terse_bytes, frame, grp, lane)) {
         if (lane == 0) atomicMax(&a.status[0], kStatusCorrupt);
         return;
     }
 
     // ---- the blocks that hold box pixels: payload dwords -> registers -> fields -> the box
-    const uint64_t d_frame = fo >> 2;                       // (terse is 4-byte aligned: dwords)
-    const uint32_t* __restrict__ s32 = reinterpret_cast<const uint32_t*>(a.terse) + d_frame;
-    const uint64_t avail_dw = (a.terse_bytes + 3) / 4 - d_frame;
-    const uint32_t bit0 = 8u * (uint32_t)(fo & 3u) + (uint32_t)t_off;
+    const GroupStream gs = group_stream(a.terse, a.terse_bytes, fo, t_off);
     T* __restrict__ out = static_cast<T*>(a.out) + box * a.box_h * a.box_w;
 #pragma unroll 1
-    for (int r = 0; r < kRoiRows; ++r) {
-        const uint32_t wr = pick(w, r), nr = pick(nb, r);
+    for (int r = 0; r < kGroupRows; ++r) {
+        const uint32_t wr = group_pick(w, r), nr = group_pick(nb, r);
         const uint32_t p0 = (grp * kTileBlocks + r * kWave + lane) * kBlock;
         const uint32_t by = p0 / width, bx = p0 - by * width;
         uint32_t mask = 0;                                  // the block's values inside the box
@@ -120,23 +70,8 @@ __device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
             }
         }
         if (__ballot(mask != 0u) == 0ull) continue;
-        const uint32_t q = bit0 + pick(off, r), d = q >> 5, s = q & 31u;
-        const uint32_t nd = (s + nr * wr + 31u) >> 5;       // dwords that hold the block's fields
-        uint32_t raw[kRaw];
-#pragma unroll
-        for (int j = 0; j < kRaw; ++j) raw[j] = mask && (uint32_t)j < nd && (uint64_t)d + j < avail_dw ? s32[d + j] : 0u;
         uint32_t o[PackedDwords<T>::n];
-#pragma unroll
-        for (int j = 0; j < PackedDwords<T>::n; ++j) o[j] = 0u;   // w == 0 -> zeros (Terse.hpp:373-374)
-        uint64_t todo = __ballot(mask != 0u && wr != 0u);
-        while (todo) {
-            const int l0 = __builtin_ctzll(todo);
-            uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)wr, l0);
-            const bool mine = mask != 0u && wr == w0;
-            asm volatile("" : "+s"(w0));                    // (the dispatch stays scalar)
-            if (mine) UnpackRegsDispatch<T, 1, PixelTraits<T>::bits>::run(raw, s, w0, o);
-            todo &= ~__ballot(mine);
-        }
+        group_extract<T>(o, gs, mask != 0u, wr, nr, group_pick(off, r));
         {
             uint32_t x = bx, y = by;
 #pragma unroll

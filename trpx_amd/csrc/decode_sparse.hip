@@ -1,0 +1,303 @@
+// Threshold decode (trpx_decode_sparse): a stack with its decode index -> the pixels at or above a threshold as (row offsets,
+// positions, values), without expanding the frames.  The order of the output is fixed (by frame, then by pixel), so the
+// shape is count -> scan -> write.  The two kernels that read the stream give a wavefront a RUN of kRun consecutive 256-block
+// groups of one frame (group_front.hpp: four blocks per lane): what belongs to the run is loaded once and coalesced (the frame's
+// bytes, the groups' offsets, counts, bases and flag words, one per lane), the next group's widths are in flight while a group is
+// scanned and extracted, and the run's counts and flag words leave in one store each.
+//
+//   k_sparse_count       every group of every frame: widths -> header_len + 12 * w -> wave scans from the group's offset -> the
+//                        group validated (so the whole stack is) -> the CANDIDATE blocks, those wide enough to hold an event (a
+//                        block's width bounds its values), compacted into consecutive lanes through a list in LDS -> per 64
+//                        candidates one round: the payload dwords straight from the stream into registers, the register
+//                        extraction, the compare on the extracted values -> per group the number of events and a 256-bit set,
+//                        bit i = "candidate i (in block order) has events".  A group that fails validation sets CORRUPT and
+//                        counts nothing.
+//   k_sparse_frame_scan  per frame (one wavefront): exclusive scan of its groups' counts, the frame's total
+//   k_sparse_stack_scan  one workgroup: exclusive scan of the frames' totals -> row_offsets; CAPACITY when the total exceeds it
+//   k_sparse_write       groups with events only: the front end again, the candidates that have events compacted and extracted
+//                        again, each event stored at row_offsets[frame] + base[group] + its rank in the group (block order,
+//                        then k), under index < capacity.
+// HBM traffic: the widths (and 16 bytes per group) twice at most, the payload of the candidate blocks, 40 bytes per group of
+// counts / flags / bases, the events.  Nothing depends on the order in which wavefronts run: the output is bit-identical across runs.
+#include "codec_common.hpp"
+#include "decode_sparse.hpp"
+#include "group_front.hpp"
+
+namespace trpx {
+
+namespace {
+
+constexpr int kWavesPerWg = kThreads / kWave;
+constexpr uint32_t kRun = 8;                                // consecutive groups of one frame per wavefront
+static_assert(kRun * kGroupRows <= kWave && kRun < kWave, "a run's offsets and flag words: one per lane");
+
+// the lane's block's values (first nr of the 12 in o) at or above the threshold: the comparison is on the extracted value
+template <typename T>
+__device__ __forceinline__ uint32_t event_mask(const uint32_t (&o)[PackedDwords<T>::n], uint32_t nr, int64_t threshold) {
+    uint32_t mask = 0;
+#pragma unroll
+    for (int k = 0; k < kBlock; ++k)
+        if ((uint32_t)k < nr && (int64_t)packed_value<T>(o, k) >= threshold) mask |= 1u << k;
+    return mask;
+}
+
+__device__ __forceinline__ uint64_t lane_value64(uint64_t v, uint32_t src) {
+    return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src, kWave) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src, kWave) << 32);
+}
+// lanes below this one in a ballot
+__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+// The wavefront's list of chosen blocks in LDS (kTileBlocks entries, block order): written by the lanes that own the blocks,
+// read 64 at a time by consecutive lanes.  An entry: payload bit in the group (17 bits: a group has < 2^17 bits), width (6),
+// block in the group (8).
+__device__ __forceinline__ uint32_t list_entry(uint32_t off, uint32_t w, uint32_t block) { return off | (w << 17) | (block << 23); }
+__device__ __forceinline__ void list_sync() {               // the wavefront's LDS writes are seen by its other lanes' reads behind this
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// entry 64 * c + lane of a list of n: the lane's block, extracted; returns its event mask (0 behind the list's end)
+template <typename T>
+__device__ __forceinline__ uint32_t list_round(uint32_t (&o)[PackedDwords<T>::n], uint32_t& block, const uint32_t* __restrict__ list,
+                                               uint32_t n, uint32_t c, uint32_t grp, const FrameGeom& g, const GroupStream& gs,
+                                               int64_t threshold, uint32_t lane) {
+    const bool have = c * kWave + lane < n;
+    const uint32_t e = have ? list[c * kWave + lane] : 0u;
+    block = grp * kTileBlocks + (e >> 23);
+    const uint32_t left = (uint32_t)g.n_values - block * kBlock;   // (listed blocks lie inside the frame: < 2^29 values)
+    const uint32_t nr = have ? (left < (uint32_t)kBlock ? left : (uint32_t)kBlock) : 0u;
+    group_extract<T>(o, gs, have, (e >> 17) & 63u, nr, e & 0x1FFFFu);
+    return have ? event_mask<T>(o, nr, threshold) : 0u;
+}
+
+// what a wavefront holds for its run: lane j the offset of group g0 + j (lane n: the group behind the run)
+struct Run {
+    uint64_t frame, u0, fo, fe, my_off;
+    uint32_t g0, n;
+    const uint8_t* __restrict__ wf;
+};
+// where the run lies (arithmetic only) ...
+__device__ __forceinline__ Run run_place(const SparseArgs& a, uint64_t run, uint32_t runs_per_frame) {
+    const FrameGeom& g = a.geom;
+    Run r;
+    r.frame = run / runs_per_frame;
+    r.g0 = (uint32_t)(run - r.frame * runs_per_frame) * kRun;
+    r.n = g.n_tiles - r.g0 < kRun ? g.n_tiles - r.g0 : kRun;
+    r.u0 = r.frame * g.n_tiles + r.g0;
+    r.wf = a.widths + r.frame * g.n_blocks;
+    return r;
+}
+// ... and what is loaded once for it
+__device__ __forceinline__ void run_load(Run& r, const SparseArgs& a, uint32_t lane) {
+    r.fo = a.frame_offsets[r.frame];
+    r.fe = a.frame_offsets[r.frame + 1];
+    r.my_off = lane <= r.n && r.g0 + lane < a.geom.n_tiles ? a.tile_off[r.u0 + lane] : 0ull;
+}
+
+template <typename T>
+__device__ __forceinline__ void sparse_count_run(const SparseArgs& a, uint64_t run, uint32_t runs_per_frame, uint32_t* __restrict__ list) {
+    const FrameGeom& g = a.geom;
+    const uint32_t lane = (uint32_t)lane_id();
+    Run R = run_place(a, run, runs_per_frame);
+    run_load(R, a, lane);
+    uint32_t wn[kGroupRows], nbn[kGroupRows], wp0n[kGroupRows];
+    group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0, lane);
+    uint32_t my_count = 0;                                  // lane j: group g0 + j's events
+    uint64_t my_flags = 0;                                  // lane 4 * j + c: "has events" of its candidates 64 c .. 64 c + 63
+    bool bad = false;
+#pragma unroll 1
+    for (uint32_t j = 0; j < R.n; ++j) {
+        uint32_t w[kGroupRows], nb[kGroupRows], wp0[kGroupRows], off[kGroupRows];
+#pragma unroll
+        for (int r = 0; r < kGroupRows; ++r) { w[r] = wn[r]; nb[r] = nbn[r]; wp0[r] = wp0n[r]; }
+        if (j + 1 < R.n) group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + j + 1, lane);   // in flight during this group
+        const uint64_t t_off = lane_value64(R.my_off, j), t_next = lane_value64(R.my_off, j + 1);
+        if (!group_offsets<T>(off, w, nb, wp0, R.fo, R.fe, t_off, t_next, R.g0 + j + 1 == g.n_tiles, a.terse_bytes, lane)) {
+            bad = true;                                     // (count 0, no flags: the later passes never touch the group)
+            continue;
+        }
+        const GroupStream gs = group_stream(a.terse, a.terse_bytes, R.fo, t_off);
+        // ---- the candidates, in block order, into consecutive entries
+        uint32_t n_cand = 0;
+#pragma unroll
+        for (int r = 0; r < kGroupRows; ++r) {
+            const bool want = nb[r] != 0u && w[r] >= a.min_width;   // an optimisation only: the verdict is the compare below
+            const uint64_t ballot = __ballot(want);
+            if (want) list[n_cand + lanes_below(ballot)] = list_entry(off[r], w[r], r * kWave + lane);
+            n_cand += (uint32_t)__builtin_popcountll(ballot);
+        }
+        list_sync();
+        uint32_t count = 0;
+#pragma unroll 1
+        for (uint32_t c = 0; c * kWave < n_cand; ++c) {
+            uint32_t o[PackedDwords<T>::n], block;
+            const uint32_t mask = list_round<T>(o, block, list, n_cand, c, R.g0 + j, g, gs, a.threshold, lane);
+            count += (uint32_t)__builtin_popcount(mask);
+            const uint64_t has = __ballot(mask != 0u);
+            if (lane == (uint32_t)kGroupRows * j + c) my_flags = has;
+        }
+        list_sync();                                        // (the next group rewrites the list)
+        const uint32_t inc = wave_inclusive_scan(count);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        if (lane == j) my_count = total;
+    }
+    if (bad && lane == 0) atomicMax(&a.status[0], kStatusCorrupt);
+    if (lane < R.n) a.counts[R.u0 + lane] = my_count;
+    if (lane < (uint32_t)kGroupRows * R.n) a.flags[kGroupRows * R.u0 + lane] = my_flags;
+}
+
+template <typename T>
+__device__ __forceinline__ void sparse_write_run(const SparseArgs& a, uint64_t run, uint32_t runs_per_frame, uint32_t* __restrict__ list) {
+    const FrameGeom& g = a.geom;
+    const uint32_t lane = (uint32_t)lane_id();
+    Run R = run_place(a, run, runs_per_frame);
+    const uint32_t my_count = lane < R.n ? a.counts[R.u0 + lane] : 0u;
+    uint64_t todo = __ballot(my_count != 0u);               // the run's groups with events
+    if (todo == 0ull) return;                               // (after one load)
+    run_load(R, a, lane);
+    const uint32_t my_base = lane < R.n ? a.base[R.u0 + lane] : 0u;
+    const uint64_t my_flags = lane < (uint32_t)kGroupRows * R.n ? a.flags[kGroupRows * R.u0 + lane] : 0ull;
+    const uint64_t row = a.row_offsets[R.frame];
+    T* __restrict__ values = static_cast<T*>(a.values);
+    uint32_t wn[kGroupRows], nbn[kGroupRows], wp0n[kGroupRows];
+    group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + (uint32_t)__builtin_ctzll(todo), lane);
+#pragma unroll 1
+    while (todo) {
+        const uint32_t j = (uint32_t)__builtin_ctzll(todo);
+        todo &= todo - 1;
+        uint32_t w[kGroupRows], nb[kGroupRows], wp0[kGroupRows], off[kGroupRows];
+#pragma unroll
+        for (int r = 0; r < kGroupRows; ++r) { w[r] = wn[r]; nb[r] = nbn[r]; wp0[r] = wp0n[r]; }
+        if (todo) group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + (uint32_t)__builtin_ctzll(todo), lane);   // in flight during this group
+        const uint64_t t_off = lane_value64(R.my_off, j), t_next = lane_value64(R.my_off, j + 1);
+        if (!group_offsets<T>(off, w, nb, wp0, R.fo, R.fe, t_off, t_next, R.g0 + j + 1 == g.n_tiles, a.terse_bytes, lane)) continue;   // (counted: it was valid)
+        const GroupStream gs = group_stream(a.terse, a.terse_bytes, R.fo, t_off);
+        // ---- the candidates again, in the count pass's order; those it found events in go into the list
+        uint64_t has[kGroupRows];
+#pragma unroll
+        for (int c = 0; c < kGroupRows; ++c) has[c] = uniform64(lane_value64(my_flags, (uint32_t)kGroupRows * j + c));
+        uint32_t n_cand = 0, n_list = 0;
+#pragma unroll
+        for (int r = 0; r < kGroupRows; ++r) {
+            const bool want = nb[r] != 0u && w[r] >= a.min_width;
+            const uint64_t ballot = __ballot(want);
+            const uint32_t i = n_cand + lanes_below(ballot);                  // the block's place among the candidates
+            const uint64_t word = (i >> 6) == 0u ? has[0] : (i >> 6) == 1u ? has[1] : (i >> 6) == 2u ? has[2] : has[3];
+            const bool listed = want && ((word >> (i & 63u)) & 1ull);
+            const uint64_t lballot = __ballot(listed);
+            if (listed) list[n_list + lanes_below(lballot)] = list_entry(off[r], w[r], r * kWave + lane);
+            n_cand += (uint32_t)__builtin_popcountll(ballot);
+            n_list += (uint32_t)__builtin_popcountll(lballot);
+        }
+        list_sync();
+        uint64_t at = row + (uint32_t)__shfl((int)my_base, (int)j, kWave);   // where the group's next event goes
+#pragma unroll 1
+        for (uint32_t c = 0; c * kWave < n_list; ++c) {
+            uint32_t o[PackedDwords<T>::n], block;
+            const uint32_t mask = list_round<T>(o, block, list, n_list, c, R.g0 + j, g, gs, a.threshold, lane);
+            const uint32_t m = (uint32_t)__builtin_popcount(mask);
+            const uint32_t inc = wave_inclusive_scan(m);
+            uint64_t i = at + (inc - m);                    // rank: the blocks in front (block order), then k ascending
+#pragma unroll
+            for (int k = 0; k < kBlock; ++k) {
+                if (mask & (1u << k)) {
+                    if (i < a.capacity) {
+                        a.positions[i] = block * kBlock + k;
+                        values[i] = packed_value<T>(o, k);
+                    }
+                    ++i;
+                }
+            }
+            at += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        }
+        list_sync();                                        // (the next group rewrites the list)
+    }
+}
+
+}  // namespace
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_sparse_count(SparseArgs a, uint32_t runs_per_frame) {
+    __shared__ uint32_t s_list[kWavesPerWg * kTileBlocks];
+    const uint64_t runs = a.n_frames * runs_per_frame;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerWg;
+    for (uint64_t run = (uint64_t)blockIdx.x * kWavesPerWg + (uint32_t)wave_id(); run < runs; run += stride)
+        sparse_count_run<T>(a, run, runs_per_frame, s_list + wave_id() * kTileBlocks);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_sparse_write(SparseArgs a, uint32_t runs_per_frame) {
+    __shared__ uint32_t s_list[kWavesPerWg * kTileBlocks];
+    const uint64_t runs = a.n_frames * runs_per_frame;
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerWg;
+    for (uint64_t run = (uint64_t)blockIdx.x * kWavesPerWg + (uint32_t)wave_id(); run < runs; run += stride)
+        sparse_write_run<T>(a, run, runs_per_frame, s_list + wave_id() * kTileBlocks);
+}
+
+// per frame, one wavefront: exclusive scan of the groups' counts (a frame has < 2^29 pixels: 32 bits), the frame's total
+__global__ __launch_bounds__(kThreads) void k_sparse_frame_scan(const uint32_t* __restrict__ counts, uint64_t n_frames, uint32_t n_tiles,
+                                                                 uint32_t* __restrict__ base, uint32_t* __restrict__ frame_total) {
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerWg;
+    for (uint64_t frame = (uint64_t)blockIdx.x * kWavesPerWg + (uint32_t)wave_id(); frame < n_frames; frame += stride) {
+        uint32_t carry = 0;
+        for (uint32_t g0 = 0; g0 < n_tiles; g0 += kWave) {
+            const uint32_t i = g0 + lane;
+            const uint32_t c = i < n_tiles ? counts[frame * n_tiles + i] : 0u;
+            const uint32_t inc = wave_inclusive_scan(c);
+            if (i < n_tiles) base[frame * n_tiles + i] = carry + inc - c;
+            carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        }
+        if (lane == 0) frame_total[frame] = carry;
+    }
+}
+
+// one workgroup: exclusive scan of the frames' totals -> row_offsets[0 .. n_frames]; the total against the capacity
+__global__ __launch_bounds__(kThreads) void k_sparse_stack_scan(const uint32_t* __restrict__ frame_total, uint64_t n_frames, uint64_t capacity,
+                                                                 uint64_t* __restrict__ row_offsets, uint32_t* __restrict__ status) {
+    __shared__ uint64_t s_tot[kWavesPerWg];
+    uint64_t carry = 0;
+    for (uint64_t f0 = 0; f0 < n_frames; f0 += kThreads) {
+        const uint64_t i = f0 + threadIdx.x;
+        const uint64_t v = i < n_frames ? (uint64_t)frame_total[i] : 0ull;
+        const uint64_t inc = wave_inclusive_scan64(v);
+        if (lane_id() == 63) s_tot[wave_id()] = inc;
+        __syncthreads();
+        uint64_t wbase = 0;
+        for (int k = 0; k < wave_id(); ++k) wbase += s_tot[k];
+        if (i < n_frames) row_offsets[i] = carry + wbase + inc - v;
+        for (int k = 0; k < kWavesPerWg; ++k) carry += s_tot[k];
+        __syncthreads();                                    // (s_tot is reused by the next round)
+    }
+    if (threadIdx.x == 0) {
+        row_offsets[n_frames] = carry;
+        if (carry > capacity) atomicMax(&status[0], (uint32_t)TRPX_ERR_CAPACITY);   // (CORRUPT, the graver code, stays)
+    }
+}
+
+uint32_t sparse_min_width(int64_t threshold, bool stream_signed) {
+    if (threshold <= 0) return 0;                           // zeros are events: width-0 blocks too
+    uint32_t bl = 0;
+    for (uint64_t t = (uint64_t)threshold; t; t >>= 1) ++bl;
+    return bl + (stream_signed ? 1u : 0u);                  // w-bit two's complement fields hold up to 2^(w - 1) - 1
+}
+
+hipError_t launch_decode_sparse(int dtype, const SparseArgs& a, bool clear_status, hipStream_t st) {
+    if (clear_status) zero_status(a.status, st);
+    // launch shapes from the geometry alone: a wavefront per run of kRun groups up to 4096 workgroups, strided runs beyond
+    const uint32_t rpf = (a.geom.n_tiles + kRun - 1) / kRun;
+    const uint64_t wgs = (a.n_frames * rpf + kWavesPerWg - 1) / kWavesPerWg;
+    const uint32_t grid = (uint32_t)(wgs < 4096 ? wgs : 4096);
+    const uint64_t fwgs = (a.n_frames + kWavesPerWg - 1) / kWavesPerWg;
+    const uint32_t fgrid = (uint32_t)(fwgs < 4096 ? fwgs : 4096);
+    return for_pixel_type(dtype, [&]<class T>() {
+        hipLaunchKernelGGL((k_sparse_count<T>), dim3(grid), dim3(kThreads), 0, st, a, rpf);
+        hipLaunchKernelGGL(k_sparse_frame_scan, dim3(fgrid), dim3(kThreads), 0, st, a.counts, a.n_frames, a.geom.n_tiles, a.base, a.frame_total);
+        hipLaunchKernelGGL(k_sparse_stack_scan, dim3(1), dim3(kThreads), 0, st, a.frame_total, a.n_frames, a.capacity, a.row_offsets, a.status);
+        if (a.positions) hipLaunchKernelGGL((k_sparse_write<T>), dim3(grid), dim3(kThreads), 0, st, a, rpf);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace trpx

@@ -140,16 +140,6 @@ __global__ __launch_bounds__(kThreads) void k_frame_scan(const uint32_t* __restr
 // ---------------------------------------------------------------------------------------------
 // K2b: exclusive scan of frame sizes over the stack (single workgroup; F is small).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t wave_inclusive_scan64(uint64_t v) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, off, 64);
-        uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), off, 64);
-        if (lane_id() >= off) v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kThreads) void k_stack_scan(const uint64_t* __restrict__ frame_size,
                                                          uint32_t n_frames, uint64_t out_capacity,
                                                          uint64_t* __restrict__ frame_offsets,

@@ -239,6 +239,42 @@ class Terse:
         frames = range(self.number_of_frames()) if frames is None else frames
         return self.prolix_boxes([(int(f), y0, x0) for f in frames], (h, w))
 
+    def prolix_sparse(self, threshold: int, frames=None):
+        """The pixels with value >= ``threshold`` (trpx_decode_sparse_host: two GPU calls, sizes then events), without decoding
+        the frames to memory.  Returns numpy ``(row_offsets int64 [n + 1], positions uint32, values)``: event i of the k-th frame
+        asked for, row_offsets[k] <= i < row_offsets[k + 1], is pixel positions[i] of that frame with value values[i], in ascending
+        pixel order; values have the narrowest integer type that holds the object's values.  ``frames``: a list of frame numbers
+        (default: all), results in the order asked."""
+        code, dt = self._stream_type("prolix_sparse")
+        f = self.number_of_frames()
+        frames = list(range(f)) if frames is None else [int(x) for x in frames]
+        if any(x < 0 or x >= f for x in frames):
+            raise ValueError("prolix_sparse: frame index out of range")
+        rows = np.zeros(f + 1, np.uint64)
+        pos, val = np.empty(0, np.uint32), np.empty(0, dt)
+        if f:
+            buf = np.frombuffer(self._data, np.uint8)
+            offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+            found = C.c_size_t(0)
+
+            def call(p, v, cap):
+                return lib().trpx_decode_sparse_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f, self._block,
+                                                     int(threshold), rows.ctypes.data, p, v, cap, C.byref(found), self._device)
+            rc = call(None, None, 0)
+            if rc != _lib.ERR_CAPACITY:                      # (CAPACITY: there are events, found.value of them)
+                check(rc)
+            if found.value:
+                pos, val = np.empty(found.value, np.uint32), np.empty(found.value, dt)
+                check(call(pos.ctypes.data, val.ctypes.data, found.value))
+        rows = rows.astype(np.int64)
+        if frames == list(range(f)):
+            return rows, pos, val
+        pieces = [slice(int(rows[x]), int(rows[x + 1])) for x in frames]     # (the whole stack is decoded: filtered on the host)
+        out_rows = np.concatenate([[0], np.cumsum([p.stop - p.start for p in pieces])]).astype(np.int64)
+        if not pieces:
+            return out_rows, pos[:0], val[:0]
+        return out_rows, np.concatenate([pos[p] for p in pieces]), np.concatenate([val[p] for p in pieces])
+
     # ---- accessors (Terse.hpp:396-444) --------------------------------------------------------
     def size(self) -> int:
         return self._size
