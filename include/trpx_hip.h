@@ -40,11 +40,28 @@ typedef enum trpx_status {
     TRPX_ERR_UNSUPPORTED = 2,   /* block outside 1..4096, decode index with block != 12, ...   */
     TRPX_ERR_CAPACITY = 3,      /* output or workspace too small                              */
     TRPX_ERR_HIP = 4,           /* a HIP runtime call failed (text has the HIP error)         */
-    TRPX_ERR_CORRUPT = 5,       /* bitstream runs past its frame / buffer                     */
+    TRPX_ERR_CORRUPT = 5,       /* bitstream runs past its frame / buffer; also a VALID stream with
+                                   RESTATED widths on the device entry points named below      */
     TRPX_ERR_NO_DEVICE = 6,     /* no gfx950 device visible                                   */
     TRPX_ERR_TIMEOUT = 7        /* single-pass encoder: a bounded inter-workgroup wait expired;
                                    re-issue through the two-pass pipeline (trpx_set_encode_path) */
 } trpx_status;
+
+/* Restated widths.  The decoder grammar (Terse.hpp:360-372) also accepts an explicit header -- flag 0 + the width code -- for a
+ * block whose width equals the one before ("restated"), and widths larger than the values need ("padded").  No encoder here
+ * writes either; files of another TERSE writer may hold them.  Padded widths decode everywhere.  A decode index describes a
+ * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
+ *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
+ *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi and
+ *     trpx_decode_sparse where they build the index themselves (no index given) -- and their _host forms;
+ *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
+ *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
+ *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
+ *   - trpx_decode_convert and trpx_locate_frames handle it like any other stream;
+ *   - the host entry points that stand in for the reference class -- trpx_decode_host, trpx_decode_host_grouped,
+ *     trpx_stack_read, the Terse classes' prolix -- decode it: where the tuned route reports CORRUPT they go on to the
+ *     converting decoder.
+ * Status 0 with pixels that are not the stream's is never an outcome (tests/test_gpu_noncanonical.py). */
 
 /* Pixel types = the reference CLI's dispatch set (src/terse.cpp:113-118). Odd = signed. */
 typedef enum trpx_dtype {
@@ -114,7 +131,8 @@ int trpx_encode(int dtype, const void* pixels, size_t n_values, size_t n_frames,
  *                  (the .trpx format stores no index), see below
  *   pixels_out     DEVICE T[n_frames * n_values], aligned to T (16-byte aligned with n_values % 4 == 0: the fastest case)
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT if a frame's
- *                  bits run past its end (the reference does not check; we do)
+ *                  bits run past its end (the reference does not check; we do), and for a valid stream with restated widths
+ *                  in a frame that is decoded through block widths ("Restated widths" above; the basic route decodes it)
  * frame_offsets = NULL (an index-free stack, a .trpx file): where trpx_locate_frames takes its position-parallel route (block
  * 12, pixels of up to 32 bits, 4 frames and 8 KB and more, not TRPX_LOCATE_PATH=serial / TRPX_DECODE_PATH=basic) and its
  * workspace fits behind the offsets in this call's workspace, the frames are located that way and then decoded by the same
@@ -149,7 +167,9 @@ int trpx_decode_convert(int stream_signed, int out_dtype, const uint8_t* terse, 
  * width[b] (1 byte per block) and the bit offset of every 256-block group.  The index is an opaque DEVICE
  * buffer of trpx_index_bytes(); it is NOT part of the bitstream (files stay byte-identical).
  *   trpx_encode_indexed   = trpx_encode that also fills `index` (index == NULL: plain trpx_encode)
- *   trpx_build_index      fills `index` from an existing stack (the walk alone)
+ *   trpx_build_index      fills `index` from an existing stack (the walk alone), and compares it with the stream's headers
+ *                           block by block: a valid stream with restated widths ("Restated widths" above) has no index,
+ *                           status[0] = TRPX_ERR_CORRUPT (trpx_index_from_group_states: the same)
  *   trpx_decode_indexed   = trpx_decode without the walk; the index is validated against the frame sizes
  *                           (inconsistent -> status[0] = TRPX_ERR_CORRUPT), frame_offsets is mandatory.
  *                           Stacks of >= 1024 small frames that start inside a 128-byte line (pixel bytes per frame no
@@ -240,7 +260,8 @@ int trpx_set_locate_path(int path);
  *                  fast case).  Output j = the sum of frames [j * group, min((j + 1) * group, n_frames)): a group that does
  *                  not divide n_frames leaves a shorter last group.
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT in the cases of trpx_decode, for an index
- *                  that does not fit the frames and for a block wider than dtype's; the sums are then unspecified
+ *                  that does not fit the frames and for a block wider than dtype's; with index == NULL also for a valid stream
+ *                  with restated widths (trpx_build_index's verdict; the host form returns it); the sums are then unspecified
  *   workspace      DEVICE, 8-byte aligned, >= trpx_decode_sum_workspace_bytes() (the need with frame_offsets and index both
  *                  NULL; with them given less is used: a call with offsets, index and no frame chunks needs none)
  * The sum is exact in integers and converted once: I32 / U32 clamp to their limits (the narrowing of Bit_pointer.hpp:747-763),
@@ -281,7 +302,8 @@ int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t 
  *                  frame boxes[i].frame
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT when a 256-block group the kernel walks does
  *                  not end where the next group's offset (the last group: the frame's size) says, a block is wider than dtype
- *                  allows, or a read would leave the frame; TRPX_ERR_INVALID_ARG when a box has frame >= n_frames, y0 + box_h
+ *                  allows, or a read would leave the frame; with index == NULL also for a valid stream with restated widths
+ *                  (trpx_build_index's verdict on the whole stack); TRPX_ERR_INVALID_ARG when a box has frame >= n_frames, y0 + box_h
  *                  > height or x0 + box_w > width -- that box's output is unspecified, the other boxes are still correct.  With
  *                  errors of both kinds either is reported.  ONLY THE GROUPS THE BOXES TOUCH ARE READ AND VALIDATED: status 0
  *                  says nothing about the rest of the stack (with offsets or index NULL the locator's / the walk's verdict on
@@ -330,7 +352,8 @@ int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
  *                  values = NULL with capacity 0 (one NULL without the other, or NULL with capacity > 0: TRPX_ERR_INVALID_ARG)
  *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT when a 256-block group does not end where the
  *                  next group's offset (the last group: the frame's size) says, a block is wider than dtype allows, a frame lies
- *                  outside the stream or the index does not fit the offsets: EVERY group of EVERY frame is walked, so the whole
+ *                  outside the stream or the index does not fit the offsets, with index == NULL also for a valid stream with
+ *                  restated widths (trpx_build_index's verdict): EVERY group of EVERY frame is walked, so the whole
  *                  stack is validated (unlike trpx_decode_roi).  The outputs are then unspecified.  TRPX_ERR_CORRUPT wins over
  *                  TRPX_ERR_CAPACITY when both apply
  * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)) is read, nothing outside

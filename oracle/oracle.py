@@ -58,6 +58,9 @@ def lib():
         L.trpx_oracle_encode.restype = C.c_long
         L.trpx_oracle_encode.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
                                          C.c_size_t, C.POINTER(C.c_uint)]
+        L.trpx_oracle_encode_with.restype = C.c_long
+        L.trpx_oracle_encode_with.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t]
         L.trpx_oracle_decode.restype = C.c_long
         L.trpx_oracle_decode.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t,
                                          C.c_uint, C.c_void_p]
@@ -166,6 +169,33 @@ def encode_stack(px: np.ndarray, block: int = 12):
         sizes.append(s.size)
         pb = max(pb, p)
     return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), np.array(sizes, np.uint64), pb
+
+
+def encode_with(px: np.ndarray, widths, explicit=None, block: int = 12) -> np.ndarray:
+    """Encode ONE frame with the caller's widths and header forms (trpx_oracle_encode_with): widths[b] >= the block's own width
+    ("padded" where larger), explicit[b] != 0 an explicit header even where the width repeats ("restated").  Valid streams that
+    no encoder here writes.  Returns the stream bytes; ValueError for a width a block does not fit or the type cannot hold."""
+    px = np.ascontiguousarray(px).reshape(-1)
+    nb = (px.size + block - 1) // block
+    w = np.ascontiguousarray(widths, dtype=np.uint8).reshape(-1)
+    e = np.zeros(nb, np.uint8) if explicit is None else np.ascontiguousarray(np.asarray(explicit) != 0, dtype=np.uint8).reshape(-1)
+    if w.size != nb or e.size != nb:
+        raise ValueError(f"encode_with: {nb} blocks, {w.size} widths, {e.size} flags")
+    cap = worst_case_bytes(px.dtype, px.size, block)
+    out = np.zeros(cap, np.uint8)
+    s = lib().trpx_oracle_encode_with(dtype_code(px.dtype), px.ctypes.data, px.size, block, w.ctypes.data, e.ctypes.data,
+                                      out.ctypes.data, cap)
+    if s < 0:
+        raise ValueError("encode_with: a width below its block's own or above the type's bit size")
+    return out[:s].copy()
+
+
+def encode_stack_with(px: np.ndarray, widths, explicit=None, block: int = 12):
+    """encode_with for a [frames, N] stack, widths / explicit as [frames, blocks]: (concatenated bytes, per-frame sizes)."""
+    px = np.ascontiguousarray(px)
+    px = px.reshape(px.shape[0], -1)
+    parts = [encode_with(px[f], widths[f], None if explicit is None else explicit[f], block) for f in range(px.shape[0])]
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), np.array([p.size for p in parts], np.uint64)
 
 
 def decode(stream: np.ndarray, n: int, dtype, stream_signed=None, block: int = 12) -> np.ndarray:

@@ -152,6 +152,46 @@ long trpx_oracle_encode(int dtype, const void* px, size_t n, unsigned block, uin
     return (long)(1 + bw.bit / 8);                          /* Terse.hpp:547 */
 }
 
+/*
+ * Encode one frame with widths and header forms the CALLER chooses: valid streams that neither this file's encoder nor the
+ * reference's ever writes, but that the decoder grammar (Terse.hpp:360-372) accepts.
+ *   widths[b]    the width block b is written with: at least the block's own width (trpx_oracle_widths) and at most the bit
+ *                size of the type, else -1 (a "padded" width where larger than needed);
+ *   explicit[b]  != 0: flag 0 + the width code even where widths[b] equals the width before (a "restated" width).  NULL: none.
+ * Fields are the low widths[b] bits of the two's complement value; everything else as trpx_oracle_encode (zero pad bits,
+ * S = 1 + bits / 8).  `out` must hold trpx_oracle_worst_case_bytes().
+ */
+long trpx_oracle_encode_with(int dtype, const void* px, size_t n, unsigned block, const uint8_t* widths,
+                             const uint8_t* explicit_hdr, uint8_t* out, size_t cap) {
+    size_t need = trpx_oracle_worst_case_bytes(dtype, n, block);
+    const unsigned tbits = 8 * dtype_bytes(dtype);
+    if (cap < need || block == 0 || tbits == 0 || dtype > TRPX_I64 || !widths) return -1;
+    memset(out, 0, need);
+    bitw_t bw = { out, 0 };
+    unsigned prev = 0;
+    size_t b = 0;
+    for (size_t from = 0; from < n; from += block, ++b) {
+        size_t to = from + block < n ? from + block : n;
+        unsigned w = widths[b];
+        if (w < block_width(dtype, px, from, to) || w > tbits) return -1;
+        if (w == prev && !(explicit_hdr && explicit_hdr[b])) {
+            put_bits(&bw, 1, 1);
+        } else {
+            put_bits(&bw, 0, 1);
+            if (w < 7) put_bits(&bw, w, 3);
+            else if (w < 10) put_bits(&bw, 7u + ((w - 7) << 3), 5);
+            else put_bits(&bw, 31u + ((uint64_t)(w - 10) << 5), 11);
+            prev = w;
+        }
+        if (w) {
+            uint64_t mask = w < 64 ? (((uint64_t)1 << w) - 1) : ~(uint64_t)0;
+            for (size_t i = from; i < to; ++i)
+                put_bits(&bw, (uint64_t)load_elem(dtype, px, i) & mask, w);
+        }
+    }
+    return (long)(1 + bw.bit / 8);
+}
+
 /* LSB-first bit reader with bounds check (the reference has none: SURVEY.md section 5). */
 typedef struct { const uint8_t* base; size_t nbits; size_t bit; int err; } bitr_t;
 

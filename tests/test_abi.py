@@ -133,7 +133,7 @@ def test_host_code_survives_corrupt_input_under_asan_ubsan(tmp_path):
 
 def test_integration_md_code_blocks_are_the_compiled_snippets():
     """INTEGRATION.md sections 2 and 4 show a maintainer the calls to write; tests/cpp/integration_snippets.cpp is those
-    blocks compiled against include/trpx_hip.h (make -C tests/cpp).  Every line of every marked snippet must appear in the
+    blocks compiled against include/trpx_hip.h (make -C tests/cpp integration_snippets, run by this test).  Every line of every marked snippet must appear in the
     document, in order: a signature change that is not carried into the document fails here."""
     import re
     cpp = open(os.path.join(ROOT, "tests", "cpp", "integration_snippets.cpp")).read()
@@ -147,7 +147,13 @@ def test_integration_md_code_blocks_are_the_compiled_snippets():
                 continue
             assert ln in doc[at:], (name, ln)
             at = doc.index(ln, at) + 1
-    assert os.path.exists(os.path.join(ROOT, "tests", "cpp", "integration_snippets")), "make -C tests/cpp did not build it"
+    # ... and the program compiles against the header as it is now: built here (make: nothing to do when build() has built it
+    # and neither the header nor the library changed since), not taken on trust from an earlier build's leftovers
+    import subprocess
+    exe = os.path.join(ROOT, "tests", "cpp", "integration_snippets")
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "integration_snippets"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert os.path.exists(exe), "make -C tests/cpp did not build it"
 
 
 def test_kernel_sources_compile_without_the_llvm_testing_option():

@@ -1180,20 +1180,32 @@ def test_fuzz_slice_every_route(gpu, oracle, route):
     """A bounded, seeded slice of tools/fuzz_paths.py inside the tier the driver runs: random pixel types, frame sizes (small,
     512 x 512, detector sizes beyond 32 K blocks), frame counts and width patterns (runs, flips, pedestals, Poisson counts, type
     extremes), encoded by the GPU (== the oracle's bytes), decoded along the forced route (== the pixels), the decode index
-    three ways.  6 - 10 s per route; the long runs stay with the tool (profiles/rNN_fuzz.txt)."""
+    three ways.  The slice is the first _FUZZ_SLICE cases of the seed's sequence that stay within max_pixels: the same cases on
+    every machine (the time budget is a safety cap far above what they take, 6 - 10 s per route); the long runs stay with the
+    tool (profiles/rNN_fuzz.txt).  Then valid streams no encoder writes -- restated widths, tests/noncanonical.py K1 and K3 --
+    along the same route: exact or refused, as tests/test_gpu_noncanonical.py pins it."""
     import importlib.util
     from trpx_amd import _lib
+    import noncanonical as nc
+    import test_gpu_noncanonical as tn
     spec = importlib.util.spec_from_file_location("fuzz_paths", os.path.join(ROOT, "tools", "fuzz_paths.py"))
     fz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fz)
     code = {"auto": 0, **_ROUTES}[route]
     assert _lib.lib().trpx_set_decode_path(code) == 0
     try:
-        n_run, n_large, n_fb = fz.run(60, seed=600 + code, basic=route == "basic", budget_s=6.0, quiet=True,
+        n_run, n_large, n_fb = fz.run(60, seed=600 + code, basic=route == "basic", budget_s=300.0, quiet=True, max_run=_FUZZ_SLICE,
                                       max_pixels=1 << (21 if route in ("basic", "frames") else 23))
+        for kind in ("K1", "K3"):
+            for dt, shape in ((np.uint16, (3, 7000)), (np.int32, (4, 1073))):
+                v = tn.Dev(nc.make(dt, shape, kind)).decode("offsets")
+                assert v in (tn.EXACT, tn.REFUSED) and v == tn.pinned(f"decode|offsets|{code}", kind, shape, dt), (route, kind, dt, shape, v)
     finally:
         _lib.lib().trpx_set_decode_path(0)
-    assert n_run >= 8, n_run
+    assert n_run == _FUZZ_SLICE, n_run
+
+
+_FUZZ_SLICE = 10     # cases per route (>= 8); every route's seed has more than that within its max_pixels among its 60
 
 
 @pytest.mark.parametrize("dtype", ALL_DTYPES)

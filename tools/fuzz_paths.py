@@ -11,10 +11,11 @@ DT = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 TDT = {np.uint8: torch.uint8, np.int8: torch.int8, np.uint16: torch.uint16, np.int16: torch.int16, np.uint32: torch.uint32, np.int32: torch.int32}
 
 
-def run(cases, seed=1, basic=False, budget_s=None, quiet=False, max_pixels=None):
+def run(cases, seed=1, basic=False, budget_s=None, quiet=False, max_pixels=None, max_run=None, count_only=False):
     """`cases` random stacks from `seed` through the route the library is set to.  basic: skip the decode-index checks (the basic
     kernels have none); budget_s: stop starting cases after this many seconds; max_pixels: skip stacks larger than this (the
-    random sequence stays the same).  Returns (cases run, large frames seen, of them handed to the fallback route)."""
+    random sequence stays the same); max_run: stop after this many cases have run; count_only: run nothing, count the cases that
+    would (no GPU needed: how many cases a seed and a max_pixels select).  Returns (cases run, large frames seen, of them handed to the fallback route)."""
     rng = np.random.RandomState(seed)
     t0 = time.time()
     n_large = n_fallback = n_run = 0
@@ -55,7 +56,9 @@ def run(cases, seed=1, basic=False, budget_s=None, quiet=False, max_pixels=None)
         if os.environ.get("TRPX_FUZZ_ONLY") and c not in [int(x) for x in os.environ["TRPX_FUZZ_ONLY"].split(",")]: continue   # (same random sequence, only these cases run)
         if max_pixels is not None and frames * n > max_pixels: continue
         if budget_s is not None and time.time() - t0 > budget_s: break
+        if max_run is not None and n_run >= max_run: break
         n_run += 1
+        if count_only: continue
         if os.environ.get("TRPX_FUZZ_ONLY"): print(f"case {c}: kind {kind} {dt} n {n} frames {frames} widths {np.unique(hi)[:8]} pixels {np.unique(px)[:12]}", flush=True)
         want, sizes, pb = O.encode_stack(px)
         dpx = torch.from_numpy(px.view(np.dtype(f"i{dt.itemsize}"))).cuda().view(TDT[dt.type])

@@ -247,8 +247,10 @@ void* indexed_scratch(size_t bytes, hipStream_t st) {
     return p;
 }
 
+// check: compare the index with the stream's headers (k_check_index); false where the stream is the encoder's own, or the
+// consumer makes the comparison itself
 int build_index_impl(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
-                     size_t n_frames, unsigned block, void* index, uint32_t* status, bool clear_status, void* stream) {
+                     size_t n_frames, unsigned block, void* index, uint32_t* status, bool clear_status, void* stream, bool check = true) {
     trpx::FrameGeom g;
     if (const int rc = check_args("trpx_build_index", kIndexOnly | kHasStream, dtype, trpx_dtype_size(dtype), 0, terse_bytes, n_values, n_frames, block,
                                   {{terse, 4}, {frame_offsets, 8}, {index, 16}, {status, 8}}, &g))
@@ -264,6 +266,9 @@ int build_index_impl(int dtype, const uint8_t* terse, size_t terse_bytes, const 
     if (a.chain) point_into(a, index, il, kParts);
     else a.parts_per_frame = 1;
     HIP_TRY(trpx::launch_walk_only(a, (uint32_t)(8 * trpx_dtype_size(dtype)), clear_status, static_cast<hipStream_t>(stream)));
+    // an index is only good for a stream whose layout follows from its widths: a restated width (valid, written by no encoder
+    // here) makes the index CORRUPT here, not pixels wrong in whatever consumes it
+    if (check) HIP_TRY(trpx::launch_check_index(a, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -312,7 +317,7 @@ int encode_impl(int dtype, const void* pixels, size_t n_values, size_t n_frames,
         trpx::fused_ws_forget(workspace, workspace_bytes);
         HIP_TRY(trpx::launch_encode(dtype, a, static_cast<hipStream_t>(stream)));
         if (index && out)   // the two-pass pipeline does not emit the index: build it from the stream it just wrote
-            return build_index_impl(dtype, out, out_capacity, frame_offsets, n_values, n_frames, block, index, status, false, stream);
+            return build_index_impl(dtype, out, out_capacity, frame_offsets, n_values, n_frames, block, index, status, false, stream, false);
     }
     return TRPX_OK;
 }
@@ -559,6 +564,7 @@ int trpx_index_from_group_states(int dtype, const uint8_t* terse, size_t terse_b
     trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, nullptr, status);
     point_into(a, index, idx_layout(g, n_frames));
     HIP_TRY(trpx::launch_walk_groups(a, (uint32_t)(8 * trpx_dtype_size(dtype)), states, true, static_cast<hipStream_t>(stream)));
+    HIP_TRY(trpx::launch_check_index(a, static_cast<hipStream_t>(stream)));         // (as trpx_build_index)
     return TRPX_OK;
 }
 
@@ -672,7 +678,7 @@ IndexWs index_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t
 // the status block (false once the locator or the walk has written its verdict there).
 int index_in_workspace(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t** frame_offsets, const void** index,
                        size_t n_values, size_t n_frames, unsigned block, const trpx::FrameGeom& g, uint32_t* status, char* ws,
-                       const IndexWs& w, void* stream, bool* clear) {
+                       const IndexWs& w, void* stream, bool* clear, bool check = true) {
     *clear = true;
     if (!*frame_offsets) {                                                      // index-free: locate the frames first (its scratch: the index region)
         uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
@@ -683,7 +689,7 @@ int index_in_workspace(int dtype, const uint8_t* terse, size_t terse_bytes, cons
     }
     if (!*index) {                                                              // the walk of trpx_build_index, into the workspace
         const int rc = build_index_impl(dtype, terse, terse_bytes, *frame_offsets, n_values, n_frames, block, ws + w.region, status,
-                                        *clear, stream);
+                                        *clear, stream, check);
         if (rc) return rc;
         *index = ws + w.region;
         *clear = false;
@@ -742,8 +748,9 @@ int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse
     char* ws = static_cast<char*>(workspace);
     if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);
     bool clear = true;
+    // (no k_check_index behind the walk: k_sum_tiles compares every block's header bit with its widths on the way)
     if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
-                                          w.front, stream, &clear))
+                                          w.front, stream, &clear, false))
         return rc;
     const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
     trpx::SumArgs a{};

@@ -63,6 +63,17 @@ template <typename T> constexpr int max_block_bits() { return 12 + kBlock * Pixe
 __device__ __forceinline__ uint32_t header_len(uint32_t w, uint32_t w_prev) {
     return w == w_prev ? 1u : (w < 7u ? 4u : (w < 10u ? 6u : 12u));
 }
+// A RESTATED width: an explicit header although the width repeats (flag 0 + the width code, 4 / 6 / 12 bits where header_len
+// says 1).  Valid (Terse.hpp:360-372 reads it), written by no encoder here.  header_len cannot know of it, so whatever rebuilds
+// a layout from widths alone must be told.  The serial walker of the basic and the converting decode (walk_serial.hpp) tells
+// its own extraction kernels (decode.hip) in bit 7 of the width byte of ITS workspace -- widths are at most 64 --; the decode
+// index (include/trpx_hip.h) has no such bit: the walkers that write it report a restated width as kStatusCorrupt.
+constexpr uint32_t kWidthMask = 0x7Fu, kWidthRestated = 0x80u;
+__device__ __forceinline__ uint32_t explicit_header_len(uint32_t w) { return w < 7u ? 4u : (w < 10u ? 6u : 12u); }
+// (raw, raw_prev: width bytes as walk_frame leaves them)
+__device__ __forceinline__ uint32_t header_len_flagged(uint32_t raw, uint32_t raw_prev) {
+    return raw & kWidthRestated ? explicit_header_len(raw & kWidthMask) : header_len(raw & kWidthMask, raw_prev & kWidthMask);
+}
 // Header value (LSB first, bit 0 = the "same" flag).
 __device__ __forceinline__ uint32_t header_val(uint32_t w, uint32_t w_prev) {
     if (w == w_prev) return 1u;                              // Terse.hpp:518

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kThreads) void k_unpack(const uint8_t* __restrict__
     const bool valid = b < g.n_blocks;
     const uint8_t* wf = widths + (uint64_t)frame * g.n_blocks;
 
-    uint32_t w = 0, w_prev = 0;
+    uint32_t w = 0, w_prev = 0;                             // (as walk_frame leaves them: kWidthRestated in bit 7)
     int nb = 0;
     if (valid) {
         w = wf[b];
@@ -86,7 +86,8 @@ __global__ __launch_bounds__(kThreads) void k_unpack(const uint8_t* __restrict__
         const uint64_t first = (uint64_t)b * kBlock;
         nb = first + kBlock <= g.n_values ? kBlock : (int)(g.n_values - first);
     }
-    const uint32_t hl = header_len(w, w_prev);
+    const uint32_t hl = header_len_flagged(w, w_prev);
+    w &= kWidthMask;
     const uint32_t len = valid ? hl + (uint32_t)nb * w : 0u;
     uint32_t total;
     const uint32_t excl = block_exclusive_scan(len, s_tot, &total);
@@ -167,12 +168,13 @@ __global__ __launch_bounds__(kThreads) void k_unpack_g(const uint8_t* __restrict
     const uint8_t* wf = widths + (uint64_t)frame * g.n_blocks;
     uint32_t w = 0, w_prev = 0, nb = 0;
     if (valid) {
-        w = wf[b];
+        w = wf[b];                                          // (as walk_frame leaves them: kWidthRestated in bit 7)
         w_prev = b ? wf[b - 1] : 0u;
         const uint64_t first = (uint64_t)b * g.block;
         nb = (uint32_t)(first + g.block <= g.n_values ? g.block : g.n_values - first);
     }
-    const uint32_t hl = header_len(w, w_prev);
+    const uint32_t hl = header_len_flagged(w, w_prev);
+    w &= kWidthMask;
     const uint32_t len = valid ? hl + nb * w : 0u;
     uint32_t total;
     const uint32_t excl = block_exclusive_scan(len, s_tot, &total);
@@ -273,12 +275,13 @@ __global__ __launch_bounds__(kThreads) void k_unpack_conv(const uint8_t* __restr
     const uint8_t* wf = widths + (uint64_t)frame * g.n_blocks;
     uint32_t w = 0, w_prev = 0, nb = 0;
     if (valid) {
-        w = wf[b];
+        w = wf[b];                                          // (as walk_frame leaves them: kWidthRestated in bit 7)
         w_prev = b ? wf[b - 1] : 0u;
         const uint64_t first = (uint64_t)b * g.block;
         nb = (uint32_t)(first + g.block <= g.n_values ? g.block : g.n_values - first);
     }
-    const uint32_t hl = header_len(w, w_prev);
+    const uint32_t hl = header_len_flagged(w, w_prev);
+    w &= kWidthMask;
     const uint32_t len = valid ? hl + nb * w : 0u;
     uint32_t total;
     const uint32_t excl = block_exclusive_scan(len, s_tot, &total);

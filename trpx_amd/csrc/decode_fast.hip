@@ -123,6 +123,54 @@ __global__ __launch_bounds__(kThreads) void k_walk_groups(const uint8_t* __restr
     if (bad) atomicMax(&status[0], kStatusCorrupt);
 }
 
+// ---------------------------------------------------------------------------------------------
+// A freshly written decode index against its stream, block by block.  Whatever consumes an index rebuilds the layout from the
+// widths alone (header_len: one bit where a width repeats), so an index must not describe a stream with a RESTATED width (an
+// explicit header of the width before: valid, codec_common.hpp) -- and the walkers that write indices do not look for one.
+// One lane per block, a workgroup per group of 256: positions by the consumers' own rule from the group's recorded offset,
+// and at each the stream's header must be what the widths say: the "same width" bit exactly where the width repeats, else the
+// width's code.  Up to a group's first restated width the rule's positions are the true ones, so that header is seen: CORRUPT.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_check_index(const uint8_t* __restrict__ terse, uint64_t terse_bytes,
+                                                          const uint64_t* __restrict__ frame_offsets, FrameGeom g,
+                                                          const uint8_t* __restrict__ widths, const uint64_t* __restrict__ tile_off,
+                                                          uint32_t* __restrict__ status) {
+    __shared__ uint32_t s_tot[4];
+    if (status[0] != 0) return;                             // (uniform: the walk has given its verdict)
+    const uint64_t tile = blockIdx.x;
+    const uint64_t frame = tile / g.n_tiles;
+    const uint32_t b = (uint32_t)(tile % g.n_tiles) * kTileBlocks + threadIdx.x;
+    const bool valid = b < g.n_blocks;
+    uint32_t w = 0, w_prev = 0, nb = 0;
+    if (valid) {
+        const uint8_t* wf = widths + frame * g.n_blocks;
+        w = wf[b];
+        w_prev = b ? wf[b - 1] : 0u;
+        const uint64_t first = (uint64_t)b * kBlock;
+        nb = (uint32_t)(first + kBlock <= g.n_values ? kBlock : g.n_values - first);
+    }
+    const uint32_t hl = header_len(w, w_prev);
+    uint32_t total;
+    const uint32_t excl = block_exclusive_scan(valid ? hl + nb * w : 0u, s_tot, &total);
+    if (!valid) return;
+    const uint64_t fo = frame_offsets[frame], fe = frame_offsets[frame + 1];
+    const uint64_t pos = tile_off[tile] + excl;             // the block's header, relative to the frame
+    bool ok = fe > fo && fe <= terse_bytes && pos + hl <= 8 * (fe - fo);
+    if (ok) {
+        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(terse);
+        const uint64_t n_dw = (terse_bytes + 3) / 4;
+        const uint32_t bits = (uint32_t)stream_bits([&](uint64_t i) { return ld_stream_dw(s32, i, n_dw); }, 8 * fo + pos);
+        ok = bits & 1u ? hl == 1u : (hl != 1u && parse_explicit_header(bits).w == w);   // Terse.hpp:361-370
+    }
+    if (!ok) atomicMax(&status[0], kStatusCorrupt);
+}
+
+hipError_t launch_check_index(const DecodeArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_check_index, dim3((uint32_t)((uint64_t)a.n_frames * a.geom.n_tiles)), dim3(kThreads), 0, st, a.terse,
+                       (uint64_t)a.terse_bytes, a.frame_offsets, a.geom, a.widths, a.tile_off, a.status);
+    return hipGetLastError();
+}
+
 hipError_t launch_index_group_states(const DecodeArgs& a, uint64_t* states, hipStream_t st) {
     const uint64_t n = (uint64_t)a.n_frames * a.geom.n_tiles;
     hipLaunchKernelGGL(k_index_group_states, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a.widths, a.tile_off,

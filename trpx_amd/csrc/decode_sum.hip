@@ -128,6 +128,9 @@ __device__ __forceinline__ bool sum_extract(SumAcc<T> (&acc)[sum_sub_tiles<T>()]
         const uint32_t q = c.img_bit0 + c.off[r] + c.hl[r];  // first payload bit in the image
         uint32_t u[kBlock];
         if (c.nb[r] && tile_too_wide<T>(c.w[r])) ok = false;
+        // (as unpack_tile: the "same width" bit stands exactly where header_len counted one bit, or the widths are not this
+        // stream's layout -- a restated width, codec_common.hpp)
+        if (c.nb[r] && ((s_image[(q - c.hl[r]) >> 5] >> ((q - c.hl[r]) & 31u)) & 1u) != (c.hl[r] == 1u ? 1u : 0u)) ok = false;
         tile_extract_full<T>(u, s_image, q, c.w[r], c.nb[r]);
         if (c.nb[r] && c.nb[r] < kBlock) {              // the frame's last, partial block (unrolled: u stays in registers)
             const uint32_t ww = tile_partial_width<T>(c.w[r]), mask = field_mask(ww);

@@ -105,6 +105,8 @@ hipError_t launch_seg_listed(const DecodeArgs& a, uint32_t max_w, hipStream_t st
 hipError_t launch_seg_groups(const DecodeArgs& a, uint32_t max_w, const uint64_t* states, hipStream_t st);   // decode_seg.hip: index from group states (frames < 2^32 bits)
 // header walk only (fills a.widths / a.tile_off from the stream): builds the decode index of an existing stack
 hipError_t launch_walk_only(const DecodeArgs& a, uint32_t max_w, bool clear_status, hipStream_t st);
+// a.widths / a.tile_off against the stream, block by block: CORRUPT where the index describes a restated width (decode_fast.hip)
+hipError_t launch_check_index(const DecodeArgs& a, hipStream_t st);
 hipError_t launch_walk_serial(const DecodeArgs& a, uint32_t max_w, hipStream_t st);
 // decode_locate.hip: frame_offsets[0 .. n_frames] of a stack without an index (trpx_locate_frames): the position-parallel
 // locator (block 12, max_w <= 32) or the serial walk, count only.  Workspace: locate_workspace_bytes (about terse_bytes / 64 +

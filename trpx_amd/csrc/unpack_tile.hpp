@@ -180,6 +180,10 @@ __device__ __forceinline__ bool unpack_tile(const uint8_t* __restrict__ terse, u
     for (int r = 0; r < kSub; ++r) {
         const uint32_t b = b0 + r * kThreads + tid;
         const uint32_t q = img_bit0 + off[r] + hl[r];       // first payload bit in the image
+        // The layout comes from the widths alone: the "same width" bit must stand exactly where header_len counted one bit.  A
+        // restated width (an explicit header of the width before: valid, codec_common.hpp) shows here -- up to the tile's first
+        // one the positions are the true ones -- and the tile's pixels would be another stream's.
+        if (nb[r] && ((s_image[(q - hl[r]) >> 5] >> ((q - hl[r]) & 31u)) & 1u) != (hl[r] == 1u ? 1u : 0u)) atomicMax(&status[0], kStatusCorrupt);
         uint32_t u[kBlock];
         tile_extract_full<T>(u, s_image, q, w[r], nb[r]);
         if (unpack_staged<T>() && __ballot(nb[r] == kBlock) == ~0ull) {   // the wavefront's 64 blocks are all full: staged, coalesced stores

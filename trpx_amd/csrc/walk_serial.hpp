@@ -10,7 +10,8 @@ __device__ __forceinline__ uint32_t peek32(const uint32_t* __restrict__ s32, uin
     return (uint32_t)stream_bits([&](uint64_t i) { return ld_stream_dw(s32, i, n_dw); }, abit);
 }
 
-// Walk one frame with one wavefront (kStore = false: count only, widths_f / tile_off_f are not touched).  Returns the frame's total bit count, or ~0ull if the
+// Walk one frame with one wavefront (kStore = false: count only, widths_f / tile_off_f are not touched).  A restated width (an
+// explicit header of the width before, codec_common.hpp) is stored with kWidthRestated set: header_len_flagged.  Returns the frame's total bit count, or ~0ull if the
 // chain runs past `limit_bits` or a width exceeds `max_w` (corrupt stream).
 template <bool kStore = true>
 __device__ uint64_t walk_frame(const uint32_t* __restrict__ s32, uint64_t n_dw, uint64_t frame_abit,
@@ -48,7 +49,7 @@ __device__ uint64_t walk_frame(const uint32_t* __restrict__ s32, uint64_t n_dw, 
             const uint32_t nbv = cb + 1 == g.n_blocks ? nb_last : g.block;
             npos = cpos + hl + (uint64_t)nbv * w;
             nw = w;
-            if constexpr (kStore) widths_f[cb] = (uint8_t)w;
+            if constexpr (kStore) widths_f[cb] = (uint8_t)(w | (w == w_prev && !lane_bad ? kWidthRestated : 0u));
         }
         // position after the frame's last block (a "same" last block may be partial)
         uint64_t fin = 0;
