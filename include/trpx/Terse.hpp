@@ -278,6 +278,52 @@ public:
                                               found, &found, -1), "Terse::prolix_sparse");
     }
 
+    /// Appends row_offsets.size() - 1 frames given as their events in CSR form -- what prolix_sparse returns -- in one device
+    /// call, without building the dense frames (trpx_encode_sparse_host): frame k is size() zeros with px[positions[i]] =
+    /// values[i] for row_offsets[k] <= i < row_offsets[k + 1].  Positions ascend strictly inside a frame and stay below the
+    /// frame size (std::invalid_argument otherwise).  The first push fixes size() -- `size`, or the product of dim() -- and the
+    /// signedness, as push_back does; afterwards the object is what push_back of the dense frames makes of it.
+    template <typename T>
+    void push_back_sparse(std::vector<std::uint64_t> const& row_offsets, std::vector<std::uint32_t> const& positions,
+                          std::vector<T> const& values, std::size_t size = 0) {
+        static_assert(std::is_integral_v<T> && sizeof(T) <= 4, "push_back_sparse: an integer type of at most 32 bits");
+        if (row_offsets.empty() || positions.size() != values.size())
+            throw std::invalid_argument("push_back_sparse: row_offsets [n_frames + 1], positions and values of one length");
+        const std::size_t n_frames = row_offsets.size() - 1;
+        if (n_frames == 0) return;
+        std::size_t n = d_size;
+        if (number_of_frames() == 0) {
+            n = size;
+            if (!n && !d_dim.empty()) { n = 1; for (std::size_t d : d_dim) n *= d; }
+            if (!n) throw std::invalid_argument("push_back_sparse: the first push needs the frame size (size, or dim())");
+        } else {
+            if (size && size != d_size) throw std::invalid_argument("each frame of a multi-Terse object must have the same size");
+            if (d_signed != std::is_signed_v<T>) throw std::invalid_argument("signedness differs from the first frame");
+        }
+        detail::require_abi();
+        const std::size_t cap = trpx_encode_sparse_bound_bytes(detail::dtype_of<T>(), n, n_frames, positions.size(), d_block);
+        if (!cap) throw std::invalid_argument("push_back_sparse: block 12 and frames of < 2^32 values only");
+        const std::size_t prev = d_terse_data.size();
+        d_terse_data.resize(prev + cap);
+        std::size_t total = 0;
+        unsigned pb = 0;
+        std::vector<std::uint64_t> offs(n_frames + 1);
+        const int rc = trpx_encode_sparse_host(detail::dtype_of<T>(), row_offsets.data(), positions.empty() ? nullptr : positions.data(),
+                                               positions.empty() ? nullptr : values.data(), positions.size(), n, n_frames, d_block,
+                                               d_terse_data.data() + prev, cap, &total, offs.data(), &pb, -1);
+        if (rc != TRPX_OK) d_terse_data.resize(prev);
+        detail::check(rc, "Terse::push_back_sparse");
+        f_drop_stack();
+        d_group_states.clear();
+        if (number_of_frames() == 0) {
+            d_size = n;
+            d_signed = std::is_signed_v<T>;
+        }
+        d_terse_data.resize(prev + total);
+        for (std::size_t f = 0; f < n_frames; ++f) d_frame_sizes.push_back(std::size_t(offs[f + 1] - offs[f]));
+        d_prolix_bits = std::max(d_prolix_bits, pb);                              // Terse.hpp:516
+    }
+
     std::size_t size() const { return d_size; }                                   // Terse.hpp:396
     std::size_t number_of_frames() const { return d_frame_sizes.size(); }         // :403
     std::vector<std::size_t> const& dim() const { return d_dim; }                 // :410

@@ -378,6 +378,62 @@ int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes,
                             void* values, size_t capacity, size_t* n_found, int device);
 
 /*
+ * Encode from events: the stream of a stack given in CSR form -- what trpx_decode_sparse writes, what a counting detector or a
+ * hit finder produces --, without a dense frame ever existing in memory.  Frame f is n_values zeros with
+ * px[f][positions[i]] = values[i] for i in [row_offsets[f], row_offsets[f + 1]).  out, frame_offsets, status word 0 and word 1
+ * (prolix_bits) are exactly what trpx_encode leaves for those frames, byte for byte, the zeroed bytes [total, align4(total))
+ * included, bit-identical across runs and launch shapes.  The work is in proportion to events + output bits, never to
+ * n_frames x n_values.
+ *   dtype          the pixel type, TRPX_U8 .. TRPX_I32; `values` has that type
+ *   row_offsets    DEVICE uint64_t[n_frames + 1], 8-byte aligned, non-decreasing: absolute indices into positions / values.
+ *                  [0] need not be 0; [n_frames] <= n_events.  Frames [a, b) of a larger CSR alone: row_offsets + a, n_frames = b - a
+ *   positions      DEVICE uint32_t[n_events]: strictly ascending inside a frame, < n_values
+ *   values         DEVICE T[n_events], aligned to T: anything of the type -- an explicit 0 is a zero pixel, negative values of
+ *                  signed types and the type's minimum are allowed
+ *   n_events       elements of positions / values.  0 with positions = values = NULL is legal: a stack of empty frames (one NULL
+ *                  without the other, or NULL with n_events > 0: TRPX_ERR_INVALID_ARG)
+ *   out, out_capacity, frame_offsets
+ *                  as for trpx_encode (out 16-byte aligned).  A stack that does not fit: status word 0 = TRPX_ERR_CAPACITY,
+ *                  frame_offsets is still complete and valid, nothing at or behind out_capacity is touched; out_capacity ==
+ *                  align4(total) is success.  A sizes-only query passes out = NULL with out_capacity 0.
+ *                  trpx_encode_sparse_bound_bytes() is an upper bound from the event count alone, so that a sparse caller need
+ *                  not allocate n_frames x trpx_worst_case_bytes: a block without events costs 1 bit (4 behind a block with
+ *                  events), a block with events at most 12 + 12 x bits(T) bits, and there are at most n_events of those; a pad
+ *                  byte per frame; clamped to n_frames x trpx_worst_case_bytes and rounded up to 16.  0 for what the call does
+ *                  not support
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  BAD EVENTS ARE DETECTED ON THE DEVICE, ALWAYS: a position >= n_values,
+ *                  two neighbours of one frame not strictly ascending, row_offsets decreasing or ending beyond n_events each set
+ *                  word 0 = TRPX_ERR_INVALID_ARG; out and frame_offsets are then unspecified.  TRPX_ERR_INVALID_ARG wins over
+ *                  TRPX_ERR_CAPACITY when both apply.  This encoder has no waits between tiles: never TRPX_ERR_TIMEOUT
+ *   workspace      DEVICE, 8-byte aligned, trpx_encode_sparse_workspace_bytes(): 16 bytes per 256-block tile + 8 per frame,
+ *                  arithmetic on n_frames and the number of tiles, never proportional to n_values
+ * Whatever the lists hold, nothing outside positions / values [0, n_events) and row_offsets[0 .. n_frames] is read and nothing
+ * outside out[0, out_capacity), frame_offsets[0 .. n_frames], status and the workspace is written: rows are clamped to the
+ * lists, and every scatter is guarded by its own range check.
+ * NO DECODE INDEX IS PRODUCED: it is one byte per block, several times the stream this call writes.  A caller who wants one
+ * runs trpx_build_index on the result.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, n_values >= 2^32 (positions
+ * are 32-bit); TRPX_ERR_INVALID_ARG for an unknown or float dtype, zero sizes, null or misaligned pointers, the NULL / n_events
+ * rule above, out NULL with a capacity; TRPX_ERR_CAPACITY for a workspace that is too small.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the host
+ * from n_frames, n_values and n_events alone, never from the contents of the lists: a captured call is replayed with new events
+ * in the same buffers.
+ * trpx_encode_sparse_host: host row_offsets / positions / values / out; checks its arguments AND the events on the host, before a
+ * device is looked for (TRPX_ERR_INVALID_ARG for the four conditions above), stages, calls trpx_encode_sparse, synchronises;
+ * *total_bytes, frame_offsets (or NULL) and *prolix_bits (or NULL) as trpx_encode_host.
+ */
+size_t trpx_encode_sparse_workspace_bytes(int dtype, size_t n_values, size_t n_frames, unsigned block);
+size_t trpx_encode_sparse_bound_bytes(int dtype, size_t n_values, size_t n_frames, size_t n_events, unsigned block);
+int trpx_encode_sparse(int dtype, const uint64_t* row_offsets, const uint32_t* positions, const void* values,
+                       size_t n_events, size_t n_values, size_t n_frames, unsigned block,
+                       uint8_t* out, size_t out_capacity, uint64_t* frame_offsets, uint32_t* status,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int trpx_encode_sparse_host(int dtype, const uint64_t* row_offsets, const uint32_t* positions, const void* values,
+                            size_t n_events, size_t n_values, size_t n_frames, unsigned block,
+                            uint8_t* out, size_t out_capacity, size_t* total_bytes, uint64_t* frame_offsets,
+                            uint32_t* prolix_bits, int device);
+
+/*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
  * box regenerates exactly the pixels the oracle anchors were computed on.  dtype U16 or I32.
  */

@@ -148,6 +148,56 @@ def encode(pixels: torch.Tensor, out: torch.Tensor | None = None, workspace: Wor
     return Encoded(out, frame_offsets, status, n_values, n_frames, px.dtype, index if index is not None else None, (px, ws, block))
 
 
+def encode_sparse_workspace_bytes(dtype, n_values: int, n_frames: int, block: int = BLOCK) -> int:
+    return lib().trpx_encode_sparse_workspace_bytes(dtype_code(torch_dtype(dtype)), n_values, n_frames, block)
+
+
+def encode_sparse_bound_bytes(dtype, n_values: int, n_frames: int, n_events: int, block: int = BLOCK) -> int:
+    """An upper bound on the stack of ``n_frames`` frames with ``n_events`` events in all (trpx_encode_sparse_bound_bytes)."""
+    return lib().trpx_encode_sparse_bound_bytes(dtype_code(torch_dtype(dtype)), n_values, n_frames, n_events, block)
+
+
+def encode_sparse(row_offsets: torch.Tensor, positions: torch.Tensor | None, values: torch.Tensor | None, n_values: int,
+                  n_frames: int, dtype, out: torch.Tensor | None = None, workspace: Workspace | None = None,
+                  frame_offsets: torch.Tensor | None = None, status: torch.Tensor | None = None, block: int = BLOCK) -> Encoded:
+    """Encode a stack given as its events in CSR form, resident on the GPU (trpx_encode_sparse): frame f is ``n_values`` zeros
+    with ``px[f][positions[i]] = values[i]`` for ``row_offsets[f] <= i < row_offsets[f + 1]`` -- what ``decode_sparse`` returns.
+    The stream is byte for byte what ``encode`` writes for the dense frames; no decode index is produced (``build_index``).
+
+    ``row_offsets``: int64 or uint64 [n_frames + 1]; ``positions``: uint32 / int32; ``values``: of ``dtype``; both ``None`` for a
+    stack of empty frames.  Asynchronous on the current stream; ``Encoded.check()`` (synchronises) raises on status[0]: 1 for
+    bad events (a position out of range, a row not strictly ascending, row_offsets decreasing or beyond the lists), 3 when
+    ``out`` is too small (``out=None`` allocates ``encode_sparse_bound_bytes``)."""
+    tdt = torch_dtype(dtype)
+    code = dtype_code(tdt)
+    dev = row_offsets.device
+    if not row_offsets.is_cuda:
+        raise ValueError("encode_sparse: the events must live on the GPU (use trpx_amd.Terse.push_back_sparse for host data)")
+    if row_offsets.dtype not in (torch.int64, torch.uint64) or row_offsets.numel() < n_frames + 1 or not row_offsets.is_contiguous():
+        raise TypeError(f"encode_sparse: row_offsets must be a contiguous int64 / uint64 tensor of >= {n_frames + 1} elements")
+    if (positions is None) != (values is None):
+        raise ValueError("encode_sparse: positions and values go together")
+    n_events = 0
+    if positions is not None:
+        n_events = positions.numel()
+        if positions.dtype not in (torch.uint32, torch.int32) or values.dtype != tdt or values.numel() != n_events \
+                or not positions.is_contiguous() or not values.is_contiguous() or positions.device != dev or values.device != dev:
+            raise ValueError(f"encode_sparse: positions (uint32) and values ({tdt}) must be contiguous tensors of one length on {dev}")
+    if out is None:
+        out = torch.empty(max(encode_sparse_bound_bytes(tdt, n_values, n_frames, n_events, block), 16), dtype=torch.uint8, device=dev)
+    if frame_offsets is None:
+        frame_offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
+    if status is None:
+        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    ws = (workspace or Workspace(dev)).get(lib().trpx_encode_sparse_workspace_bytes(code, n_values, n_frames, block))
+    with torch.cuda.device(dev):
+        check(lib().trpx_encode_sparse(code, row_offsets.data_ptr(), positions.data_ptr() if n_events else None,
+                                       values.data_ptr() if n_events else None, n_events, n_values, n_frames, block,
+                                       out.data_ptr(), out.numel(), frame_offsets.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), _stream_ptr(row_offsets)))
+    return Encoded(out, frame_offsets, status, n_values, n_frames, tdt)
+
+
 def decode(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype,
            out: torch.Tensor | None = None, workspace: Workspace | None = None,
            status: torch.Tensor | None = None, stream_signed: bool | None = None,

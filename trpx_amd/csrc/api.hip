@@ -18,6 +18,7 @@
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
+#include "sparse_events.hpp"
 
 namespace trpx {
 Profiler& profiler() {
@@ -925,6 +926,86 @@ int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, cons
     return TRPX_OK;
 }
 
+// ---- encode from events (encode_sparse.hip) ----------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// trpx_encode_sparse's workspace: the two-pass encoder's [frame_size u64 x F] [tile_off u64 x F*T] [tile_bits u32 x F*T] and
+// [tile_lo u32 x F*T], the events of the frame in front of every tile: 16 bytes per tile + 8 per frame, nothing per pixel.
+struct SparseEncWs { size_t frame_size, tile_off, tile_bits, tile_lo, total; };
+SparseEncWs sparse_enc_ws(const trpx::FrameGeom& g, size_t n_frames) {
+    SparseEncWs w;
+    const size_t tiles = n_frames * (size_t)g.n_tiles;
+    w.frame_size = 0;
+    w.tile_off = 8 * n_frames;
+    w.tile_bits = w.tile_off + 8 * tiles;
+    w.tile_lo = w.tile_bits + 4 * tiles;
+    w.total = trpx::align_up(w.tile_lo + 4 * tiles, 8);
+    return w;
+}
+// what the call supports at all (the rest is UNSUPPORTED or INVALID_ARG there, 0 in the size queries)
+bool sparse_enc_supported(int dtype, size_t n_values, size_t n_frames, unsigned block, trpx::FrameGeom* g) {
+    return dtype >= TRPX_U8 && dtype <= TRPX_I32 && block == kBlock && n_values < (1ull << 32) && geom_of(n_values, block, g) &&
+           sizes_ok(*g, n_frames);
+}
+// the rule the device-pointer and the host-pointer entry point share: both lists, or neither and no events
+int sparse_enc_inputs(const char* fn, const void* positions, const void* values, size_t n_events) {
+    if ((positions == nullptr) != (values == nullptr)) return fail(TRPX_ERR_INVALID_ARG, "%s: positions and values go together", fn);
+    if (!positions && n_events) return fail(TRPX_ERR_INVALID_ARG, "%s: %zu events without lists", fn, n_events);
+    return TRPX_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t trpx_encode_sparse_workspace_bytes(int dtype, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    if (!sparse_enc_supported(dtype, n_values, n_frames, block, &g)) return 0;
+    return sparse_enc_ws(g, n_frames).total;
+}
+
+size_t trpx_encode_sparse_bound_bytes(int dtype, size_t n_values, size_t n_frames, size_t n_events, unsigned block) {
+    trpx::FrameGeom g;
+    if (!sparse_enc_supported(dtype, n_values, n_frames, block, &g)) return 0;
+    return trpx::sparse_bound_bytes(trpx_dtype_size(dtype), g.n_blocks, n_frames, n_events,               // (derived there)
+                                    (uint64_t)n_frames * trpx_worst_case_bytes(dtype, n_values, block));
+}
+
+int trpx_encode_sparse(int dtype, const uint64_t* row_offsets, const uint32_t* positions, const void* values, size_t n_events,
+                       size_t n_values, size_t n_frames, unsigned block, uint8_t* out, size_t out_capacity, uint64_t* frame_offsets,
+                       uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (!es) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_sparse: unknown dtype %d", dtype);
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode_sparse: block=%u dtype=%d (block 12, containers of <= 32 bits)", block, dtype);
+    if (const int rc = check_args("trpx_encode_sparse", kDtypeFirst, dtype, es, 0, 0, n_values, n_frames, block,
+                                  {{row_offsets, 8}, {frame_offsets, 8}, {status, 8}, {workspace, 8}, {positions, 4, false},
+                                   {values, es, false}, {out, 16, out_capacity != 0}}, &g))
+        return rc;
+    if (n_values >= (1ull << 32)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode_sparse: n_values=%zu (positions are 32-bit)", n_values);
+    if (const int rc = sparse_enc_inputs("trpx_encode_sparse", positions, values, n_events)) return rc;
+    const SparseEncWs w = sparse_enc_ws(g, n_frames);
+    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_encode_sparse: workspace %zu < %zu", workspace_bytes, w.total);
+
+    trpx::fused_ws_forget(workspace, workspace_bytes);
+    char* ws = static_cast<char*>(workspace);
+    trpx::SparseEncodeArgs a{};
+    a.row_offsets = row_offsets;
+    a.positions = positions;
+    a.values = values;
+    a.n_events = n_events;
+    a.geom = g;
+    a.n_frames = (uint32_t)n_frames;
+    a.out = out;
+    a.out_capacity = out_capacity;
+    a.frame_offsets = frame_offsets;
+    a.status = status;
+    a.frame_size = reinterpret_cast<uint64_t*>(ws + w.frame_size);
+    a.tile_off = reinterpret_cast<uint64_t*>(ws + w.tile_off);
+    a.tile_bits = reinterpret_cast<uint32_t*>(ws + w.tile_bits);
+    a.tile_lo = reinterpret_cast<uint32_t*>(ws + w.tile_lo);
+    HIP_TRY(trpx::launch_encode_sparse(dtype, a, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
 // ---- host-pointer convenience wrappers ---------------------------------------------------
 // The callers of the reference's API work frame by frame from host memory (src/terse.cpp:63-69 pushes one image at a
 // time, src/prolix.cpp:69-92 expands one frame at a time): a device allocation per call would cost more than the
@@ -1251,6 +1332,60 @@ int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes,
         HIP_TRY(copy_sync(hs, positions, o + pos_at, 4 * total, hipMemcpyDeviceToHost));
         HIP_TRY(copy_sync(hs, values, o + val_at, es * total, hipMemcpyDeviceToHost));
     }
+    return TRPX_OK;
+}
+
+int trpx_encode_sparse_host(int dtype, const uint64_t* row_offsets, const uint32_t* positions, const void* values, size_t n_events,
+                            size_t n_values, size_t n_frames, unsigned block, uint8_t* out, size_t out_capacity, size_t* total_bytes,
+                            uint64_t* frame_offsets, uint32_t* prolix_bits, int device) {
+    // (the argument and event checks need no device: they come first)
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (!es || !row_offsets || !out || !total_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_sparse_host: bad argument");
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode_sparse_host: block=%u dtype=%d", block, dtype);
+    if (n_values >= (1ull << 32)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_encode_sparse_host: n_values=%zu (positions are 32-bit)", n_values);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_sparse_host: bad sizes");
+    if (const int rc = sparse_enc_inputs("trpx_encode_sparse_host", positions, values, n_events)) return rc;
+    trpx::SparseStaging in_at;
+    if (!trpx::sparse_staging(n_frames, n_events, es, &in_at)) return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_sparse_host: bad n_events %zu", n_events);
+    uint64_t bad_frame = 0, bad_event = 0;
+    if (const char* why = trpx::bad_events(row_offsets, positions, n_events, n_values, n_frames, &bad_frame, &bad_event))
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_encode_sparse_host: %s (frame %llu, event %llu)", why, (unsigned long long)bad_frame,
+                    (unsigned long long)bad_event);
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_encode_sparse_host", device, &hs)) return rc;
+    // the inputs in one device block: [row_offsets] [positions] [values]
+    const size_t pos_at = in_at.pos_at, val_at = in_at.val_at;            // (sparse_events.hpp)
+    const size_t cap = trpx_encode_sparse_bound_bytes(dtype, n_values, n_frames, n_events, block);
+    const size_t ws_bytes = sparse_enc_ws(g, n_frames).total;
+    void *d_in = nullptr, *d_out = nullptr, *d_ws = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
+    Arena& A = arena();
+    HIP_TRY(A.get(Arena::kPixels, in_at.total, &d_in));
+    HIP_TRY(A.get(Arena::kStream, cap, &d_out));
+    HIP_TRY(A.get(Arena::kWorkspace, ws_bytes, &d_ws));
+    int rc = upload_offsets(hs, nullptr, n_frames, 0, &d_off);
+    if (rc || (rc = status_slot(&d_st))) return rc;
+    char* in = static_cast<char*>(d_in);
+    HIP_TRY(copy_sync(hs, in, row_offsets, 8 * (n_frames + 1), hipMemcpyHostToDevice));
+    if (n_events) {
+        HIP_TRY(copy_sync(hs, in + pos_at, positions, 4 * n_events, hipMemcpyHostToDevice));
+        HIP_TRY(copy_sync(hs, in + val_at, values, es * n_events, hipMemcpyHostToDevice));
+    }
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_encode_sparse(dtype, reinterpret_cast<const uint64_t*>(in), n_events ? reinterpret_cast<const uint32_t*>(in + pos_at) : nullptr,
+                            n_events ? in + val_at : nullptr, n_events, n_values, n_frames, block, static_cast<uint8_t*>(d_out), cap, d_off,
+                            d_st, d_ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_encode_sparse_host", st))) return rc;
+    std::vector<uint64_t> offs(n_frames + 1);
+    HIP_TRY(copy_sync(hs, offs.data(), d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
+    const size_t total = (size_t)offs[n_frames];
+    if (total > out_capacity) return fail(TRPX_ERR_CAPACITY, "trpx_encode_sparse_host: need %zu bytes, have %zu", total, out_capacity);
+    HIP_TRY(copy_sync(hs, out, d_out, total, hipMemcpyDeviceToHost));
+    *total_bytes = total;
+    if (frame_offsets) memcpy(frame_offsets, offs.data(), 8 * (n_frames + 1));
+    if (prolix_bits) *prolix_bits = st[1];
     return TRPX_OK;
 }
 

@@ -84,6 +84,25 @@ hipError_t launch_chain_zero(const DecodeArgs& a, uint32_t max_w, bool clear_sta
 hipError_t launch_unpack_tiles(int dtype, const DecodeArgs& a, hipStream_t st, const uint32_t* frame_mode = nullptr);   // frame_mode: only frames with mode 1
 
 hipError_t launch_encode(int dtype, const EncodeArgs& a, hipStream_t st);
+// encode_sparse.hip: the stack from its events in CSR form (trpx_encode_sparse); block = 12, containers of <= 32 bits, n_values < 2^32
+struct SparseEncodeArgs {
+    const uint64_t* row_offsets;   // device, n_frames + 1: absolute indices into positions / values
+    const uint32_t* positions;     // device, n_events (NULL with n_events == 0)
+    const void*     values;        // device, n_events of the pixel type
+    uint64_t        n_events;
+    FrameGeom       geom;
+    uint32_t        n_frames;
+    uint8_t*        out;           // device, compact stack (NULL: sizes only)
+    size_t          out_capacity;
+    uint64_t*       frame_offsets; // device, n_frames + 1
+    uint32_t*       status;        // device, 8 words
+    // workspace carve
+    uint64_t*       frame_size;    // n_frames
+    uint64_t*       tile_off;      // n_frames * n_tiles
+    uint32_t*       tile_bits;     // n_frames * n_tiles
+    uint32_t*       tile_lo;       // n_frames * n_tiles: events of the frame in front of the tile
+};
+hipError_t launch_encode_sparse(int dtype, const SparseEncodeArgs& a, hipStream_t st);
 // any block size (encode.hip, correct-first kernels): geom.block != 12
 hipError_t launch_encode_generic(int dtype, const EncodeArgs& a, hipStream_t st);
 // single-pass encoder (encode_fused.hip); `ws` = fused_workspace_bytes() of descriptor words

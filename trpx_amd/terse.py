@@ -101,6 +101,52 @@ class Terse:
         self._frame_sizes += [int(x) for x in np.diff(offs)]
         self._prolix_bits = max(self._prolix_bits, int(pb.value))   # Terse.hpp:516
 
+    def push_back_sparse(self, row_offsets, positions, values, size: int | None = None) -> None:
+        """Append frames given as their events in CSR form, in ONE GPU call (trpx_encode_sparse_host), without building the
+        dense frames: frame k is ``size()`` zeros with ``px[positions[i]] = values[i]`` for ``row_offsets[k] <= i <
+        row_offsets[k + 1]`` -- what ``prolix_sparse`` returns.  Positions ascend strictly inside a frame (``ValueError``
+        otherwise).  The pixel type is that of ``values``; on the first push the frame size is ``size``, or the product of
+        ``dim()``.  Afterwards the object is what ``push_back_stack`` of the dense frames makes of it."""
+        rows = np.ascontiguousarray(np.asarray(row_offsets), dtype=np.uint64)
+        pos = np.ascontiguousarray(np.asarray(positions), dtype=np.uint32).reshape(-1)
+        val = np.ascontiguousarray(values).reshape(-1)
+        code = _code(val.dtype)
+        n_frames = rows.size - 1
+        if rows.ndim != 1 or n_frames < 0 or pos.size != val.size:
+            raise ValueError("push_back_sparse: row_offsets [n_frames + 1], positions and values of one length")
+        if n_frames == 0:
+            return
+        if self._frame_sizes:
+            if size is not None and int(size) != self._size:
+                raise ValueError("each frame of a multi-Terse object must have the same size")   # Terse.hpp:297
+            if (val.dtype.kind == "i") != self._signed:
+                raise ValueError("signedness differs from the first frame")                      # Terse.hpp:298
+            n = self._size
+        else:
+            n = int(size) if size is not None else int(np.prod(self._dim)) if self._dim else 0
+            if n <= 0:
+                raise ValueError("push_back_sparse: the first push needs the frame size (size=, or dim())")
+        cap = lib().trpx_encode_sparse_bound_bytes(code, n, n_frames, pos.size, self._block)
+        if cap == 0:
+            raise ValueError("push_back_sparse: block 12, pixels of <= 32 bits and frames of < 2^32 values only")
+        out = np.empty(cap, np.uint8)
+        total = C.c_size_t(0)
+        offs = np.empty(n_frames + 1, np.uint64)
+        pb = C.c_uint(0)
+        rc = lib().trpx_encode_sparse_host(code, rows.ctypes.data, pos.ctypes.data if pos.size else None,
+                                           val.ctypes.data if pos.size else None, pos.size, n, n_frames, self._block,
+                                           out.ctypes.data, cap, C.byref(total), offs.ctypes.data, C.byref(pb), self._device)
+        if rc == _lib.ERR_INVALID_ARG:
+            raise ValueError(lib().trpx_last_error_string().decode(errors="replace"))
+        check(rc)
+        if not self._frame_sizes:
+            self._size = n
+            self._signed = val.dtype.kind == "i"
+        self._data += out[: total.value].tobytes()
+        self._group_states = None
+        self._frame_sizes += [int(x) for x in np.diff(offs)]
+        self._prolix_bits = max(self._prolix_bits, int(pb.value))   # Terse.hpp:516
+
     # ---- decode -----------------------------------------------------------------------------
     def prolix(self, out: np.ndarray, frame: int = 0) -> np.ndarray:
         """Unpack frame `frame` into `out` (Terse.hpp:333-341, :352-389).  `out` may have any supported type:
