@@ -55,11 +55,8 @@ bool tuned_type(int stream_signed, int out_dtype) {
     return trpx_dtype_size(out_dtype) && out_dtype <= TRPX_I32 && (stream_signed != 0) == (trpx_dtype_is_signed(out_dtype) != 0);
 }
 uint64_t worst_frame_bits(int dtype, size_t n_values, unsigned block) { return 8 * (uint64_t)trpx_worst_case_bytes(dtype, n_values, block); }
-// frame-relative bit positions are kept in 32 bits (with head room for one step's overshoot)
-bool frame_bits_fit_32(int dtype, size_t n_values, unsigned block) { return worst_frame_bits(dtype, n_values, block) < 0xF0000000ull; }
-// the per-frame decoder packs a block's bit position with its width into 32 bits: frames of < 2^26 bits less the walker's ring
-// offset and one step's overshoot
-bool fits_per_frame_decoder(int dtype, size_t n_values, unsigned block) { return worst_frame_bits(dtype, n_values, block) + (1u << 17) < (1ull << 26); }
+// what the index entry points refuse (the routes' own use of the limit: decode_plan.hpp)
+bool frame_bits_fit_32(int dtype, size_t n_values, unsigned block) { return trpx::frame_bits_fit_32(worst_frame_bits(dtype, n_values, block)); }
 
 bool geom_of(size_t n_values, unsigned block, trpx::FrameGeom* g) {
     if (n_values == 0 || block == 0 || block > kMaxBlock) return false;
@@ -166,15 +163,16 @@ trpx::DecodeArgs decode_args(const uint8_t* terse, size_t terse_bytes, const uin
     a.status = status;
     return a;
 }
-// points a's index (always) and the scratch asked for into an index or workspace block laid out as l
-enum : unsigned { kSeg = 1, kDefer = 2, kParts = 4 };
-void point_into(trpx::DecodeArgs& a, const void* block, const DecLayout& l, unsigned scratch = 0) {
+// points a's index (always) and the scratch a.plan's launches use into an index or workspace block laid out as l: the one
+// place that matches pointers to a plan
+void point_into(trpx::DecodeArgs& a, const void* block, const DecLayout& l) {
     char* b = const_cast<char*>(static_cast<const char*>(block));
+    const unsigned scratch = trpx::plan_scratch(a.plan);
     a.tile_off = reinterpret_cast<uint64_t*>(b + l.tile_off);
     a.widths = reinterpret_cast<uint8_t*>(b + l.widths);
-    if (scratch & kSeg) a.seg_ws = b + l.seg;
-    if (scratch & kDefer) a.defer = reinterpret_cast<uint32_t*>(b + l.defer + trpx::kDeferFront);
-    if (scratch & kParts) {
+    if (scratch & trpx::kSeg) a.seg_ws = b + l.seg;
+    if (scratch & trpx::kDefer) a.defer = reinterpret_cast<uint32_t*>(b + l.defer + trpx::kDeferFront);
+    if (scratch & trpx::kParts) {
         a.parts = reinterpret_cast<trpx::PartDesc*>(b + l.parts);
         a.part_ws = b + l.part_ws;
     }
@@ -187,28 +185,19 @@ int g_encode_path = [] {
     const char* e = getenv("TRPX_ENCODE_PATH");
     return e && strcmp(e, "twopass") == 0 ? 1 : 0;
 }();
-// The decode route, with the values trpx_set_decode_path documents.  Initialised from $TRPX_DECODE_PATH ("basic" / "tiles" /
-// "frames" / "parts"), changed by trpx_set_decode_path().  A forced route is still subject to its preconditions (alignment,
-// block = 12, frame size).  Selector 5 / "dense" is no route: it is kRouteAuto plus a flag of decode_seg.hip (set_dense_route).
-enum DecodeRoute {
-    kRouteAuto = 0,
-    kRouteBasic = 1,     // decode.hip
-    kRouteTiled = 2,     // position-parallel walk + k_unpack_tiles
-    kRouteFrames = 3,    // per-frame decoder for any number of frames
-    kRouteParts = 4,     // large frames by round 4's parts route (two walks) instead of the index route
-};
+// The decode route (trpx::DecodeRoute, decode_plan.hpp).  Initialised from $TRPX_DECODE_PATH ("basic" / "tiles" / "frames" /
+// "parts" / "dense"), changed by trpx_set_decode_path().  Selector 5 / "dense" is kRouteAuto plus g_dense_listed.
+using trpx::kRouteAuto;
 constexpr int kSelectDense = 5;
-DecodeRoute g_decode_path = [] {
+bool g_dense_listed = false;
+trpx::DecodeRoute g_decode_path = [] {
+    using namespace trpx;
     const char* e = getenv("TRPX_DECODE_PATH");
     if (!e) return kRouteAuto;
-    if (strcmp(e, "dense") == 0) trpx::set_dense_route(true);
+    g_dense_listed = strcmp(e, "dense") == 0;
     return strcmp(e, "basic") == 0 ? kRouteBasic : (strcmp(e, "tiles") == 0 || strcmp(e, "seg") == 0) ? kRouteTiled
            : strcmp(e, "frames") == 0 ? kRouteFrames : strcmp(e, "parts") == 0 ? kRouteParts : kRouteAuto;
 }();
-// Large frames (more than 32 K blocks) take the index route -- one walk of many short parts, decode_part.hip -- unless the tiled
-// route is forced (it walks them position-parallel) or round 4's parts route is.  trpx_decode and trpx_build_index must choose
-// alike for the same stack: both ask here.
-bool large_frames_by_index() { return g_decode_path != kRouteTiled && g_decode_path != kRouteParts; }
 // $TRPX_SINGLE_PART = "frames,blocks": stacks of that many frames and more keep frames of up to that many blocks on the per-frame
 // route (launchers.hpp: single_part_blocks; tuning runs -- the built-in rule otherwise)
 [[maybe_unused]] const int g_single_part_env = [] {
@@ -217,6 +206,50 @@ bool large_frames_by_index() { return g_decode_path != kRouteTiled && g_decode_p
     if (e && sscanf(e, "%u,%u", &f, &b) == 2) trpx::set_single_part_rule(f, b);
     return 0;
 }();
+// What a routing decision depends on (decode_plan.hpp), gathered from the call, the selectors above and the kernel files' host
+// functions; the entry points add what only they know.  dtype: the one the worst-case frame is reckoned in.
+trpx::PlanInput plan_input(trpx::Entry entry, int dtype, size_t es, const trpx::FrameGeom& g, size_t n_frames, bool have_offsets = true) {
+    trpx::PlanInput in;
+    in.entry = entry;
+    in.route = g_decode_path;                                                  // trpx_set_decode_path / $TRPX_DECODE_PATH
+    in.dense = g_dense_listed;
+    in.elem_size = es;
+    in.block = g.block;
+    in.n_blocks = g.n_blocks;
+    in.n_frames = n_frames;
+    in.frame_bits = worst_frame_bits(dtype, g.n_values, g.block);
+    in.have_offsets = have_offsets;
+    in.parts_per_frame = trpx::parts_per_frame(g, n_frames);
+    in.chain_parts_per_frame = trpx::chain_parts_per_frame(g, n_frames, es);
+    in.seg_single_wave = trpx::seg_single_wave(g, n_frames);
+#ifdef TRPX_CHAIN_EXTRACT_TILES
+    in.chain_extract = TRPX_CHAIN_EXTRACT_TILES;                               // (make chainextract)
+#endif
+#ifdef TRPX_INDEXED_LARGE_TILES
+    in.indexed_large_tiles = true;
+#endif
+#ifdef TRPX_DIAGNOSTICS
+    static const bool no_defer = getenv("TRPX_NO_DEFER") != nullptr;
+    static const bool lds_walk = getenv("TRPX_WALK") && strcmp(getenv("TRPX_WALK"), "lds") == 0;
+    in.no_defer = no_defer;
+    in.lds_walk = lds_walk;
+#endif
+    return in;
+}
+void misalignment(trpx::PlanInput& in, const trpx::FrameGeom& g, const void* pixels_out) {
+    in.frames_misaligned = (g.n_values * in.elem_size) % 128u != 0u;
+    in.out_misaligned = (uintptr_t)pixels_out % 128u != 0u;
+}
+// the launcher of a plan with an extraction (the converting decoder's apart: it takes the stream's signedness)
+hipError_t launch_planned(int dtype, const trpx::DecodeArgs& a, hipStream_t hs) {
+    using trpx::Extract;
+    switch (a.plan.extract) {
+    case Extract::kBasic: return trpx::launch_decode(dtype, a, hs);
+    case Extract::kTiled: case Extract::kFramesIndexed: case Extract::kUnitsIndexed: return trpx::launch_decode_fast(dtype, a, hs);
+    case Extract::kFrames: case Extract::kParts: case Extract::kChainTiles: case Extract::kChainUnits: return trpx::launch_decode_frames(dtype, a, hs);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 // trpx_decode_indexed's hand-over list (see there): per calling thread, one buffer per (device, stream), grow-only, freed with the thread.
 struct IdxScratch {
@@ -257,19 +290,16 @@ int build_index_impl(int dtype, const uint8_t* terse, size_t terse_bytes, const 
                                   {{terse, 4}, {frame_offsets, 8}, {index, 16}, {status, 8}}, &g))
         return rc;
     if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_build_index: frames of >= 2^32 bits");
+    trpx::PlanInput in = plan_input(trpx::Entry::kBuildIndex, dtype, trpx_dtype_size(dtype), g, n_frames);
+    in.keep_status = !clear_status;
+    in.check_index = check;
     trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, nullptr, status);
-    const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
-    point_into(a, index, il, kSeg | kDefer);
-    // frames of < 2^26 bits: the per-frame decoder's walker writes the index (the conditions of trpx_decode's per-frame route)
-    a.index_per_frame = fits_per_frame_decoder(dtype, n_values, block) && g_decode_path != kRouteTiled;
-    a.parts_per_frame = trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(dtype));
-    a.chain = a.parts_per_frame > 1u && n_frames * (uint64_t)a.parts_per_frame < 0x7FFFFFFFull && large_frames_by_index();
-    if (a.chain) point_into(a, index, il, kParts);
-    else a.parts_per_frame = 1;
-    HIP_TRY(trpx::launch_walk_only(a, (uint32_t)(8 * trpx_dtype_size(dtype)), clear_status, static_cast<hipStream_t>(stream)));
+    a.plan = trpx::plan_decode(in);
+    point_into(a, index, idx_layout(g, n_frames, trpx_dtype_size(dtype)));
+    HIP_TRY(trpx::launch_walk_only(a, (uint32_t)(8 * trpx_dtype_size(dtype)), a.plan.clear_status, static_cast<hipStream_t>(stream)));
     // an index is only good for a stream whose layout follows from its widths: a restated width (valid, written by no encoder
     // here) makes the index CORRUPT here, not pixels wrong in whatever consumes it
-    if (check) HIP_TRY(trpx::launch_check_index(a, static_cast<hipStream_t>(stream)));
+    if (a.plan.check_index) HIP_TRY(trpx::launch_check_index(a, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -403,8 +433,8 @@ size_t trpx_index_bytes(int dtype, size_t n_values, size_t n_frames, unsigned bl
 unsigned trpx_decode_parts_per_frame(int dtype, size_t n_values, size_t n_frames, unsigned block) {
     trpx::FrameGeom g;
     if (!trpx_dtype_size(dtype) || is64(dtype) || block != kBlock || !geom_of(n_values, block, &g)) return 1;
-    return g_decode_path != kRouteParts && frame_bits_fit_32(dtype, n_values, block) ? trpx::chain_parts_per_frame(g, n_frames, trpx_dtype_size(dtype))
-                                                                                   : trpx::parts_per_frame(g, n_frames);
+    // (not always the count trpx_decode then uses: see plan_parts_query)
+    return trpx::plan_parts_query(plan_input(trpx::Entry::kDecode, dtype, trpx_dtype_size(dtype), g, n_frames));
 }
 
 int trpx_encode(int dtype, const void* pixels, size_t n_values, size_t n_frames, unsigned block, uint8_t* out,
@@ -450,46 +480,25 @@ int trpx_decode(int stream_signed, int out_dtype, const uint8_t* terse, size_t t
 
     hipStream_t hs = static_cast<hipStream_t>(stream);
     trpx::fused_ws_forget(workspace, workspace_bytes);      // (an encoder's clean descriptor words in this memory are about to be overwritten)
-    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
+    trpx::PlanInput in = plan_input(trpx::Entry::kDecode, out_dtype, es, g, n_frames, frame_offsets != nullptr);
+    misalignment(in, g, pixels_out);
     char* ws = static_cast<char*>(workspace);
-    a.walk_offsets = reinterpret_cast<uint64_t*>(ws);
-#ifdef TRPX_DIAGNOSTICS
-    static const bool no_defer = getenv("TRPX_NO_DEFER") != nullptr;          // (diagnostic build: the per-frame decoder keeps every frame)
-#else
-    constexpr bool no_defer = false;
-#endif
-    point_into(a, ws, w, no_defer ? kSeg : kSeg | kDefer);
-    const bool basic = g_decode_path == kRouteBasic, force_tiles = g_decode_path == kRouteTiled;   // trpx_set_decode_path / $TRPX_DECODE_PATH
-    const bool bits32 = frame_bits_fit_32(out_dtype, n_values, block);
-    // no offsets: the frames located by trpx_locate_frames' position-parallel route into walk_offsets, its scratch laid over the
-    // regions behind them (nothing the decode writes exists yet), and then the routes a caller with offsets takes.  Elsewhere
-    // (the basic or serial route asked for, other sizes, scratch too small): the decode's own serial walk, launch_decode.
     const uint32_t max_w = 8u * (uint32_t)es;
-    const bool located = !frame_offsets && !basic && bits32 && block == kBlock && trpx::locate_parallel(g, terse_bytes, n_frames, max_w) &&
-                         w.total - w.tile_off >= trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    if (located) {
-        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, a.walk_offsets, status, ws + w.tile_off, hs));
-        a.frame_offsets = frame_offsets = a.walk_offsets;
+    if (!frame_offsets) {
+        // the locator writes into walk_offsets, its scratch laid over the regions behind them (nothing the decode writes exists yet)
+        in.locate_parallel = trpx::locate_parallel(g, terse_bytes, n_frames, max_w);
+        in.locate_fits = w.total - w.tile_off >= trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
     }
-    const bool fast_ok = frame_offsets && !basic && bits32 && block == kBlock;
-    // frames that fit the per-frame decoder: one workgroup per frame, the walk and the extraction overlap inside it -- whatever
-    // the number of frames (since the round-3 walker a single 512^2 frame takes 0.10 ms this way against 0.24 ms through the
-    // position-parallel walk + tiled extraction, eight 1024^2 frames 0.37 against 0.73 ms); larger frames: the tiled kernels
-    const bool frame26 = fits_per_frame_decoder(out_dtype, n_values, block);
-    // larger frames, or frames of more than 32 K blocks: cut into parts of the size of a 512 x 512 frame first (decode_part.hip);
-    // a part's positions are relative to its own first bit, so the 2^26 limit applies to the part
-    a.chain = large_frames_by_index() && bits32;                               // (frame-relative 32-bit positions)
-    a.parts_per_frame = a.chain ? trpx::chain_parts_per_frame(g, n_frames, es) : trpx::parts_per_frame(g, n_frames);
-    const bool parts_ok = a.parts_per_frame > 1u && n_frames * (uint64_t)a.parts_per_frame < 0x7FFFFFFFull && a.defer;
-    if (parts_ok) point_into(a, ws, w, kParts);
-    else a.parts_per_frame = 1;
-    if (fast_ok && (parts_ok || (frame26 && trpx::parts_per_frame(g, n_frames) == 1u)) && !force_tiles)
-        HIP_TRY(trpx::launch_decode_frames(out_dtype, a, hs));
-    else if (fast_ok)
-        HIP_TRY(trpx::launch_decode_fast(out_dtype, a, false, hs));
-    else
-        HIP_TRY(trpx::launch_decode(out_dtype, a, frame_offsets != nullptr, hs));
-    if (located)                                                               // (the decode cleared the status: the locate's verdict again)
+    trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
+    a.plan = trpx::plan_decode(in);
+    a.walk_offsets = reinterpret_cast<uint64_t*>(ws);
+    point_into(a, ws, w);
+    if (a.plan.locate) {
+        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, max_w, a.walk_offsets, status, ws + w.tile_off, hs));
+        a.frame_offsets = a.walk_offsets;
+    }
+    HIP_TRY(launch_planned(out_dtype, a, hs));
+    if (a.plan.locate)                                                         // (the decode cleared the status: the locate's verdict again)
         HIP_TRY(trpx::launch_locate_status(a.walk_offsets, (uint32_t)n_frames, status, hs));
     return TRPX_OK;
 }
@@ -508,32 +517,23 @@ int trpx_decode_indexed(int stream_signed, int out_dtype, const uint8_t* terse, 
                                   n_values, n_frames, block, {{terse, 4}, {index, 16}, {frame_offsets, 8}, {pixels_out, es}, {status, 8}}, &g))
         return rc;
     hipStream_t hs = static_cast<hipStream_t>(stream);
+    trpx::PlanInput in = plan_input(trpx::Entry::kIndexed, out_dtype, es, g, n_frames);
+    misalignment(in, g, pixels_out);
     trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
+    a.plan = trpx::plan_decode(in);
     point_into(a, index, idx_layout(g, n_frames, es));
-    // a thousand frames and more: one workgroup per frame; fewer: the tiled kernel spreads a frame's tiles over the whole GPU
-    // (512^2 u16 frames, tiled / per-frame: 128 frames 0.023 / 0.121 ms, 600 frames 0.092 / 0.137, 1000 frames 0.148 / 0.142, 2000
-    // frames 0.30 / 0.21 -- both scale with the blocks per frame, so the frame count alone decides)
-    const bool per_frame = fits_per_frame_decoder(out_dtype, n_values, block) && g_decode_path != kRouteTiled &&
-                           (g_decode_path == kRouteFrames || n_frames >= 1024);
-    // Frames that start inside a cache line (513 x 511 u16: most detectors): the indexed extraction's 16-byte stores are then
-    // misaligned and it LOSES to the walking decoder, whose extraction waves write line images (2000 frames: 0.33 against 0.27 ms).
-    // Such stacks take the walking decoder, and the frames it hands over -- header-dense ones, where the walk is what costs --
-    // are extracted with the caller's index instead of being walked position-parallel: never slower than trpx_decode.  The
-    // hand-over list needs a few KB of scratch, which this entry point has no argument for: one grow-only buffer per calling
-    // thread, device and stream (calls on one stream are ordered; a call that is being captured into a graph takes the plain indexed
-    // route: a graph would keep the buffer's address, and a later, larger call frees it).
-    const bool misaligned = (g.n_values * es) % 128u != 0u || (uintptr_t)pixels_out % 128u != 0u;
-    if (per_frame && misaligned && g_decode_path == kRouteAuto && trpx::parts_per_frame(g, n_frames) == 1u) {
+    if (a.plan.extract == trpx::Extract::kFrames) {
+        // The walking decoder's hand-over list needs a few KB of scratch, which this entry point has no argument for: one grow-only
+        // buffer per calling thread, device and stream (calls on one stream are ordered; a call that is being captured into a graph
+        // takes the plain indexed route: a graph would keep the buffer's address, and a later, larger call frees it).
         void* scratch = indexed_scratch(trpx::defer_bytes(n_frames), hs);
-        if (scratch) {
-            a.defer = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + trpx::kDeferFront);
-            a.seg_ws = scratch;                                               // (not used: no walk of the listed frames)
-            a.index_given = true;
-            HIP_TRY(trpx::launch_decode_frames(out_dtype, a, hs));
-            return TRPX_OK;
+        if (scratch) a.defer = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + trpx::kDeferFront);
+        else {
+            in.indexed_scratch = false;
+            a.plan = trpx::plan_decode(in);
         }
     }
-    HIP_TRY(trpx::launch_decode_fast(out_dtype, a, true, hs, per_frame));
+    HIP_TRY(launch_planned(out_dtype, a, hs));
     return TRPX_OK;
 }
 
@@ -581,9 +581,10 @@ int trpx_decode_convert(int stream_signed, int out_dtype, const uint8_t* terse, 
     if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_convert: workspace %zu < %zu", workspace_bytes, w.total);
     trpx::fused_ws_forget(workspace, workspace_bytes);
     trpx::DecodeArgs a = decode_args(terse, terse_bytes, frame_offsets, g, n_frames, pixels_out, status);
+    a.plan = trpx::plan_decode(plan_input(trpx::Entry::kConvert, out_dtype, es, g, n_frames, frame_offsets != nullptr));
     a.walk_offsets = static_cast<uint64_t*>(workspace);
-    point_into(a, workspace, w, kSeg);
-    HIP_TRY(trpx::launch_decode_convert(out_dtype, a, stream_signed != 0, frame_offsets != nullptr, static_cast<hipStream_t>(stream)));
+    point_into(a, workspace, w);
+    HIP_TRY(trpx::launch_decode_convert(out_dtype, a, stream_signed != 0, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -600,8 +601,8 @@ int trpx_set_encode_path(int path) {
 
 int trpx_set_decode_path(int path) {
     if (path < kRouteAuto || path > kSelectDense) return fail(TRPX_ERR_INVALID_ARG, "trpx_set_decode_path: 0 = auto, 1 = basic, 2 = tiled, 3 = per-frame, 4 = parts route for large frames, 5 = auto with the dense walk for listed frames");
-    trpx::set_dense_route(path == kSelectDense);
-    g_decode_path = path == kSelectDense ? kRouteAuto : static_cast<DecodeRoute>(path);
+    g_dense_listed = path == kSelectDense;
+    g_decode_path = path == kSelectDense ? kRouteAuto : static_cast<trpx::DecodeRoute>(path);
     return TRPX_OK;
 }
 

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void k_unpack_g(const uint8_t* __restrict
 }
 
 template <typename T>
-static hipError_t launch_decode_t(const DecodeArgs& a, bool have_offsets, hipStream_t st) {
+static hipError_t launch_decode_t(const DecodeArgs& a, hipStream_t st) {
     const FrameGeom g = a.geom;
     const uint64_t n_tiles_total = (uint64_t)a.n_frames * g.n_tiles;
     const bool vec = (g.n_values % 4 == 0) && ((uintptr_t)a.pixels_out % 16 == 0);
@@ -203,7 +203,7 @@ static hipError_t launch_decode_t(const DecodeArgs& a, bool have_offsets, hipStr
     Profiler& prof = profiler();
     prof.begin();
     prof.mark(st);
-    if (have_offsets) {
+    if (a.plan.walk == Walk::kHeaders) {
         hipLaunchKernelGGL(k_walk, dim3(a.n_frames), dim3(kWave), 0, st, a.terse, (uint64_t)a.terse_bytes, offs, g,
                            max_w, a.widths, a.tile_off, a.status);
     } else {
@@ -232,8 +232,8 @@ hipError_t launch_walk_serial(const DecodeArgs& a, uint32_t max_w, hipStream_t s
     return hipGetLastError();
 }
 
-hipError_t launch_decode(int dtype, const DecodeArgs& a, bool have_offsets, hipStream_t st) {
-    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_t<T>(a, have_offsets, st); });
+hipError_t launch_decode(int dtype, const DecodeArgs& a, hipStream_t st) {
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_t<T>(a, st); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -307,11 +307,11 @@ __global__ __launch_bounds__(kThreads) void k_unpack_conv(const uint8_t* __restr
 }
 
 template <typename OutT>
-static hipError_t launch_decode_convert_t(const DecodeArgs& a, int stream_signed, bool have_offsets, hipStream_t st) {
+static hipError_t launch_decode_convert_t(const DecodeArgs& a, int stream_signed, hipStream_t st) {
     const FrameGeom g = a.geom;
     zero_status(a.status, st);
     const uint64_t* offs = a.frame_offsets;
-    if (have_offsets) {
+    if (a.plan.walk == Walk::kHeaders) {
         hipLaunchKernelGGL(k_walk, dim3(a.n_frames), dim3(kWave), 0, st, a.terse, (uint64_t)a.terse_bytes, offs, g, 64u,
                            a.widths, a.tile_off, a.status);
     } else {
@@ -326,13 +326,13 @@ static hipError_t launch_decode_convert_t(const DecodeArgs& a, int stream_signed
 }
 
 // dtype: the OUTPUT type -- the six 8/16/32-bit integral pixel types, float, double, uint64 / int64
-hipError_t launch_decode_convert(int dtype, const DecodeArgs& a, int stream_signed, bool have_offsets, hipStream_t st) {
+hipError_t launch_decode_convert(int dtype, const DecodeArgs& a, int stream_signed, hipStream_t st) {
     switch (dtype) {
-    default: return for_pixel_type(dtype, [&]<class T>() { return launch_decode_convert_t<T>(a, stream_signed, have_offsets, st); });
-    case TRPX_F32: return launch_decode_convert_t<float>(a, stream_signed, have_offsets, st);
-    case TRPX_F64: return launch_decode_convert_t<double>(a, stream_signed, have_offsets, st);
-    case TRPX_U64: return launch_decode_convert_t<uint64_t>(a, stream_signed, have_offsets, st);
-    case TRPX_I64: return launch_decode_convert_t<int64_t>(a, stream_signed, have_offsets, st);
+    default: return for_pixel_type(dtype, [&]<class T>() { return launch_decode_convert_t<T>(a, stream_signed, st); });
+    case TRPX_F32: return launch_decode_convert_t<float>(a, stream_signed, st);
+    case TRPX_F64: return launch_decode_convert_t<double>(a, stream_signed, st);
+    case TRPX_U64: return launch_decode_convert_t<uint64_t>(a, stream_signed, st);
+    case TRPX_I64: return launch_decode_convert_t<int64_t>(a, stream_signed, st);
     }
 }
 

@@ -190,38 +190,30 @@ hipError_t launch_walk_groups(const DecodeArgs& a, uint32_t max_w, const uint64_
 }
 
 template <typename T>
-static hipError_t launch_decode_fast_t(const DecodeArgs& a, bool have_index, bool per_frame, hipStream_t st) {
+static hipError_t launch_decode_fast_t(const DecodeArgs& a, hipStream_t st) {
     const FrameGeom g = a.geom;
     constexpr uint32_t tb = unpack_sub_tiles<T>() * kThreads;
     const uint32_t tpf = (g.n_blocks + tb - 1) / tb;
-    const uint32_t max_w = PixelTraits<T>::bits;
     zero_status(a.status, st);
     Profiler& prof = profiler();
     prof.begin();
     prof.mark(st);
-    if (!have_index) {
-        const hipError_t e = launch_walk_only(a, max_w, false, st);
+    if (a.plan.walk != Walk::kCallers) {
+        const hipError_t e = launch_walk_only(a, PixelTraits<T>::bits, false, st);
         if (e != hipSuccess) return e;
     }
     prof.mark(st);
-    if (have_index && per_frame) {                              // many small frames: the per-frame decoder with the widths given
-        const hipError_t e = launch_decode_frames_indexed(PixelTraits<T>::dtype, a, nullptr, st);
-        prof.mark(st);
-        return e;
-    }
-#ifndef TRPX_INDEXED_LARGE_TILES
-    if (have_index && sizeof(T) < 4 && g.n_blocks >= (1u << 18) &&
-        8 * (uint64_t)g.n_blocks * (12u + 12u * max_w) < (1ull << 31)) {   // large frames of 8/16-bit pixels with their index: units of the per-frame decoder, as the index route extracts them (decode_frame.hip)
-        const hipError_t e = launch_decode_units_indexed(PixelTraits<T>::dtype, a, st, nullptr);
-        prof.mark(st);
-        return e;
-    }
-#endif
-    hipLaunchKernelGGL((k_unpack_tiles<T>), dim3((uint32_t)((uint64_t)a.n_frames * tpf)), dim3(kThreads), 0, st, a.terse,
-                       (uint64_t)a.terse_bytes, a.frame_offsets, g, tpf, a.widths, a.tile_off,
-                       static_cast<T*>(a.pixels_out), a.status, static_cast<const uint32_t*>(nullptr));
+    hipError_t e = hipErrorInvalidValue;
+    if (a.plan.extract == Extract::kFramesIndexed)              // many small frames: the per-frame decoder with the widths given
+        e = launch_decode_frames_indexed(PixelTraits<T>::dtype, a, nullptr, st);
+    else if (a.plan.extract == Extract::kUnitsIndexed)          // large frames of 8/16-bit pixels with their index: as the index route extracts them (decode_frame.hip)
+        e = launch_decode_units_indexed(PixelTraits<T>::dtype, a, st, nullptr);
+    else if (a.plan.extract == Extract::kTiled)
+        hipLaunchKernelGGL((k_unpack_tiles<T>), dim3((uint32_t)((uint64_t)a.n_frames * tpf)), dim3(kThreads), 0, st, a.terse,
+                           (uint64_t)a.terse_bytes, a.frame_offsets, g, tpf, a.widths, a.tile_off,
+                           static_cast<T*>(a.pixels_out), a.status, static_cast<const uint32_t*>(nullptr));
     prof.mark(st);
-    return hipGetLastError();
+    return a.plan.extract == Extract::kTiled ? hipGetLastError() : e;
 }
 
 template <typename T>
@@ -240,27 +232,23 @@ hipError_t launch_walk_lds_only(const DecodeArgs& a, uint32_t max_w, const uint3
 
 // Fast path preconditions (checked by the caller): block = 12, frame offsets known, frames of < 2^32 bits (T-aligned pointers, any pixel count).
 hipError_t launch_walk_only(const DecodeArgs& a, uint32_t max_w, bool clear_status, hipStream_t st) {
-    // the position-parallel walk; diagnostic builds: TRPX_WALK = lds keeps the one-wavefront-per-frame walk (A/B checks)
-#ifdef TRPX_DIAGNOSTICS
-    static const bool lds_walk = getenv("TRPX_WALK") && strcmp(getenv("TRPX_WALK"), "lds") == 0;
-#else
-    constexpr bool lds_walk = false;
-#endif
-    if (!lds_walk && a.seg_ws && a.chain && a.parts && a.defer) {
-        // large frames: one walk of many short parts writes the index (every frame through k_chain_index: narrow = false); the
+    if (a.plan.walk == Walk::kChain) {
+        // large frames: one walk of many short parts writes the index (every frame through k_chain_index: not narrow); the
         // frames where that does not work out are listed and get theirs from the position-parallel walk
         hipError_t e = launch_chain_zero(a, max_w, clear_status, st);
         if (e != hipSuccess) return e;
         const uint32_t* mode = nullptr;
-        e = launch_build_index_chain(a, max_w, false, &mode, st);
+        e = launch_build_index_chain(a, max_w, &mode, st);
         if (e != hipSuccess) return e;
         return launch_seg_listed(a, max_w, st);
     }
     if (clear_status) zero_status(a.status, st);
-    if (!lds_walk && a.seg_ws && a.index_per_frame && a.defer)
-        return launch_index_frames(max_w, a, false, st);        // (status cleared above if asked)
-    if (!lds_walk && a.seg_ws) return launch_seg_walk(a, max_w, st);
-    return launch_walk_lds_only(a, max_w, nullptr, st);
+    switch (a.plan.walk) {
+    case Walk::kFrames: return launch_index_frames(max_w, a, false, st);        // (status cleared above if asked)
+    case Walk::kSeg: return launch_seg_walk(a, max_w, st);
+    case Walk::kLds: return launch_walk_lds_only(a, max_w, nullptr, st);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_walk_lds_only(const DecodeArgs& a, uint32_t max_w, const uint32_t* only, hipStream_t st, const uint32_t* list) {
@@ -269,8 +257,8 @@ hipError_t launch_walk_lds_only(const DecodeArgs& a, uint32_t max_w, const uint3
     return hipGetLastError();
 }
 
-hipError_t launch_decode_fast(int dtype, const DecodeArgs& a, bool have_index, hipStream_t st, bool per_frame) {
-    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_fast_t<T>(a, have_index, per_frame, st); });
+hipError_t launch_decode_fast(int dtype, const DecodeArgs& a, hipStream_t st) {
+    return for_pixel_type(dtype, [&]<class T>() { return launch_decode_fast_t<T>(a, st); });
 }
 
 }  // namespace trpx

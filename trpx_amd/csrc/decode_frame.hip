@@ -826,15 +826,13 @@ __global__ __launch_bounds__(kFrameThreads, sizeof(T) == 4 ? 6 : 8) void k_index
 hipError_t launch_index_frames(uint32_t max_w, const DecodeArgs& a, bool clear_status, hipStream_t st) {
     hipLaunchKernelGGL(k_zero_words<0>, dim3(1), dim3(kThreads), 0, st, reinterpret_cast<uint64_t*>(a.defer) - kDeferSlots * kDeferSlotWords,
                        (uint64_t)(kDeferSlots * kDeferSlotWords + 1), reinterpret_cast<uint64_t*>(a.status), (uint64_t)(clear_status ? 4 : 0));
-    if (max_w <= 8u)
-        hipLaunchKernelGGL((k_index_frames<uint8_t>), dim3(a.n_frames), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
+    const auto walk = [&]<class T>() {
+        hipLaunchKernelGGL((k_index_frames<T>), dim3(a.n_frames), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
                            a.frame_offsets, a.geom, a.widths, a.tile_off, a.defer, a.status);
-    else if (max_w <= 16u)
-        hipLaunchKernelGGL((k_index_frames<uint16_t>), dim3(a.n_frames), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
-                           a.frame_offsets, a.geom, a.widths, a.tile_off, a.defer, a.status);
-    else
-        hipLaunchKernelGGL((k_index_frames<uint32_t>), dim3(a.n_frames), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
-                           a.frame_offsets, a.geom, a.widths, a.tile_off, a.defer, a.status);
+    };
+    if (max_w <= 8u) walk.template operator()<uint8_t>();
+    else if (max_w <= 16u) walk.template operator()<uint16_t>();
+    else walk.template operator()<uint32_t>();
     return launch_seg_listed(a, max_w, st);
 }
 
@@ -865,10 +863,10 @@ hipError_t launch_decode_frames_indexed(int dtype, const DecodeArgs& a, const ui
 
 template <typename T>
 static hipError_t launch_decode_frames_t(const DecodeArgs& a, hipStream_t st) {
-    uint32_t* defer = a.defer && a.seg_ws ? a.defer : nullptr;
-    const bool chain = a.chain && a.parts && a.parts_per_frame > 1u;
+    const DecodePlan& p = a.plan;
+    const bool chain = p.walk == Walk::kChain;
+    uint32_t* defer = p.defer ? a.defer : nullptr;
     if (chain) {                                                              // (the same words and the index route's own, in one launch)
-        if (!defer) return hipErrorInvalidValue;
         const hipError_t e = launch_chain_zero(a, (uint32_t)PixelTraits<T>::bits, true, st);
         if (e != hipSuccess) return e;
     } else
@@ -883,40 +881,33 @@ static hipError_t launch_decode_frames_t(const DecodeArgs& a, hipStream_t st) {
         // Large frames by the index route (decode_part.hip): one walk of many short parts writes the decode index, the frames
         // where that does not work out are listed and get theirs from the position-parallel walk, then every frame's tiles are
         // extracted with the widths given.
-        if (!defer) return hipErrorInvalidValue;
         constexpr int dt = PixelTraits<T>::dtype;
-        constexpr bool narrow = sizeof(T) < 4;
         const uint32_t* frame_mode = nullptr;
-        hipError_t e = launch_build_index_chain(a, (uint32_t)PixelTraits<T>::bits, narrow, &frame_mode, st);
+        hipError_t e = launch_build_index_chain(a, (uint32_t)PixelTraits<T>::bits, &frame_mode, st);
         if (e != hipSuccess) return e;
         prof.mark(st);
         e = launch_seg_listed(a, (uint32_t)PixelTraits<T>::bits, st);
         if (e != hipSuccess) return e;
-        // (the tiled kernel, or units of the per-frame decoder with the widths given: eight 4096^2 int32 frames 0.406 / 0.444 ms,
-        // 200 x (1030 x 1065) u16 0.246 / 0.268, 128 x 2048^2 u16 0.594 / 0.554 -- tools/r5_ab.sh xtiles / xunits)
-#ifdef TRPX_CHAIN_EXTRACT_TILES
-        const bool tiles = TRPX_CHAIN_EXTRACT_TILES != 0;
-#else
-        const bool tiles = sizeof(T) == 4 || a.geom.n_blocks < (1u << 18);
-#endif
-        e = tiles ? launch_unpack_tiles(dt, a, st, narrow ? frame_mode : nullptr) : launch_decode_units_indexed(dt, a, st, narrow ? frame_mode : nullptr);
+        if (!p.narrow) frame_mode = nullptr;
+        e = p.extract == Extract::kChainTiles ? launch_unpack_tiles(dt, a, st, frame_mode) : launch_decode_units_indexed(dt, a, st, frame_mode);
         if (e != hipSuccess) return e;
-        if constexpr (narrow)                                                 // frames with few explicit headers: part by part, walker + extraction fused
-            hipLaunchKernelGGL((k_decode_parts<T>), dim3(a.n_frames * a.parts_per_frame), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
+        if (p.narrow)                                                         // frames with few explicit headers: part by part, walker + extraction fused
+            hipLaunchKernelGGL((k_decode_parts<T>), dim3(a.n_frames * p.parts_per_frame), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
                                a.frame_offsets, a.geom, static_cast<T*>(a.pixels_out), a.status, static_cast<const PartDesc*>(a.parts), frame_mode);
         prof.mark(st);
         return hipGetLastError();
-    } else if (a.parts && a.parts_per_frame > 1u) {
+    } else if (p.extract == Extract::kParts) {
         // Large frames: cut into parts first (decode_part.hip: a walk-only pass from guessed states inside runs of equal widths,
         // verified link by link); frames whose parts cannot be established -- no runs to start from: header-dense data -- are
         // listed in a.defer as whole frames and take the position-parallel walk + tiled extraction below.
-        if (!defer) return hipErrorInvalidValue;
         const hipError_t e = launch_build_parts(a, (uint32_t)PixelTraits<T>::bits, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_decode_parts<T>), dim3(a.n_frames * a.parts_per_frame), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
+        hipLaunchKernelGGL((k_decode_parts<T>), dim3(a.n_frames * p.parts_per_frame), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
                            a.frame_offsets, a.geom, static_cast<T*>(a.pixels_out), a.status, static_cast<const PartDesc*>(a.parts),
                            static_cast<const uint32_t*>(nullptr));
-    } else if ((a.geom.n_values * sizeof(T)) % 128u == 0u && (uintptr_t)a.pixels_out % 128u == 0u)   // every frame starts a cache line
+    } else if (p.extract != Extract::kFrames)
+        return hipErrorInvalidValue;
+    else if (!p.misaligned)                                                   // every frame starts a cache line
         hipLaunchKernelGGL((k_decode_frames<T, false>), dim3(a.n_frames), dim3(kFrameThreads), 0, st, a.terse, (uint64_t)a.terse_bytes,
                            a.frame_offsets, a.geom, static_cast<T*>(a.pixels_out), defer, a.status);
     else

@@ -947,7 +947,7 @@ __global__ __launch_bounds__(kWave) void k_part_resolve(const PartState* __restr
 }
 
 hipError_t launch_build_parts(const DecodeArgs& a, uint32_t max_w, hipStream_t st) {
-    const uint32_t P = a.parts_per_frame;
+    const uint32_t P = a.plan.parts_per_frame;
     if (P < 2u || !a.parts || !a.part_ws || !a.defer) return hipErrorInvalidValue;
     const PartWs l = part_ws_layout(a.n_frames, P);
     char* ws = static_cast<char*>(a.part_ws);
@@ -1726,7 +1726,7 @@ __global__ __launch_bounds__(kThreads) void k_chain_zero(uint64_t* __restrict__ 
 }
 hipError_t launch_chain_zero(const DecodeArgs& a, uint32_t max_w, bool clear_status, hipStream_t st) {
     (void)max_w;
-    const uint32_t P = a.parts_per_frame;
+    const uint32_t P = a.plan.parts_per_frame;
     if (P < 4u || !a.part_ws || !a.defer) return hipErrorInvalidValue;
     const ChainWs l = chain_ws_layout(a.geom, a.n_frames, P);
     const uint64_t k = l.cks / 8;
@@ -1738,8 +1738,8 @@ hipError_t launch_chain_zero(const DecodeArgs& a, uint32_t max_w, bool clear_sta
 
 // Fills a.widths / a.tile_off for every frame that works out and lists the others in a.defer.  The caller has cleared the route's
 // words (launch_chain_zero) earlier on the stream.
-hipError_t launch_build_index_chain(const DecodeArgs& a, uint32_t max_w, bool narrow, const uint32_t** frame_mode, hipStream_t st) {
-    const uint32_t P = a.parts_per_frame;
+hipError_t launch_build_index_chain(const DecodeArgs& a, uint32_t max_w, const uint32_t** frame_mode, hipStream_t st) {
+    const uint32_t P = a.plan.parts_per_frame;
     if (P < 4u || !a.parts || !a.part_ws || !a.defer) return hipErrorInvalidValue;
     const ChainWs l = chain_ws_layout(a.geom, a.n_frames, P);
     char* ws = static_cast<char*>(a.part_ws);
@@ -1755,7 +1755,7 @@ hipError_t launch_build_index_chain(const DecodeArgs& a, uint32_t max_w, bool na
     hipLaunchKernelGGL(k_chain_walk, dim3(a.n_frames * P), dim3(kWave), 0, st, a.terse, (uint64_t)a.terse_bytes, a.frame_offsets, max_w, P, cap,
                        states, walks, cks, ents, fixes, fixents, vote_words, a.status);
     hipLaunchKernelGGL(k_chain_resolve, dim3(a.n_frames), dim3(kWave), 0, st, static_cast<const PartWalk*>(walks),
-                       static_cast<const ChainFix*>(fixes), a.geom, P, narrow ? 1u : 0u, a.parts, modes, a.defer, a.status);
+                       static_cast<const ChainFix*>(fixes), a.geom, P, a.plan.narrow ? 1u : 0u, a.parts, modes, a.defer, a.status);
     hipLaunchKernelGGL(k_chain_index, dim3(a.n_frames * P), dim3(kWave), 0, st, a.terse, (uint64_t)a.terse_bytes, a.frame_offsets, a.geom,
                        max_w, P, cap, a.parts, ents, static_cast<const ChainFix*>(fixes), static_cast<const uint8_t*>(fixents), a.widths,
                        a.tile_off, modes, a.defer, a.status);

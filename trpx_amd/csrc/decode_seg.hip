@@ -736,8 +736,6 @@ size_t seg_workspace_bytes(const FrameGeom& g, size_t n_frames) {
     // behind the segment states: the scratch of the listed frames' dense walk (decode_dense.hip; frames of one wavefront's worth here)
     return seg_state_bytes(g, n_frames) + (seg_waves_per_frame(g, n_frames) == 1 ? dense_workspace_bytes(g, n_frames) : 0);
 }
-static bool g_dense_route = false;   // (off: measured slower than the rounds on Poisson(3) counts, see LABNOTES round 6; trpx_set_decode_path(5) / TRPX_DECODE_PATH=dense)
-void set_dense_route(bool on) { g_dense_route = on; }
 
 hipError_t launch_walk_lds_only(const DecodeArgs& a, uint32_t max_w, const uint32_t* only, hipStream_t st, const uint32_t* list = nullptr);   // decode_fast.hip
 
@@ -820,7 +818,7 @@ hipError_t launch_seg_walk(const DecodeArgs& a, uint32_t max_w, hipStream_t st) 
 hipError_t launch_seg_listed(const DecodeArgs& a, uint32_t max_w, hipStream_t st) {
     const uint32_t K = seg_waves_per_frame(a.geom, a.n_frames);
     if (K > 1) return launch_seg_multi(a, max_w, K, static_cast<const uint32_t*>(a.defer), st);
-    if (g_dense_route)
+    if (a.plan.dense)   // (off by default: measured slower than the rounds on Poisson(3) counts, see LABNOTES round 6; trpx_set_decode_path(5) / TRPX_DECODE_PATH=dense)
         return launch_dense_listed(a, max_w, static_cast<char*>(a.seg_ws) + seg_state_bytes(a.geom, a.n_frames), static_cast<const uint32_t*>(a.defer), st);
     const SegWs ws = seg_carve(a.seg_ws, a.n_frames, 1u);
     hipLaunchKernelGGL(k_seg_listed, dim3((a.n_frames + kSegWgWaves - 1) / kSegWgWaves), dim3(kWave * kSegWgWaves), 0, st, a.terse, (uint64_t)a.terse_bytes, a.frame_offsets,
@@ -830,11 +828,11 @@ hipError_t launch_seg_listed(const DecodeArgs& a, uint32_t max_w, hipStream_t st
 
 template <typename T>
 static hipError_t launch_decode_deferred_t(const DecodeArgs& a, hipStream_t st) {
-    if (!a.index_given) {                                                   // (trpx_decode_indexed on frames that start inside a cache line: the index is the caller's)
+    if (a.plan.walk != Walk::kCallers) {                                    // (trpx_decode_indexed on frames that start inside a cache line: the index is the caller's)
         const hipError_t e0 = launch_seg_listed(a, (uint32_t)PixelTraits<T>::bits, st);
         if (e0 != hipSuccess) return e0;
     }
-    if (seg_waves_per_frame(a.geom, a.n_frames) > 1u) {                     // large frames: their tiles, spread over the GPU
+    if (a.plan.listed_tiles) {                                              // large frames: their tiles, spread over the GPU
         constexpr uint32_t tb = unpack_sub_tiles<T>() * kThreads;
         const uint64_t tiles = (uint64_t)a.n_frames * ((a.geom.n_blocks + tb - 1) / tb);
         hipLaunchKernelGGL((k_unpack_listed<T>), dim3((uint32_t)(tiles < 1024 ? tiles : 1024)), dim3(kThreads), 0, st, a.terse,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "codec_common.hpp"
+#include "decode_plan.hpp"
 
 namespace trpx {
 
@@ -58,13 +59,10 @@ struct DecodeArgs {
     uint64_t*       walk_offsets;  // n_frames + 1 : frame offsets produced by the serial walk
     uint32_t*       defer;         // 2 + n_frames words, 8-byte aligned (may be null): [0] = count, [1 + i] = frames the per-frame decoder hands to the position-parallel path
     void*           seg_ws;        // seg_workspace_bytes(): segment states of the position-parallel walk (decode_seg.hip)
-    bool            index_per_frame = false;   // launch_walk_only: many small frames, use the per-frame walker (launch_index_frames)
     // frames of more than kPartMaxBlocks blocks on the per-frame route: the part table and the scratch of its construction
-    PartDesc*       parts = nullptr;           // n_frames * parts_per_frame entries
-    uint32_t        parts_per_frame = 1;
+    PartDesc*       parts = nullptr;           // n_frames * plan.parts_per_frame entries
     void*           part_ws = nullptr;         // part_workspace_bytes() / chain_workspace_bytes()
-    bool            index_given = false;       // a.widths / a.tile_off are the CALLER's decode index (read only): the frames the per-frame decoder lists are extracted with it, no walk
-    bool            chain = false;             // large frames by the index route (decode_part.hip: one walk -> the decode index -> extraction with the widths given); parts / parts_per_frame / part_ws are that route's
+    DecodePlan      plan;                      // the route: what the launchers below launch (decode_plan.hpp); api.hip points the scratch it names (plan_scratch)
 };
 uint32_t parts_per_frame(const FrameGeom& g, size_t n_frames);
 size_t part_workspace_bytes(const FrameGeom& g, size_t n_frames);
@@ -74,9 +72,9 @@ hipError_t launch_build_parts(const DecodeArgs& a, uint32_t max_w, hipStream_t s
 // that does not work out are listed in a.defer (the position-parallel walk writes their index: launch_seg_listed)
 uint32_t chain_parts_per_frame(const FrameGeom& g, size_t n_frames, size_t pixel_bytes);   // (pixel_bytes: of the type decoded into)
 size_t chain_workspace_bytes(const FrameGeom& g, size_t n_frames, size_t pixel_bytes);
-// narrow: 8 / 16-bit pixels -- frames with few explicit headers are left to k_decode_parts on a.parts (*frame_mode: per frame, 1 = the
-// index was written, 0 = extract part by part)
-hipError_t launch_build_index_chain(const DecodeArgs& a, uint32_t max_w, bool narrow, const uint32_t** frame_mode, hipStream_t st);
+// a.plan.narrow: 8 / 16-bit pixels -- frames with few explicit headers are left to k_decode_parts on a.parts (*frame_mode: per frame,
+// 1 = the index was written, 0 = extract part by part)
+hipError_t launch_build_index_chain(const DecodeArgs& a, uint32_t max_w, const uint32_t** frame_mode, hipStream_t st);
 // ... and what has to be cleared in front of it, in one launch: the deferred-frame list's count and statistics, the route's ready
 // flags, and (clear_status) the status block
 hipError_t launch_chain_zero(const DecodeArgs& a, uint32_t max_w, bool clear_status, hipStream_t st);
@@ -110,11 +108,11 @@ size_t fused_workspace_bytes(const FrameGeom& g, size_t n_frames);
 hipError_t launch_encode_fused(int dtype, const EncodeArgs& a, void* ws, hipStream_t st);
 // the library's memory of workspaces its single-pass encoder left clean: forget those inside [lo, lo + bytes) (lo == nullptr: all)
 void fused_ws_forget(const void* lo, size_t bytes, const void* keep = nullptr);
-hipError_t launch_decode(int dtype, const DecodeArgs& a, bool have_offsets, hipStream_t st);
+hipError_t launch_decode(int dtype, const DecodeArgs& a, hipStream_t st);
 // converting decode (decode.hip): any integral output type with clamping, float, double; stream signedness given
-hipError_t launch_decode_convert(int dtype, const DecodeArgs& a, int stream_signed, bool have_offsets, hipStream_t st);
+hipError_t launch_decode_convert(int dtype, const DecodeArgs& a, int stream_signed, hipStream_t st);
 // tuned decode (decode_fast.hip): needs block = 12, frame offsets, frames of < 2^32 bits; pixels_out aligned to the pixel type (any pixel count)
-hipError_t launch_decode_fast(int dtype, const DecodeArgs& a, bool have_index, hipStream_t st, bool per_frame = false);   // per_frame (with an index): k_decode_frames_indexed
+hipError_t launch_decode_fast(int dtype, const DecodeArgs& a, hipStream_t st);
 // one workgroup per frame, walk and extraction fused through LDS (decode_frame.hip): many small frames
 hipError_t launch_decode_frames(int dtype, const DecodeArgs& a, hipStream_t st);
 hipError_t launch_decode_frames_indexed(int dtype, const DecodeArgs& a, const uint32_t* list, hipStream_t st);   // widths / group offsets given
@@ -146,7 +144,6 @@ size_t seg_workspace_bytes(const FrameGeom& g, size_t n_frames);   // (includes 
 // link walks, a write pass per frame; dense_ws: dense_workspace_bytes()
 size_t dense_workspace_bytes(const FrameGeom& g, size_t n_frames);
 hipError_t launch_dense_listed(const DecodeArgs& a, uint32_t max_w, void* dense_ws, const uint32_t* list, hipStream_t st);
-void set_dense_route(bool on);                                       // (off: the fix-point rounds of decode_seg.hip, A/B and tests)
 hipError_t launch_seg_walk(const DecodeArgs& a, uint32_t max_w, hipStream_t st);
 // frames k_decode_frames flagged in a.defer (explicit headers every few blocks): position-parallel walk + tiled extraction
 bool seg_single_wave(const FrameGeom& g, size_t n_frames);
