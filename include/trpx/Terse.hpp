@@ -278,6 +278,28 @@ public:
                                               found, &found, -1), "Terse::prolix_sparse");
     }
 
+    /// Per frame the sums of its pixels weighted by n_maps integer maps, in one device call, without expanding the frames
+    /// (trpx_decode_dot_host): weights = n_maps x size() values, map after map; out[f * n_maps + k] = sum_p px[f][p] *
+    /// weights[k * size() + p] in int64, modulo 2^64.  A mask gives a virtual detector image, the maps x, y and 1 the centre
+    /// of mass.  1 <= n_maps <= 16.
+    void prolix_dot(std::int32_t const* weights, std::size_t n_maps, std::int64_t* out) {
+        if (n_maps == 0 || n_maps > 16) throw std::invalid_argument("prolix_dot: 1 to 16 maps");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_dot: values of more than 32 bits are not supported");
+        if (d_frame_sizes.empty()) return;
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_dot_host(bits + (d_signed ? 1 : 0), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                           d_frame_sizes.size(), d_block, weights, (unsigned)n_maps, out, -1), "Terse::prolix_dot");
+    }
+    std::vector<std::int64_t> prolix_dot(std::vector<std::int32_t> const& weights, std::size_t n_maps) {
+        if (n_maps == 0 || weights.size() != n_maps * d_size) throw std::invalid_argument("prolix_dot: weights must hold n_maps x size() values");
+        std::vector<std::int64_t> out(d_frame_sizes.size() * n_maps);
+        prolix_dot(weights.data(), n_maps, out.data());
+        return out;
+    }
+
     /// Appends row_offsets.size() - 1 frames given as their events in CSR form -- what prolix_sparse returns -- in one device
     /// call, without building the dense frames (trpx_encode_sparse_host): frame k is size() zeros with px[positions[i]] =
     /// values[i] for row_offsets[k] <= i < row_offsets[k + 1].  Positions ascend strictly inside a frame and stay below the

@@ -52,8 +52,8 @@ typedef enum trpx_status {
  * writes either; files of another TERSE writer may hold them.  Padded widths decode everywhere.  A decode index describes a
  * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
- *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi and
- *     trpx_decode_sparse where they build the index themselves (no index given) -- and their _host forms;
+ *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
+ *     trpx_decode_sparse and trpx_decode_dot where they build the index themselves (no index given) -- and their _host forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -376,6 +376,54 @@ int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, cons
 int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                             size_t n_frames, unsigned block, int64_t threshold, uint64_t* row_offsets, uint32_t* positions,
                             void* values, size_t capacity, size_t* n_found, int device);
+
+/*
+ * Weighted per-frame sums: dots_out[f][k] = sum over the pixels p of frame f of px[f][p] * weights[k][p], straight from the stream
+ * and its decode index, without expanding the frames -- a virtual detector image (a mask per detector region), the centre of mass
+ * (the maps x, y and 1), the per-frame dose.  A width-0 block adds nothing and has no payload; the payload of a block on which
+ * every map is zero is never read.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_sum: index given -- validated against the frame sizes as in
+ *                  trpx_decode_indexed; offsets only -- the index is built in the workspace by trpx_build_index's walk; offsets
+ *                  NULL -- the frames are located in the workspace first.  workspace: DEVICE, 8-byte aligned, ALWAYS needed (one
+ *                  support bit per block of a frame and the partial sums live there): trpx_decode_dot_workspace_bytes() is the
+ *                  need with offsets and index both NULL; with offsets or index given less is used, and the call checks against
+ *                  what its own form needs.  The size is arithmetic on terse_bytes, n_frames, the number of 256-block groups and
+ *                  n_maps: beyond what the index needs, 8 * n_maps bytes per run of 8 groups and n_values / 96 bytes
+ *   weights        DEVICE const int32_t[n_maps][n_values], map after map, compact, 4-byte aligned; 16-byte aligned with
+ *                  n_values % 4 == 0 is the fast case.  Any int32 is legal, INT32_MIN included.  A device array on purpose: a
+ *                  captured graph is replayed with new maps in the same buffer, and nothing derived from its contents is decided
+ *                  on the host.  1 <= n_maps <= 16
+ *   dots_out       DEVICE int64_t[n_frames][n_maps], 8-byte aligned: [f][k] = sum_p (int64) px[f][p] * (int64) weights[k][p] modulo
+ *                  2^64 (two's-complement wrap; every single product fits int64 for every pixel type, so only the sum can wrap) --
+ *                  what numpy's int64 arithmetic gives.  Integer arithmetic throughout: bit-identical across runs, input forms
+ *                  and launch shapes
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT in exactly the cases of trpx_decode_sparse: a
+ *                  256-block group does not end where the next group's offset (the last group: the frame's size) says, a block is
+ *                  wider than dtype allows, a frame lies outside the stream or the index does not fit the offsets, with index ==
+ *                  NULL also for a valid stream with restated widths (trpx_build_index's verdict).  EVERY group of EVERY frame is
+ *                  walked and validated, also where no block of it is fetched.  The outputs are then unspecified
+ * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)) and weights[0 .. n_maps * n_values)
+ * is read (the weights behind a map's n_values are never read for a frame's partial last block), nothing outside dots_out, status
+ * and the workspace is written, whatever the status.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits;
+ * TRPX_ERR_INVALID_ARG for an unknown or float dtype, zero sizes, n_maps 0 or above 16, null or misaligned pointers, an index
+ * without offsets, a NULL workspace; TRPX_ERR_CAPACITY for a workspace that is too small.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the
+ * host from n_frames, n_values and n_maps alone, never from the data or the maps.
+ * trpx_decode_dot_host: host terse / frame_offsets (or NULL) / weights / dots_out; checks its arguments before a device is looked
+ * for, stages, calls trpx_decode_dot and synchronises.
+ */
+size_t trpx_decode_dot_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                       unsigned n_maps);
+int trpx_decode_dot(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                    size_t n_values, size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps,
+                    int64_t* dots_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                         size_t n_values, size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps,
+                         int64_t* dots_out, int device);
 
 /*
  * Encode from events: the stream of a stack given in CSR form -- what trpx_decode_sparse writes, what a counting detector or a

@@ -412,3 +412,42 @@ def decode_sparse(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
         raise ValueError(f"decode_sparse: positions (uint32) and values ({tdt}) must be contiguous tensors of >= {capacity} elements on {dev}")
     call(positions, values, capacity)
     return row_offsets, positions, values, status
+
+
+def decode_dot_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, n_maps: int, block: int = BLOCK) -> int:
+    return lib().trpx_decode_dot_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block, n_maps)
+
+
+def decode_dot(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, weights: torch.Tensor,
+               index: torch.Tensor | None = None, out: torch.Tensor | None = None, workspace: Workspace | None = None,
+               status: torch.Tensor | None = None, block: int = BLOCK):
+    """Per frame the sums of its pixels weighted by K integer maps (trpx_decode_dot), for a stack resident on the GPU, without
+    decoding its frames to memory: a mask gives a virtual detector image, the maps x, y and 1 the centre of mass.
+
+    ``dtype`` is the stream's pixel type; ``weights`` a contiguous int32 tensor ``[K, n_values]`` (or ``[K, H, W]`` with
+    ``H * W == n_values``) on the stack's device, 1 <= K <= 16.  Returns (dots int64 [n_frames, K], status): ``dots[f, k] =
+    sum_p px[f][p] * weights[k][p]``, exact, modulo 2^64; asynchronous on the current stream, like ``decode``.  status[0] is 5
+    for a corrupt stream or index -- the whole stack is validated, whatever the maps.  ``frame_offsets = None``: the frames are
+    located first; ``index = None``: the decode index is built on the way (both in ``workspace``)."""
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    if weights.dtype != torch.int32 or weights.dim() < 2 or not weights.is_contiguous() or weights.numel() != weights.shape[0] * n_values:
+        raise TypeError(f"decode_dot: weights must be a contiguous int32 tensor [K, {n_values}] (or [K, H, W])")
+    if weights.device != dev:
+        raise ValueError("decode_dot: weights must live on the stack's device")
+    n_maps = weights.shape[0]
+    if not 1 <= n_maps <= 16:
+        raise ValueError("decode_dot: 1 to 16 maps")
+    if out is None:
+        out = torch.empty((n_frames, n_maps), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.numel() != n_frames * n_maps or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_dot: out must be a contiguous int64 tensor of {n_frames} x {n_maps} elements on {dev}")
+    if status is None:
+        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    ws = (workspace or Workspace(dev)).get(lib().trpx_decode_dot_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_maps))
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_dot(code, terse.data_ptr(), terse.numel(),
+                                    frame_offsets.data_ptr() if frame_offsets is not None else None,
+                                    index.data_ptr() if index is not None else None, n_values, n_frames, block, weights.data_ptr(),
+                                    n_maps, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+    return out, status

@@ -15,6 +15,7 @@
 #include "../../include/trpx_hip.h"
 #include "decode_roi.hpp"
 #include "decode_sparse.hpp"
+#include "decode_dot.hpp"
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -927,6 +928,74 @@ int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, cons
     return TRPX_OK;
 }
 
+// ---- weighted per-frame sums (decode_dot.hip) --------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// trpx_decode_dot's workspace: what the missing inputs need (index_ws), then [support: one bit per block of a frame] and per
+// (frame, run of 8 groups, map) [partial sum i64]
+struct DotWs { IndexWs front; size_t support, partials, total; };
+DotWs dot_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, unsigned n_maps, bool have_offsets, bool have_index) {
+    DotWs w;
+    w.front = index_ws(dtype, g, terse_bytes, n_frames, have_offsets, have_index);
+    w.support = w.front.total;
+    w.partials = trpx::align_up(w.support + 4 * trpx::dot_support_words(g), 8);
+    w.total = w.partials + 8 * n_frames * (size_t)trpx::dot_runs_per_frame(g) * n_maps;
+    return w;
+}
+bool dot_maps_ok(unsigned n_maps) { return n_maps >= 1 && n_maps <= trpx::kDotMaxMaps; }
+}  // namespace
+extern "C" {
+
+size_t trpx_decode_dot_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned n_maps) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !dot_maps_ok(n_maps) || !geom_of(n_values, block, &g) ||
+        !sizes_ok(g, n_frames))
+        return 0;
+    return dot_ws(dtype, g, terse_bytes, n_frames, n_maps, false, false).total;
+}
+
+int trpx_decode_dot(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                    size_t n_values, size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps, int64_t* dots_out,
+                    uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_dot", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {weights, 4}, {dots_out, 8}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
+                                   {workspace, 8, false}}, &g))
+        return rc;
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot: frames of >= 2^32 bits");
+    if (n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (!dot_maps_ok(n_maps)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: n_maps=%u (1..%u)", n_maps, trpx::kDotMaxMaps);
+    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: an index needs its frame offsets");
+    if (!workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: null workspace (the support bits and the partial sums live there)");
+    const DotWs w = dot_ws(dtype, g, terse_bytes, n_frames, n_maps, frame_offsets != nullptr, index != nullptr);
+    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_dot: workspace %zu < %zu", workspace_bytes, w.total);
+
+    trpx::fused_ws_forget(workspace, workspace_bytes);
+    char* ws = static_cast<char*>(workspace);
+    bool clear = true;
+    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
+                                          w.front, stream, &clear))
+        return rc;
+    const DecLayout il = idx_layout(g, n_frames, es);
+    trpx::DotArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.geom = g;
+    a.n_frames = n_frames;
+    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
+    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    a.weights = weights;
+    a.n_maps = n_maps;
+    a.support = reinterpret_cast<uint32_t*>(ws + w.support);
+    a.partials = reinterpret_cast<int64_t*>(ws + w.partials);
+    a.dots_out = dots_out;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_dot(dtype, a, clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
 // ---- encode from events (encode_sparse.hip) ----------------------------------------------------------------------------------
 }  // extern "C"
 namespace {
@@ -1333,6 +1402,38 @@ int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes,
         HIP_TRY(copy_sync(hs, positions, o + pos_at, 4 * total, hipMemcpyDeviceToHost));
         HIP_TRY(copy_sync(hs, values, o + val_at, es * total, hipMemcpyDeviceToHost));
     }
+    return TRPX_OK;
+}
+
+int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                         size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps, int64_t* dots_out, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (!terse || !weights || !dots_out || !terse_bytes || !dot_maps_ok(n_maps)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad argument");
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot_host: block=%u dtype=%d", block, dtype);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad sizes");
+    const size_t ws_bytes = trpx_decode_dot_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_maps);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad dtype/sizes");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot_host: frames of >= 2^32 bits");
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_dot_host", device, &hs)) return rc;
+    // the maps and the sums in one device block: [weights] [dots]
+    const size_t w_bytes = 4 * (size_t)n_maps * n_values, out_at = trpx::align_up(w_bytes, 16), out_bytes = 8 * n_frames * (size_t)n_maps;
+    const uint8_t* d_in = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t* d_st = nullptr;
+    void *d_out = nullptr, *d_ws = nullptr;
+    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
+    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
+    HIP_TRY(arena().get(Arena::kPixels, out_at + out_bytes, &d_out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
+    char* o = static_cast<char*>(d_out);
+    HIP_TRY(copy_sync(hs, o, weights, w_bytes, hipMemcpyHostToDevice));
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_dot(dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, reinterpret_cast<const int32_t*>(o), n_maps,
+                         reinterpret_cast<int64_t*>(o + out_at), d_st, d_ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_dot_host", st))) return rc;
+    HIP_TRY(copy_sync(hs, dots_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

@@ -1,0 +1,33 @@
+// Host-visible interface of decode_dot.hip (trpx_decode_dot): per frame the sums of its pixels weighted by K integer maps,
+// straight from the stream and its decode index.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stddef.h>
+#include "codec_common.hpp"
+
+namespace trpx {
+
+constexpr uint32_t kDotMaxMaps = 16;
+
+struct DotArgs {
+    const uint8_t*  terse;
+    uint64_t        terse_bytes;
+    const uint64_t* frame_offsets;  // n_frames + 1
+    FrameGeom       geom;
+    uint64_t        n_frames;
+    const uint8_t*  widths;         // decode index: width of every block
+    const uint64_t* tile_off;       // decode index: frame-relative bit offset of every 256-block group
+    const int32_t*  weights;        // [n_maps][n_values]
+    uint32_t        n_maps;
+    uint32_t*       support;        // workspace, dot_support_words(): bit b = some map is non-zero on block b of a frame
+    int64_t*        partials;       // workspace, [n_frames][dot_runs_per_frame()][n_maps]
+    int64_t*        dots_out;       // [n_frames][n_maps]
+    uint32_t*       status;
+};
+uint32_t dot_runs_per_frame(const FrameGeom& g);
+__host__ __device__ inline size_t dot_support_words(const FrameGeom& g) { return ((size_t)g.n_blocks + 31) / 32; }
+// k_dot_support, k_dot_runs, k_dot_reduce; clear_status: zero the status block first
+hipError_t launch_decode_dot(int dtype, const DotArgs& a, bool clear_status, hipStream_t st);
+
+}  // namespace trpx

@@ -1,9 +1,10 @@
 // Threshold decode (trpx_decode_sparse): a stack with its decode index -> the pixels at or above a threshold as (row offsets,
 // positions, values), without expanding the frames.  The order of the output is fixed (by frame, then by pixel), so the
 // shape is count -> scan -> write.  The two kernels that read the stream give a wavefront a RUN of kRun consecutive 256-block
-// groups of one frame (group_front.hpp: four blocks per lane): what belongs to the run is loaded once and coalesced (the frame's
-// bytes, the groups' offsets, counts, bases and flag words, one per lane), the next group's widths are in flight while a group is
-// scanned and extracted, and the run's counts and flag words leave in one store each.
+// groups of one frame (group_front.hpp: four blocks per lane; group_runs.hpp: the run and the candidate list): what belongs to
+// the run is loaded once and coalesced (the frame's bytes, the groups' offsets, counts, bases and flag words, one per lane), the
+// next group's widths are in flight while a group is scanned and extracted, and the run's counts and flag words leave in one
+// store each.
 //
 //   k_sparse_count       every group of every frame: widths -> header_len + 12 * w -> wave scans from the group's offset -> the
 //                        group validated (so the whole stack is) -> the CANDIDATE blocks, those wide enough to hold an event (a
@@ -22,14 +23,11 @@
 #include "codec_common.hpp"
 #include "decode_sparse.hpp"
 #include "group_front.hpp"
+#include "group_runs.hpp"
 
 namespace trpx {
 
 namespace {
-
-constexpr int kWavesPerWg = kThreads / kWave;
-constexpr uint32_t kRun = 8;                                // consecutive groups of one frame per wavefront
-static_assert(kRun * kGroupRows <= kWave && kRun < kWave, "a run's offsets and flag words: one per lane");
 
 // the lane's block's values (first nr of the 12 in o) at or above the threshold: the comparison is on the extracted value
 template <typename T>
@@ -41,22 +39,6 @@ __device__ __forceinline__ uint32_t event_mask(const uint32_t (&o)[PackedDwords<
     return mask;
 }
 
-__device__ __forceinline__ uint64_t lane_value64(uint64_t v, uint32_t src) {
-    return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)src, kWave) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)src, kWave) << 32);
-}
-// lanes below this one in a ballot
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-// The wavefront's list of chosen blocks in LDS (kTileBlocks entries, block order): written by the lanes that own the blocks,
-// read 64 at a time by consecutive lanes.  An entry: payload bit in the group (17 bits: a group has < 2^17 bits), width (6),
-// block in the group (8).
-__device__ __forceinline__ uint32_t list_entry(uint32_t off, uint32_t w, uint32_t block) { return off | (w << 17) | (block << 23); }
-__device__ __forceinline__ void list_sync() {               // the wavefront's LDS writes are seen by its other lanes' reads behind this
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // entry 64 * c + lane of a list of n: the lane's block, extracted; returns its event mask (0 behind the list's end)
 template <typename T>
 __device__ __forceinline__ uint32_t list_round(uint32_t (&o)[PackedDwords<T>::n], uint32_t& block, const uint32_t* __restrict__ list,
@@ -69,30 +51,6 @@ __device__ __forceinline__ uint32_t list_round(uint32_t (&o)[PackedDwords<T>::n]
     const uint32_t nr = have ? (left < (uint32_t)kBlock ? left : (uint32_t)kBlock) : 0u;
     group_extract<T>(o, gs, have, (e >> 17) & 63u, nr, e & 0x1FFFFu);
     return have ? event_mask<T>(o, nr, threshold) : 0u;
-}
-
-// what a wavefront holds for its run: lane j the offset of group g0 + j (lane n: the group behind the run)
-struct Run {
-    uint64_t frame, u0, fo, fe, my_off;
-    uint32_t g0, n;
-    const uint8_t* __restrict__ wf;
-};
-// where the run lies (arithmetic only) ...
-__device__ __forceinline__ Run run_place(const SparseArgs& a, uint64_t run, uint32_t runs_per_frame) {
-    const FrameGeom& g = a.geom;
-    Run r;
-    r.frame = run / runs_per_frame;
-    r.g0 = (uint32_t)(run - r.frame * runs_per_frame) * kRun;
-    r.n = g.n_tiles - r.g0 < kRun ? g.n_tiles - r.g0 : kRun;
-    r.u0 = r.frame * g.n_tiles + r.g0;
-    r.wf = a.widths + r.frame * g.n_blocks;
-    return r;
-}
-// ... and what is loaded once for it
-__device__ __forceinline__ void run_load(Run& r, const SparseArgs& a, uint32_t lane) {
-    r.fo = a.frame_offsets[r.frame];
-    r.fe = a.frame_offsets[r.frame + 1];
-    r.my_off = lane <= r.n && r.g0 + lane < a.geom.n_tiles ? a.tile_off[r.u0 + lane] : 0ull;
 }
 
 template <typename T>

@@ -321,6 +321,29 @@ class Terse:
             return out_rows, pos[:0], val[:0]
         return out_rows, np.concatenate([pos[p] for p in pieces]), np.concatenate([val[p] for p in pieces])
 
+    def prolix_dot(self, weights) -> np.ndarray:
+        """Per frame the sums of its pixels weighted by K integer maps in ONE GPU call (trpx_decode_dot_host), without decoding
+        the frames to memory.  ``weights``: int32 ``[K, size]`` (or ``[K, H, W]`` with ``H * W == size``, or one map), 1 <= K <=
+        16.  Returns int64 ``[number_of_frames, K]``: ``[f, k] = sum_p px[f][p] * weights[k][p]``, exact, modulo 2^64 -- a mask
+        gives a virtual detector image, the maps x, y and 1 the centre of mass."""
+        w = np.asarray(weights)
+        if w.dtype.kind not in "iu" or (w.size and (w.min() < -2**31 or w.max() > 2**31 - 1)):
+            raise TypeError("prolix_dot: weights must be integers that fit int32")
+        if w.ndim == 1:
+            w = w[None]
+        if w.ndim < 2 or w.size != w.shape[0] * self._size or not 1 <= w.shape[0] <= 16:
+            raise ValueError("prolix_dot: weights must be [K, size] or [K, H, W] with 1 <= K <= 16")
+        w = np.ascontiguousarray(w.reshape(w.shape[0], self._size), dtype=np.int32)
+        code, _ = self._stream_type("prolix_dot")
+        f = self.number_of_frames()
+        out = np.zeros((f, w.shape[0]), np.int64)
+        if f:
+            buf = np.frombuffer(self._data, np.uint8)
+            offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+            check(lib().trpx_decode_dot_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f, self._block,
+                                             w.ctypes.data, w.shape[0], out.ctypes.data, self._device))
+        return out
+
     # ---- accessors (Terse.hpp:396-444) --------------------------------------------------------
     def size(self) -> int:
         return self._size
