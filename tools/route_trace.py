@@ -2,7 +2,7 @@
 
 Run (GPU box, library from $TRPX_LIB or the tree's):
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/route_trace.py --out DIR
-calls trpx_decode (with and without offsets), trpx_build_index, trpx_decode_indexed and trpx_decode_sum / _roi / _sparse
+calls trpx_decode (with and without offsets), trpx_build_index, trpx_decode_indexed and trpx_decode_sum / _roi / _sparse / _dot
 without an index once per stack under the selectors 0 .. 5 of trpx_set_decode_path.  Every call is preceded by one k_synth
 launch, so the trace falls into one segment per call; the labels go to DIR/calls_<pid>.txt.  The many-frames rule's stacks run
 as 4 frames under TRPX_SINGLE_PART=4,1048576 in a child process of their own (the rule is read when the library loads).
@@ -53,6 +53,7 @@ def run(out_dir, many):
         terse, offs = enc.stack(), enc.frame_offsets
         box = torch.tensor([[0, 0, 0]], dtype=torch.int32, device=dev)
         high = 1 << (14 if px.dtype == torch.uint16 else 28)
+        ones = torch.ones((1, n), dtype=torch.int32, device=dev)
 
         def decoded(label, **kw):
             mark(label)
@@ -77,6 +78,9 @@ def run(out_dir, many):
             mark(tag + "decode_sparse")
             _, _, _, st = codec.decode_sparse(terse, offs, n, f, dt, high, capacity=4096, workspace=ws)
             assert int(st[0].item()) in (_lib.OK, _lib.ERR_CAPACITY), tag
+            mark(tag + "decode_dot")
+            _, st = codec.decode_dot(terse, offs, n, f, dt, ones, workspace=ws)
+            assert int(st[0].item()) == 0, tag
         _lib.check(L.trpx_set_decode_path(0))
         if name == "4x64^2 u16":                              # the routes outside the tuned decoders
             decoded(name + ": decode into int64", dtype=torch.int64, stream_signed=False)

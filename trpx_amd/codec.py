@@ -34,6 +34,14 @@ def _stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _ptr(t: torch.Tensor | None):
+    return t.data_ptr() if t is not None else None
+
+
+def _status(status: torch.Tensor | None, dev) -> torch.Tensor:
+    return status if status is not None else torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+
+
 def worst_case_bytes(dtype, n_values: int, block: int = BLOCK) -> int:
     return lib().trpx_worst_case_bytes(dtype_code(dtype), n_values, block)
 
@@ -68,8 +76,7 @@ class Encoded:
             with torch.cuda.device(px.device):
                 check(lib().trpx_encode_checked(dtype_code(px.dtype), px.data_ptr(), self.n_values, self.n_frames, block,
                                                 self.data.data_ptr(), self.data.numel(), self.frame_offsets.data_ptr(),
-                                                self.status.data_ptr(), self.index.data_ptr() if self.index is not None else None,
-                                                ws.data_ptr(), ws.numel(), _stream_ptr(px), None))
+                                                self.status.data_ptr(), _ptr(self.index), ws.data_ptr(), ws.numel(), _stream_ptr(px), None))
             code = int(self.status[0].item())
         if code:
             raise _lib.TrpxError(code, "device status after encode")
@@ -105,6 +112,10 @@ class Workspace:
         self.release()
 
 
+def _scratch(workspace: Workspace | None, dev, nbytes: int) -> torch.Tensor:
+    return (workspace or Workspace(dev)).get(nbytes)
+
+
 def index_bytes(dtype, n_values: int, n_frames: int, block: int = BLOCK) -> int:
     return lib().trpx_index_bytes(dtype_code(dtype), n_values, n_frames, block)
 
@@ -127,8 +138,7 @@ def encode(pixels: torch.Tensor, out: torch.Tensor | None = None, workspace: Wor
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
     if frame_offsets is None:
         frame_offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    status = _status(status, dev)
     ws_bytes = lib().trpx_encode_workspace_bytes(code, n_values, n_frames, block)
     # (no Workspace given: a plain tensor that nobody owns beyond Encoded._retry -- a throw-away Workspace object would
     # invalidate in its destructor BEFORE the call below registers the memory as clean)
@@ -137,8 +147,7 @@ def encode(pixels: torch.Tensor, out: torch.Tensor | None = None, workspace: Wor
         index = torch.empty(index_bytes(px.dtype, n_values, n_frames, block), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         check(lib().trpx_encode_indexed(code, px.data_ptr(), n_values, n_frames, block, out.data_ptr(), out.numel(),
-                                        frame_offsets.data_ptr(), status.data_ptr(),
-                                        index.data_ptr() if index is not None else None, ws.data_ptr(), ws.numel(),
+                                        frame_offsets.data_ptr(), status.data_ptr(), _ptr(index), ws.data_ptr(), ws.numel(),
                                         _stream_ptr(px)))
         if workspace is None:
             # The buffer dies with the Encoded object and goes back to torch's allocator, which may hand its address to
@@ -187,9 +196,8 @@ def encode_sparse(row_offsets: torch.Tensor, positions: torch.Tensor | None, val
         out = torch.empty(max(encode_sparse_bound_bytes(tdt, n_values, n_frames, n_events, block), 16), dtype=torch.uint8, device=dev)
     if frame_offsets is None:
         frame_offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
-    ws = (workspace or Workspace(dev)).get(lib().trpx_encode_sparse_workspace_bytes(code, n_values, n_frames, block))
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_encode_sparse_workspace_bytes(code, n_values, n_frames, block))
     with torch.cuda.device(dev):
         check(lib().trpx_encode_sparse(code, row_offsets.data_ptr(), positions.data_ptr() if n_events else None,
                                        values.data_ptr() if n_events else None, n_events, n_values, n_frames, block,
@@ -210,19 +218,16 @@ def decode(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: in
         stream_signed = bool(lib().trpx_dtype_is_signed(code))
     if out is None:
         out = torch.empty((n_frames, n_values), dtype=tdt, device=dev)
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    status = _status(status, dev)
     if index is not None:   # walk-free decode with a previously kept index
         with torch.cuda.device(dev):
             check(lib().trpx_decode_indexed(int(stream_signed), code, terse.data_ptr(), terse.numel(),
                                             frame_offsets.data_ptr(), index.data_ptr(), n_values, n_frames, block,
                                             out.data_ptr(), status.data_ptr(), _stream_ptr(terse)))
         return out, status
-    ws_bytes = lib().trpx_decode_workspace_bytes(code, n_values, n_frames, block)
-    ws = (workspace or Workspace(dev)).get(ws_bytes)
+    ws = _scratch(workspace, dev, lib().trpx_decode_workspace_bytes(code, n_values, n_frames, block))
     with torch.cuda.device(dev):
-        check(lib().trpx_decode(int(stream_signed), code, terse.data_ptr(), terse.numel(),
-                                frame_offsets.data_ptr() if frame_offsets is not None else None,
+        check(lib().trpx_decode(int(stream_signed), code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets),
                                 n_values, n_frames, block, out.data_ptr(), status.data_ptr(), ws.data_ptr(),
                                 ws.numel(), _stream_ptr(terse)))
     return out, status
@@ -244,9 +249,8 @@ def locate_frames(terse: torch.Tensor, n_values: int, n_frames: int, dtype, bloc
     dev = terse.device
     if out is None:
         out = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
-    ws = (workspace or Workspace(dev)).get(locate_workspace_bytes(terse.numel(), n_values, n_frames, block))
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, locate_workspace_bytes(terse.numel(), n_values, n_frames, block))
     with torch.cuda.device(dev):
         check(lib().trpx_locate_frames(terse.data_ptr(), terse.numel(), n_values, n_frames, block, _max_bits(dtype),
                                        out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
@@ -259,7 +263,7 @@ def build_index(terse: torch.Tensor, frame_offsets: torch.Tensor, n_values: int,
     code = dtype_code(torch_dtype(dtype))
     dev = terse.device
     index = torch.empty(index_bytes(dtype, n_values, n_frames, block), dtype=torch.uint8, device=dev)
-    status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    status = _status(None, dev)
     with torch.cuda.device(dev):
         check(lib().trpx_build_index(code, terse.data_ptr(), terse.numel(), frame_offsets.data_ptr(), n_values,
                                      n_frames, block, index.data_ptr(), status.data_ptr(), _stream_ptr(terse)))
@@ -300,15 +304,12 @@ def decode_sum(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
     n_out = -(-n_frames // group) if group > 0 else 0
     if out is None:
         out = torch.empty((n_out, n_values), dtype=odt, device=dev)
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
-    ws_bytes = lib().trpx_decode_sum_workspace_bytes(code, terse.numel(), n_values, n_frames, block, group)
-    ws = (workspace or Workspace(dev)).get(ws_bytes)
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_sum_workspace_bytes(code, terse.numel(), n_values, n_frames, block, group))
     with torch.cuda.device(dev):
-        check(lib().trpx_decode_sum(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(),
-                                    frame_offsets.data_ptr() if frame_offsets is not None else None,
-                                    index.data_ptr() if index is not None else None, n_values, n_frames, block, group,
-                                    out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+        check(lib().trpx_decode_sum(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                    n_values, n_frames, block, group, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    _stream_ptr(terse)))
     return out, status
 
 
@@ -340,18 +341,15 @@ def decode_roi(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
         out = torch.empty((n_boxes, box_h, box_w), dtype=tdt, device=dev)
     elif out.dtype != tdt or out.numel() != n_boxes * box_h * box_w or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"decode_roi: out must be a contiguous {tdt} tensor of {n_boxes} x {box_h} x {box_w} elements on {dev}")
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
+    status = _status(status, dev)
     ws_ptr, ws_bytes = None, 0
     if index is None or frame_offsets is None:
-        ws = (workspace or Workspace(dev)).get(lib().trpx_decode_roi_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+        ws = _scratch(workspace, dev, lib().trpx_decode_roi_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
         ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
     with torch.cuda.device(dev):
-        check(lib().trpx_decode_roi(code, terse.data_ptr(), terse.numel(),
-                                    frame_offsets.data_ptr() if frame_offsets is not None else None,
-                                    index.data_ptr() if index is not None else None, n_values, n_frames, block, width,
-                                    boxes.data_ptr(), n_boxes, box_h, box_w, out.data_ptr(), status.data_ptr(), ws_ptr, ws_bytes,
-                                    _stream_ptr(terse)))
+        check(lib().trpx_decode_roi(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                    n_values, n_frames, block, width, boxes.data_ptr(), n_boxes, box_h, box_w, out.data_ptr(),
+                                    status.data_ptr(), ws_ptr, ws_bytes, _stream_ptr(terse)))
     return out, status
 
 
@@ -382,18 +380,14 @@ def decode_sparse(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
     dev = terse.device
     if row_offsets is None:
         row_offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
-    ws = (workspace or Workspace(dev)).get(lib().trpx_decode_sparse_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_sparse_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
 
     def call(pos, val, cap):
         with torch.cuda.device(dev):
-            check(lib().trpx_decode_sparse(code, terse.data_ptr(), terse.numel(),
-                                           frame_offsets.data_ptr() if frame_offsets is not None else None,
-                                           index.data_ptr() if index is not None else None, n_values, n_frames, block, int(threshold),
-                                           row_offsets.data_ptr(), pos.data_ptr() if pos is not None else None,
-                                           val.data_ptr() if val is not None else None, cap, status.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), _stream_ptr(terse)))
+            check(lib().trpx_decode_sparse(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                           n_values, n_frames, block, int(threshold), row_offsets.data_ptr(), _ptr(pos),
+                                           _ptr(val), cap, status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
 
     if capacity is None:
         if positions is not None or values is not None:
@@ -442,12 +436,9 @@ def decode_dot(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
         out = torch.empty((n_frames, n_maps), dtype=torch.int64, device=dev)
     elif out.dtype != torch.int64 or out.numel() != n_frames * n_maps or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"decode_dot: out must be a contiguous int64 tensor of {n_frames} x {n_maps} elements on {dev}")
-    if status is None:
-        status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=dev)
-    ws = (workspace or Workspace(dev)).get(lib().trpx_decode_dot_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_maps))
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_dot_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_maps))
     with torch.cuda.device(dev):
-        check(lib().trpx_decode_dot(code, terse.data_ptr(), terse.numel(),
-                                    frame_offsets.data_ptr() if frame_offsets is not None else None,
-                                    index.data_ptr() if index is not None else None, n_values, n_frames, block, weights.data_ptr(),
-                                    n_maps, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+        check(lib().trpx_decode_dot(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                    n_values, n_frames, block, weights.data_ptr(), n_maps, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
     return out, status

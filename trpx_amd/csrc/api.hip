@@ -1,8 +1,9 @@
 // C ABI of libtrpx_hip.so (declared in include/trpx_hip.h).  Thin: argument checks, workspace
 // carving, kernel launches on the caller's stream.  No CPU codec lives here: without a gfx950
 // device every compute entry point fails with TRPX_ERR_NO_DEVICE / TRPX_ERR_HIP.
-// Layout: predicates and routes, the one argument prologue, workspace layouts, the device-pointer ABI, then the host
-// staging helpers (Arena, enter, upload_stream, ...) and the host-pointer wrappers built from them.
+// Layout: predicates and routes, the one argument prologue, workspace layouts, the device-pointer ABI, the consumers of a decode
+// index behind their shared front (consumer_front), then the host staging helpers (Arena, enter, stage, finish, ...) and the
+// host-pointer wrappers built from them.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -657,57 +658,143 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 }
 
 }  // extern "C"
-// ---- summing decode (decode_sum.hip) -------------------------------------------------------------------------------------
+// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot -------------------
+// Each reads: its own checks, the shared checks (stack_limits, consumer_ws), the front (consumer_front), its own few fields, launch.
 namespace {
-bool sum_out_ok(int out_dtype) {
-    return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_I64 || out_dtype == TRPX_U64 ||
-           out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
-}
-size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
-// The consumers of a decode index (trpx_decode_sum, trpx_decode_roi) take three input forms: index given; offsets only -- the
-// index is built by trpx_build_index's walk; neither -- the frames are located first.  Their workspace starts with what the
-// missing inputs need: [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)].
-struct IndexWs { size_t offsets, region, total; };
+// The consumers take three input forms: index given; offsets only -- the index is built by trpx_build_index's walk; neither --
+// the frames are located first.  Their workspace starts with what the missing inputs need:
+// [frame offsets (no offsets given)] [the locator's scratch, then the decode index (no index given)]; the consumer's own scratch
+// follows at `total`, and `need` is the whole of it (consumer_ws).
+struct IndexWs { size_t offsets, region, total, need; };
 IndexWs index_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, bool have_offsets, bool have_index) {
     IndexWs w;
     w.offsets = 0;
     w.region = have_offsets ? 0 : trpx::align_up(8 * (n_frames + 1), 256);
     const size_t idx = have_index ? 0 : idx_layout(g, n_frames, trpx_dtype_size(dtype)).total;
     const size_t loc = have_offsets ? 0 : trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    w.total = w.region + trpx::align_up(std::max(idx, loc), 256);
+    w.need = w.total = w.region + trpx::align_up(std::max(idx, loc), 256);
     return w;
 }
-// Makes *frame_offsets and *index valid, in the workspace where the caller gave none.  *clear: the consumer still has to clear
-// the status block (false once the locator or the walk has written its verdict there).
-int index_in_workspace(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t** frame_offsets, const void** index,
-                       size_t n_values, size_t n_frames, unsigned block, const trpx::FrameGeom& g, uint32_t* status, char* ws,
-                       const IndexWs& w, void* stream, bool* clear, bool check = true) {
-    *clear = true;
-    if (!*frame_offsets) {                                                      // index-free: locate the frames first (its scratch: the index region)
-        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
-        HIP_TRY(trpx::launch_locate(terse, terse_bytes, g, (uint32_t)n_frames, 8u * (uint32_t)trpx_dtype_size(dtype), offs, status,
-                                    ws + w.region, static_cast<hipStream_t>(stream)));
-        *frame_offsets = offs;
-        *clear = false;                                                         // (the locator's verdict stays)
-    }
-    if (!*index) {                                                              // the walk of trpx_build_index, into the workspace
-        const int rc = build_index_impl(dtype, terse, terse_bytes, *frame_offsets, n_values, n_frames, block, ws + w.region, status,
-                                        *clear, stream, check);
-        if (rc) return rc;
-        *index = ws + w.region;
-        *clear = false;
-    }
+// what the *_workspace_bytes queries answer for: the front of the form without offsets and index, 0 for what no consumer takes
+size_t consumer_front_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, trpx::FrameGeom* g) {
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !geom_of(n_values, block, g) || !sizes_ok(*g, n_frames))
+        return 0;
+    return index_ws(dtype, *g, terse_bytes, n_frames, false, false).total;
+}
+// a consumer's call, as the shared steps see it (g: from the entry point's own argument checks)
+struct Consumer {
+    const char* fn;
+    int dtype;
+    const uint8_t* terse;
+    size_t terse_bytes;
+    const uint64_t* frame_offsets;
+    const void* index;
+    size_t n_values, n_frames;
+    unsigned block;
+    trpx::FrameGeom g;
+    uint32_t* status;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+};
+int stack_limits(const Consumer& c) {
+    if (!frame_bits_fit_32(c.dtype, c.n_values, c.block)) return fail(TRPX_ERR_UNSUPPORTED, "%s: frames of >= 2^32 bits", c.fn);
+    if (c.n_frames > c.terse_bytes)                                             // every frame is at least one byte (Terse.hpp:547)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", c.fn, c.n_values, c.n_frames);
     return TRPX_OK;
 }
-// trpx_decode_sum's workspace: the above, then [partial slab]
-struct SumWs { IndexWs front; size_t partial, total; };
-SumWs sum_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, size_t group, bool have_offsets, bool have_index) {
-    SumWs w;
-    w.front = index_ws(dtype, g, terse_bytes, n_frames, have_offsets, have_index);
-    w.partial = w.front.total;
-    w.total = w.partial + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes;
+// The workspace against what this form of the call needs: *w, then own_bytes of the consumer's.  always: why the consumer needs
+// a workspace in every form (asked before the capacity), or null: only a form that needs one has to bring one.
+int consumer_ws(const Consumer& c, size_t own_bytes, const char* always, IndexWs* w) {
+    if (c.index && !c.frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "%s: an index needs its frame offsets", c.fn);
+    if (always && !c.workspace) return fail(TRPX_ERR_INVALID_ARG, "%s: null workspace (%s)", c.fn, always);
+    *w = index_ws(c.dtype, c.g, c.terse_bytes, c.n_frames, c.frame_offsets != nullptr, c.index != nullptr);
+    w->need = w->total + own_bytes;
+    if (c.workspace_bytes < w->need) return fail(TRPX_ERR_CAPACITY, "%s: workspace %zu < %zu", c.fn, c.workspace_bytes, w->need);
+    if (w->need && !c.workspace) return fail(TRPX_ERR_INVALID_ARG, "%s: null workspace", c.fn);
+    return TRPX_OK;
+}
+// The front itself: a workspace that is used is forgotten as an encoder's, the offsets and the index are made valid, in the
+// workspace where the caller gave none, and the stack is viewed through them.  clear: the consumer still has to clear the status block (false once the locator or the walk has written
+// its verdict there); own: the consumer's scratch.  check_index: compare a walked index with the stream's headers
+// (k_check_index; false where the consumer makes the comparison itself).
+struct Front { trpx::IndexedStack stack; bool clear; char* own; };
+int consumer_front(const Consumer& c, const IndexWs& w, bool check_index, Front* f) {
+    char* ws = static_cast<char*>(c.workspace);
+    const uint64_t* frame_offsets = c.frame_offsets;
+    const char* index = static_cast<const char*>(c.index);
+    if (w.need) trpx::fused_ws_forget(c.workspace, c.workspace_bytes);
+    f->clear = true;
+    f->own = ws + w.total;
+    if (!frame_offsets) {                                                       // index-free: locate the frames first (its scratch: the index region)
+        uint64_t* offs = reinterpret_cast<uint64_t*>(ws + w.offsets);
+        HIP_TRY(trpx::launch_locate(c.terse, c.terse_bytes, c.g, (uint32_t)c.n_frames, 8u * (uint32_t)trpx_dtype_size(c.dtype), offs, c.status,
+                                    ws + w.region, static_cast<hipStream_t>(c.stream)));
+        frame_offsets = offs;
+        f->clear = false;                                                       // (the locator's verdict stays)
+    }
+    if (!index) {                                                               // the walk of trpx_build_index, into the workspace
+        if (const int rc = build_index_impl(c.dtype, c.terse, c.terse_bytes, frame_offsets, c.n_values, c.n_frames, c.block, ws + w.region,
+                                            c.status, f->clear, c.stream, check_index))
+            return rc;
+        index = ws + w.region;
+        f->clear = false;
+    }
+    const DecLayout il = idx_layout(c.g, c.n_frames, trpx_dtype_size(c.dtype));
+    f->stack = {c.terse, c.terse_bytes, frame_offsets, c.g, c.n_frames, reinterpret_cast<const uint8_t*>(index + il.widths),
+                reinterpret_cast<const uint64_t*>(index + il.tile_off)};
+    return TRPX_OK;
+}
+
+// ---- summing decode (decode_sum.hip): its scratch is [partial slab] --------------------------------------------------------------
+bool sum_out_ok(int out_dtype) {
+    return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_I64 || out_dtype == TRPX_U64 ||
+           out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
+}
+size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
+
+// ---- box decode (decode_roi.hip): no scratch of its own ------------------------------------------------------------------------------
+// the geometry checks the device-pointer and the host-pointer entry point share (sizes from the frame: < 2^29 values, see
+// frame_bits_fit_32); 0 = fine
+int roi_geometry(const char* fn, size_t n_values, size_t width, size_t n_boxes, unsigned box_h, unsigned box_w) {
+    if (width == 0 || n_values % width) return fail(TRPX_ERR_INVALID_ARG, "%s: width %zu does not divide n_values %zu", fn, width, n_values);
+    if (box_h == 0 || box_w == 0 || box_h > n_values / width || box_w > width)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: box %u x %u in frames of %zu x %zu", fn, box_h, box_w, n_values / width, width);
+    if (n_boxes == 0) return fail(TRPX_ERR_INVALID_ARG, "%s: no boxes", fn);
+    return TRPX_OK;
+}
+
+// ---- threshold decode (decode_sparse.hip): its scratch is per (frame, group) [counts u32] [flags 4 x u64] [base u32] and per
+// frame [total u32] -----------------------------------------------------------------------------------------------------------------
+struct SparseWs { size_t counts, flags, base, frame_total, total; };
+SparseWs sparse_ws(const trpx::FrameGeom& g, size_t n_frames) {
+    SparseWs w;
+    const size_t groups = n_frames * (size_t)g.n_tiles;
+    w.counts = 0;
+    w.flags = trpx::align_up(w.counts + 4 * groups, 8);
+    w.base = w.flags + 32 * groups;
+    w.frame_total = w.base + 4 * groups;
+    w.total = trpx::align_up(w.frame_total + 4 * n_frames, 8);
     return w;
 }
+// the rule the device-pointer and the host-pointer entry point share: both outputs, or neither and no capacity (sizes only)
+int sparse_outputs(const char* fn, const void* positions, const void* values, size_t capacity) {
+    if ((positions == nullptr) != (values == nullptr)) return fail(TRPX_ERR_INVALID_ARG, "%s: positions and values go together", fn);
+    if (!positions && capacity) return fail(TRPX_ERR_INVALID_ARG, "%s: capacity %zu without outputs", fn, capacity);
+    return TRPX_OK;
+}
+
+// ---- weighted per-frame sums (decode_dot.hip): its scratch is [support: one bit per block of a frame] and per (frame, run of 8
+// groups, map) [partial sum i64] ------------------------------------------------------------------------------------------------------
+struct DotWs { size_t support, partials, total; };
+DotWs dot_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_maps) {
+    DotWs w;
+    w.support = 0;
+    w.partials = trpx::align_up(w.support + 4 * trpx::dot_support_words(g), 8);
+    w.total = w.partials + 8 * n_frames * (size_t)trpx::dot_runs_per_frame(g) * n_maps;
+    return w;
+}
+bool dot_maps_ok(unsigned n_maps) { return n_maps >= 1 && n_maps <= trpx::kDotMaxMaps; }
 }  // namespace
 
 extern "C" {
@@ -715,10 +802,8 @@ extern "C" {
 size_t trpx_decode_sum_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
                                        unsigned group) {
     trpx::FrameGeom g;
-    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !group || !terse_bytes ||
-        !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
-        return 0;
-    return sum_ws(dtype, g, terse_bytes, n_frames, group, false, false).total;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && group ? front + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes : 0;
 }
 
 // (its own order of checks: a 64-bit dtype is UNSUPPORTED before an unknown one is INVALID_ARG, tests/test_decode_sum_args.py)
@@ -740,63 +825,35 @@ int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse
     if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 ||
         (uintptr_t)workspace % 8 || (uintptr_t)sums_out % sum_out_size(out_dtype))
         return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: misaligned pointer (terse 4 B, offsets / workspace 8 B, index 16 B, sums their type)");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: frames of >= 2^32 bits");
-    const SumWs w = sum_ws(dtype, g, terse_bytes, n_frames, group, frame_offsets != nullptr, index != nullptr);
-    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sum: workspace %zu < %zu", workspace_bytes, w.total);
-    if (w.total && !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null workspace");
+    const Consumer c{"trpx_decode_sum", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
     const trpx::SumPlan p = trpx::sum_plan(dtype, g, n_frames, group);
+    IndexWs w;
+    if (const int rc = consumer_ws(c, p.partial_bytes, nullptr, &w)) return rc;
     if (p.n_out * p.chunks * (uint64_t)p.tpf >= (1ull << 40)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes");
-
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);
-    bool clear = true;
+    if (workspace) trpx::fused_ws_forget(workspace, workspace_bytes);            // (also in the form that needs none)
+    Front f;
     // (no k_check_index behind the walk: k_sum_tiles compares every block's header bit with its widths on the way)
-    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
-                                          w.front, stream, &clear, false))
-        return rc;
-    const DecLayout il = idx_layout(g, n_frames, trpx_dtype_size(dtype));
+    if (const int rc = consumer_front(c, w, false, &f)) return rc;
     trpx::SumArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = n_frames;
+    trpx::set_stack(a, f.stack);
     a.group = group;
     a.n_out = p.n_out;
     a.tpf = p.tpf;
     a.chunks = p.chunks;
     a.fpc = p.fpc;
-    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
-    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
     a.out = sums_out;
     a.out_code = out_dtype;
-    a.partial = p.chunks > 1 ? ws + w.partial : nullptr;
+    a.partial = p.chunks > 1 ? f.own : nullptr;
     a.status = status;
-    HIP_TRY(trpx::launch_decode_sum(dtype, a, clear, st));
+    HIP_TRY(trpx::launch_decode_sum(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
-
-// ---- box decode (decode_roi.hip) -----------------------------------------------------------------------------------------
-}  // extern "C"
-namespace {
-// the geometry checks the device-pointer and the host-pointer entry point share (sizes from the frame: < 2^29 values, see
-// frame_bits_fit_32); 0 = fine
-int roi_geometry(const char* fn, size_t n_values, size_t width, size_t n_boxes, unsigned box_h, unsigned box_w) {
-    if (width == 0 || n_values % width) return fail(TRPX_ERR_INVALID_ARG, "%s: width %zu does not divide n_values %zu", fn, width, n_values);
-    if (box_h == 0 || box_w == 0 || box_h > n_values / width || box_w > width)
-        return fail(TRPX_ERR_INVALID_ARG, "%s: box %u x %u in frames of %zu x %zu", fn, box_h, box_w, n_values / width, width);
-    if (n_boxes == 0) return fail(TRPX_ERR_INVALID_ARG, "%s: no boxes", fn);
-    return TRPX_OK;
-}
-}  // namespace
-extern "C" {
 
 size_t trpx_decode_roi_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
     trpx::FrameGeom g;
-    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
-        return 0;
-    return index_ws(dtype, g, terse_bytes, n_frames, false, false).total;
+    return consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
 }
 
 int trpx_decode_roi(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
@@ -809,29 +866,19 @@ int trpx_decode_roi(int dtype, const uint8_t* terse, size_t terse_bytes, const u
                                   {{terse, 4}, {boxes, 4}, {pixels_out, es}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
                                    {workspace, 8, false}}, &g))
         return rc;
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_roi: frames of >= 2^32 bits");
-    if (n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    const Consumer c{"trpx_decode_roi", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
     if (const int rc = roi_geometry("trpx_decode_roi", n_values, width, n_boxes, box_h, box_w)) return rc;
-    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: an index needs its frame offsets");
     const uint32_t units = trpx::roi_units_per_box(g, (uint32_t)width, box_h, box_w);
     if ((unsigned __int128)n_boxes * units >= ((unsigned __int128)1 << 40) || (unsigned __int128)n_boxes * box_h * box_w * es >= ((unsigned __int128)1 << 62))
         return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: bad sizes n_boxes=%zu", n_boxes);
-    const IndexWs w = index_ws(dtype, g, terse_bytes, n_frames, frame_offsets != nullptr, index != nullptr);
-    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_roi: workspace %zu < %zu", workspace_bytes, w.total);
-    if (w.total && !workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi: null workspace");
-
-    if (w.total) trpx::fused_ws_forget(workspace, workspace_bytes);
-    bool clear = true;
-    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status,
-                                          static_cast<char*>(workspace), w, stream, &clear))
-        return rc;
-    const DecLayout il = idx_layout(g, n_frames, es);
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, 0, nullptr, &w)) return rc;             // (offsets and index given: no workspace at all)
+    if (const int rc = consumer_front(c, w, true, &f)) return rc;
     trpx::RoiArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = n_frames;
+    trpx::set_stack(a, f.stack);
     a.width = (uint32_t)width;
     a.height = (uint32_t)(n_values / width);
     a.boxes = boxes;
@@ -839,45 +886,16 @@ int trpx_decode_roi(int dtype, const uint8_t* terse, size_t terse_bytes, const u
     a.box_h = box_h;
     a.box_w = box_w;
     a.units_per_box = units;
-    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
-    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
     a.out = pixels_out;
     a.status = status;
-    HIP_TRY(trpx::launch_decode_roi(dtype, a, clear, static_cast<hipStream_t>(stream)));
+    HIP_TRY(trpx::launch_decode_roi(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
-
-// ---- threshold decode (decode_sparse.hip) --------------------------------------------------------------------------------
-}  // extern "C"
-namespace {
-// trpx_decode_sparse's workspace: what the missing inputs need (index_ws), then per (frame, group) [counts u32] [flags 4 x u64]
-// [base u32] and per frame [total u32]
-struct SparseWs { IndexWs front; size_t counts, flags, base, frame_total, total; };
-SparseWs sparse_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, bool have_offsets, bool have_index) {
-    SparseWs w;
-    const size_t groups = n_frames * (size_t)g.n_tiles;
-    w.front = index_ws(dtype, g, terse_bytes, n_frames, have_offsets, have_index);
-    w.counts = w.front.total;
-    w.flags = trpx::align_up(w.counts + 4 * groups, 8);
-    w.base = w.flags + 32 * groups;
-    w.frame_total = w.base + 4 * groups;
-    w.total = trpx::align_up(w.frame_total + 4 * n_frames, 8);
-    return w;
-}
-// the rule the device-pointer and the host-pointer entry point share: both outputs, or neither and no capacity (sizes only)
-int sparse_outputs(const char* fn, const void* positions, const void* values, size_t capacity) {
-    if ((positions == nullptr) != (values == nullptr)) return fail(TRPX_ERR_INVALID_ARG, "%s: positions and values go together", fn);
-    if (!positions && capacity) return fail(TRPX_ERR_INVALID_ARG, "%s: capacity %zu without outputs", fn, capacity);
-    return TRPX_OK;
-}
-}  // namespace
-extern "C" {
 
 size_t trpx_decode_sparse_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
     trpx::FrameGeom g;
-    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !geom_of(n_values, block, &g) || !sizes_ok(g, n_frames))
-        return 0;
-    return sparse_ws(dtype, g, terse_bytes, n_frames, false, false).total;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front ? front + sparse_ws(g, n_frames).total : 0;
 }
 
 int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
@@ -890,68 +908,36 @@ int trpx_decode_sparse(int dtype, const uint8_t* terse, size_t terse_bytes, cons
                                   {{terse, 4}, {row_offsets, 8}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
                                    {workspace, 8, false}, {positions, 4, false}, {values, es, false}}, &g))
         return rc;
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse: frames of >= 2^32 bits");
-    if (n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    const Consumer c{"trpx_decode_sparse", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
     if (const int rc = sparse_outputs("trpx_decode_sparse", positions, values, capacity)) return rc;
-    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse: an index needs its frame offsets");
-    if (!workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse: null workspace (the counts live there)");
-    const SparseWs w = sparse_ws(dtype, g, terse_bytes, n_frames, frame_offsets != nullptr, index != nullptr);
-    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sparse: workspace %zu < %zu", workspace_bytes, w.total);
-
-    trpx::fused_ws_forget(workspace, workspace_bytes);
-    char* ws = static_cast<char*>(workspace);
-    bool clear = true;
-    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
-                                          w.front, stream, &clear))
-        return rc;
-    const DecLayout il = idx_layout(g, n_frames, es);
+    const SparseWs own = sparse_ws(g, n_frames);
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, own.total, "the counts live there", &w)) return rc;
+    if (const int rc = consumer_front(c, w, true, &f)) return rc;
     trpx::SparseArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = n_frames;
-    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
-    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    static_cast<trpx::IndexedStack&>(a) = f.stack;
     a.threshold = threshold;
     a.min_width = trpx::sparse_min_width(threshold, trpx_dtype_is_signed(dtype) != 0);
-    a.counts = reinterpret_cast<uint32_t*>(ws + w.counts);
-    a.flags = reinterpret_cast<uint64_t*>(ws + w.flags);
-    a.base = reinterpret_cast<uint32_t*>(ws + w.base);
-    a.frame_total = reinterpret_cast<uint32_t*>(ws + w.frame_total);
+    a.counts = reinterpret_cast<uint32_t*>(f.own + own.counts);
+    a.flags = reinterpret_cast<uint64_t*>(f.own + own.flags);
+    a.base = reinterpret_cast<uint32_t*>(f.own + own.base);
+    a.frame_total = reinterpret_cast<uint32_t*>(f.own + own.frame_total);
     a.row_offsets = row_offsets;
     a.positions = positions;
     a.values = values;
     a.capacity = capacity;
     a.status = status;
-    HIP_TRY(trpx::launch_decode_sparse(dtype, a, clear, static_cast<hipStream_t>(stream)));
+    HIP_TRY(trpx::launch_decode_sparse(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
-// ---- weighted per-frame sums (decode_dot.hip) --------------------------------------------------------------------------------
-}  // extern "C"
-namespace {
-// trpx_decode_dot's workspace: what the missing inputs need (index_ws), then [support: one bit per block of a frame] and per
-// (frame, run of 8 groups, map) [partial sum i64]
-struct DotWs { IndexWs front; size_t support, partials, total; };
-DotWs dot_ws(int dtype, const trpx::FrameGeom& g, size_t terse_bytes, size_t n_frames, unsigned n_maps, bool have_offsets, bool have_index) {
-    DotWs w;
-    w.front = index_ws(dtype, g, terse_bytes, n_frames, have_offsets, have_index);
-    w.support = w.front.total;
-    w.partials = trpx::align_up(w.support + 4 * trpx::dot_support_words(g), 8);
-    w.total = w.partials + 8 * n_frames * (size_t)trpx::dot_runs_per_frame(g) * n_maps;
-    return w;
-}
-bool dot_maps_ok(unsigned n_maps) { return n_maps >= 1 && n_maps <= trpx::kDotMaxMaps; }
-}  // namespace
-extern "C" {
-
 size_t trpx_decode_dot_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned n_maps) {
     trpx::FrameGeom g;
-    if (dtype < TRPX_U8 || dtype > TRPX_I32 || block != kBlock || !terse_bytes || !dot_maps_ok(n_maps) || !geom_of(n_values, block, &g) ||
-        !sizes_ok(g, n_frames))
-        return 0;
-    return dot_ws(dtype, g, terse_bytes, n_frames, n_maps, false, false).total;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && dot_maps_ok(n_maps) ? front + dot_ws(g, n_frames, n_maps).total : 0;
 }
 
 int trpx_decode_dot(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
@@ -963,36 +949,24 @@ int trpx_decode_dot(int dtype, const uint8_t* terse, size_t terse_bytes, const u
                                   {{terse, 4}, {weights, 4}, {dots_out, 8}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
                                    {workspace, 8, false}}, &g))
         return rc;
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot: frames of >= 2^32 bits");
-    if (n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    const Consumer c{"trpx_decode_dot", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
     if (!dot_maps_ok(n_maps)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: n_maps=%u (1..%u)", n_maps, trpx::kDotMaxMaps);
-    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: an index needs its frame offsets");
-    if (!workspace) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot: null workspace (the support bits and the partial sums live there)");
-    const DotWs w = dot_ws(dtype, g, terse_bytes, n_frames, n_maps, frame_offsets != nullptr, index != nullptr);
-    if (workspace_bytes < w.total) return fail(TRPX_ERR_CAPACITY, "trpx_decode_dot: workspace %zu < %zu", workspace_bytes, w.total);
-
-    trpx::fused_ws_forget(workspace, workspace_bytes);
-    char* ws = static_cast<char*>(workspace);
-    bool clear = true;
-    if (const int rc = index_in_workspace(dtype, terse, terse_bytes, &frame_offsets, &index, n_values, n_frames, block, g, status, ws,
-                                          w.front, stream, &clear))
-        return rc;
-    const DecLayout il = idx_layout(g, n_frames, es);
+    const DotWs own = dot_ws(g, n_frames, n_maps);
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, own.total, "the support bits and the partial sums live there", &w)) return rc;
+    if (const int rc = consumer_front(c, w, true, &f)) return rc;
     trpx::DotArgs a{};
-    a.terse = terse;
-    a.terse_bytes = terse_bytes;
-    a.frame_offsets = frame_offsets;
-    a.geom = g;
-    a.n_frames = n_frames;
-    a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + il.tile_off);
-    a.widths = reinterpret_cast<const uint8_t*>(static_cast<const char*>(index) + il.widths);
+    static_cast<trpx::IndexedStack&>(a) = f.stack;
     a.weights = weights;
     a.n_maps = n_maps;
-    a.support = reinterpret_cast<uint32_t*>(ws + w.support);
-    a.partials = reinterpret_cast<int64_t*>(ws + w.partials);
+    a.support = reinterpret_cast<uint32_t*>(f.own + own.support);
+    a.partials = reinterpret_cast<int64_t*>(f.own + own.partials);
     a.dots_out = dots_out;
     a.status = status;
-    HIP_TRY(trpx::launch_decode_dot(dtype, a, clear, static_cast<hipStream_t>(stream)));
+    HIP_TRY(trpx::launch_decode_dot(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -1172,6 +1146,44 @@ int status_slot(uint32_t** d_st) {
     *d_st = static_cast<uint32_t*>(p);
     return TRPX_OK;
 }
+// What every decoding host wrapper stages: the padded stream, the status slot, the offsets slot (offs_slot: wanted at all;
+// uploaded where the caller has them, offs_extra bytes behind them), the output block and the workspace.
+struct Staged { const uint8_t* terse; uint32_t* status; uint64_t* offs; void* out; void* ws; };
+int stage(hipStream_t hs, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_frames, bool offs_slot,
+          size_t offs_extra, size_t out_bytes, size_t ws_bytes, Staged* s) {
+    *s = {};
+    int rc = upload_stream(hs, terse, terse_bytes, &s->terse);
+    if (rc || (rc = status_slot(&s->status)) || (offs_slot && (rc = upload_offsets(hs, frame_offsets, n_frames, offs_extra, &s->offs)))) return rc;
+    if (out_bytes) HIP_TRY(arena().get(Arena::kPixels, out_bytes, &s->out));
+    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &s->ws));
+    return TRPX_OK;
+}
+// what a host wrapper answers for the work it queued on hs: the status block read back (into st), as a return code
+int finish(const char* fn, hipStream_t hs, const uint32_t* d_status, uint32_t st[TRPX_STATUS_WORDS]) {
+    const int rc = read_status(hs, d_status, st);
+    return rc ? rc : status_result(fn, st);
+}
+// what the host wrappers of the index consumers refuse first (own_ok: the wrapper's own pointers and counts)
+int consumer_host_refusals(const char* fn, bool own_ok, int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                           trpx::FrameGeom* g) {
+    if (!own_ok || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "%s: bad argument", fn);
+    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "%s: block=%u dtype=%d", fn, block, dtype);
+    if (!geom_of(n_values, block, g) || !sizes_ok(*g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes", fn);
+    return TRPX_OK;
+}
+// the end of the encoding host wrappers: the offsets back, their total against the caller's room, the stream back
+int download_stream(const char* fn, hipStream_t hs, const uint64_t* d_off, const void* d_out, size_t n_frames, const uint32_t* st, uint8_t* out,
+                    size_t out_capacity, size_t* total_bytes, uint64_t* frame_offsets, uint32_t* prolix_bits) {
+    std::vector<uint64_t> offs(n_frames + 1);
+    HIP_TRY(copy_sync(hs, offs.data(), d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
+    const size_t total = (size_t)offs[n_frames];
+    if (total > out_capacity) return fail(TRPX_ERR_CAPACITY, "%s: need %zu bytes, have %zu", fn, total, out_capacity);
+    HIP_TRY(copy_sync(hs, out, d_out, total, hipMemcpyDeviceToHost));
+    *total_bytes = total;
+    if (frame_offsets) memcpy(frame_offsets, offs.data(), 8 * (n_frames + 1));
+    if (prolix_bits) *prolix_bits = st[1];
+    return TRPX_OK;
+}
 
 // Decode into any output type, everything on the device, the last status block in st.  Same signedness into <= 32 bits: the
 // tuned decoders.  They report CORRUPT for a block wider than the output type, which is also what a legitimately wider stream
@@ -1233,15 +1245,7 @@ int trpx_encode_host(int dtype, const void* pixels, size_t n_values, size_t n_fr
     uint32_t st[TRPX_STATUS_WORDS];
     rc = encode_retrying(dtype, d_px, n_values, n_frames, block, static_cast<uint8_t*>(d_out), cap, d_off, d_st, nullptr, d_ws, ws_bytes, hs, st);
     if (rc || (rc = status_result("trpx_encode_host", st))) return rc;
-    std::vector<uint64_t> offs(n_frames + 1);
-    HIP_TRY(copy_sync(hs, offs.data(), d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
-    const size_t total = (size_t)offs[n_frames];
-    if (total > out_capacity) return fail(TRPX_ERR_CAPACITY, "trpx_encode_host: need %zu bytes, have %zu", total, out_capacity);
-    HIP_TRY(copy_sync(hs, out, d_out, total, hipMemcpyDeviceToHost));
-    *total_bytes = total;
-    if (frame_offsets) memcpy(frame_offsets, offs.data(), 8 * (n_frames + 1));
-    if (prolix_bits) *prolix_bits = st[1];
-    return TRPX_OK;
+    return download_stream("trpx_encode_host", hs, d_off, d_out, n_frames, st, out, out_capacity, total_bytes, frame_offsets, prolix_bits);
 }
 
 int trpx_decode_host(int stream_signed, int out_dtype, const uint8_t* terse, size_t terse_bytes,
@@ -1256,18 +1260,13 @@ int trpx_decode_host(int stream_signed, int out_dtype, const uint8_t* terse, siz
     if (!sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host: bad sizes");
     const size_t out_bytes = n_values * n_frames * es;
     const size_t ws_bytes = trpx_decode_workspace_bytes(TRPX_U8, n_values, n_frames, block);
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_st = nullptr;
-    void *d_out = nullptr, *d_ws = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
-    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
-    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
+    if (rc) return rc;
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = decode_any(stream_signed, out_dtype, d_in, terse_bytes, d_off, n_values, n_frames, block, d_out, d_st, d_ws, ws_bytes, hs, st);
+    rc = decode_any(stream_signed, out_dtype, d.terse, terse_bytes, d.offs, n_values, n_frames, block, d.out, d.status, d.ws, ws_bytes, hs, st);
     if (rc || (rc = status_result("trpx_decode_host", st))) return rc;
-    HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(hs, pixels_out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -1282,17 +1281,13 @@ int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_v
     if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                     // every frame is at least one byte (Terse.hpp:547)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_frame_offsets_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
     const size_t ws_bytes = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_st = nullptr;
-    void* d_ws = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = upload_offsets(hs, nullptr, n_frames, 0, &d_off)) || (rc = status_slot(&d_st))) return rc;
-    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
+    Staged d;                                                                  // (the offsets slot is the output)
+    int rc = stage(hs, terse, terse_bytes, nullptr, n_frames, true, 0, 0, ws_bytes, &d);
+    if (rc) return rc;
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_locate_frames(d_in, terse_bytes, n_values, n_frames, block, max_bits, d_off, d_st, d_ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_frame_offsets_host", st))) return rc;
-    HIP_TRY(copy_sync(hs, frame_offsets, d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
+    rc = trpx_locate_frames(d.terse, terse_bytes, n_values, n_frames, block, max_bits, d.offs, d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_frame_offsets_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, frame_offsets, d.offs, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -1301,25 +1296,19 @@ int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t 
     hipStream_t hs = nullptr;
     if (const int rc = enter("trpx_decode_sum_host", device, &hs)) return rc;
     trpx::FrameGeom g;
-    if (!terse || !sums_out || !terse_bytes || !sum_out_ok(out_dtype) || !group)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad argument");
-    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum_host: block=%u dtype=%d", block, dtype);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad sizes");
+    if (const int rc = consumer_host_refusals("trpx_decode_sum_host", terse && sums_out && sum_out_ok(out_dtype) && group, dtype, terse_bytes, n_values,
+                                              n_frames, block, &g))
+        return rc;
     const size_t ws_bytes = trpx_decode_sum_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group);
     if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad dtype/sizes");
     const size_t out_bytes = (n_frames + group - 1) / group * n_values * sum_out_size(out_dtype);
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_st = nullptr;
-    void *d_out = nullptr, *d_ws = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
-    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
-    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
+    if (rc) return rc;
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_sum(dtype, out_dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, group, d_out, d_st, d_ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_sum_host", st))) return rc;
-    HIP_TRY(copy_sync(hs, sums_out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    rc = trpx_decode_sum(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, group, d.out, d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_sum_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, sums_out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -1328,9 +1317,8 @@ int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
                          unsigned box_w, void* pixels_out, int device) {
     // (the argument checks need no device: they come first)
     trpx::FrameGeom g;
-    if (!terse || !boxes || !pixels_out || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad argument");
-    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_roi_host: block=%u dtype=%d", block, dtype);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad sizes");
+    if (const int rc = consumer_host_refusals("trpx_decode_roi_host", terse && boxes && pixels_out, dtype, terse_bytes, n_values, n_frames, block, &g))
+        return rc;
     if (const int rc = roi_geometry("trpx_decode_roi_host", n_values, width, n_boxes, box_h, box_w)) return rc;
     const size_t ws_bytes = trpx_decode_roi_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
     if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad dtype/sizes");
@@ -1343,21 +1331,16 @@ int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
     hipStream_t hs = nullptr;
     if (const int rc = enter("trpx_decode_roi_host", device, &hs)) return rc;
     const size_t out_bytes = n_boxes * box_h * box_w * trpx_dtype_size(dtype);
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;                                                 // the offsets, then the boxes
-    uint32_t* d_st = nullptr;
-    void *d_out = nullptr, *d_ws = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = status_slot(&d_st)) || (rc = upload_offsets(hs, frame_offsets, n_frames, 12 * n_boxes, &d_off))) return rc;
-    uint32_t* d_boxes = reinterpret_cast<uint32_t*>(d_off + (n_frames + 1));
+    Staged d;                                                                  // (the offsets slot: the offsets, then the boxes)
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, true, 12 * n_boxes, out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    uint32_t* d_boxes = reinterpret_cast<uint32_t*>(d.offs + (n_frames + 1));
     HIP_TRY(copy_sync(hs, d_boxes, boxes, 12 * n_boxes, hipMemcpyHostToDevice));
-    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
-    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_roi(dtype, d_in, terse_bytes, frame_offsets ? d_off : nullptr, nullptr, n_values, n_frames, block, width, d_boxes,
-                         n_boxes, box_h, box_w, d_out, d_st, d_ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_roi_host", st))) return rc;
-    HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    rc = trpx_decode_roi(dtype, d.terse, terse_bytes, frame_offsets ? d.offs : nullptr, nullptr, n_values, n_frames, block, width, d_boxes,
+                         n_boxes, box_h, box_w, d.out, d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_roi_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, pixels_out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -1366,9 +1349,8 @@ int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes,
                             void* values, size_t capacity, size_t* n_found, int device) {
     // (the argument checks need no device: they come first)
     trpx::FrameGeom g;
-    if (!terse || !row_offsets || !n_found || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad argument");
-    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse_host: block=%u dtype=%d", block, dtype);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad sizes");
+    if (const int rc = consumer_host_refusals("trpx_decode_sparse_host", terse && row_offsets && n_found, dtype, terse_bytes, n_values, n_frames, block, &g))
+        return rc;
     const size_t ws_bytes = trpx_decode_sparse_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
     if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad dtype/sizes");
     if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse_host: frames of >= 2^32 bits");
@@ -1379,20 +1361,15 @@ int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes,
     if (const int rc = enter("trpx_decode_sparse_host", device, &hs)) return rc;
     // the outputs in one device block: [row_offsets] [positions] [values]
     const size_t pos_at = trpx::align_up(8 * (n_frames + 1), 16), val_at = trpx::align_up(pos_at + 4 * capacity, 16);
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_st = nullptr;
-    void *d_out = nullptr, *d_ws = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
-    HIP_TRY(arena().get(Arena::kPixels, val_at + es * capacity, &d_out));
-    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
-    char* o = static_cast<char*>(d_out);
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, val_at + es * capacity, ws_bytes, &d);
+    if (rc) return rc;
+    char* o = static_cast<char*>(d.out);
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_sparse(dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, threshold, reinterpret_cast<uint64_t*>(o),
-                            positions ? reinterpret_cast<uint32_t*>(o + pos_at) : nullptr, positions ? o + val_at : nullptr, capacity, d_st,
-                            d_ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d_st, st))) return rc;
+    rc = trpx_decode_sparse(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, threshold, reinterpret_cast<uint64_t*>(o),
+                            positions ? reinterpret_cast<uint32_t*>(o + pos_at) : nullptr, positions ? o + val_at : nullptr, capacity, d.status,
+                            d.ws, ws_bytes, hs);
+    if (rc || (rc = read_status(hs, d.status, st))) return rc;
     if (st[0] && st[0] != TRPX_ERR_CAPACITY) return status_result("trpx_decode_sparse_host", st);
     HIP_TRY(copy_sync(hs, row_offsets, o, 8 * (n_frames + 1), hipMemcpyDeviceToHost));   // (valid when the capacity is too small, too)
     const size_t total = (size_t)row_offsets[n_frames];
@@ -1409,9 +1386,9 @@ int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
                          size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps, int64_t* dots_out, int device) {
     // (the argument checks need no device: they come first)
     trpx::FrameGeom g;
-    if (!terse || !weights || !dots_out || !terse_bytes || !dot_maps_ok(n_maps)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad argument");
-    if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot_host: block=%u dtype=%d", block, dtype);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad sizes");
+    if (const int rc = consumer_host_refusals("trpx_decode_dot_host", terse && weights && dots_out && dot_maps_ok(n_maps), dtype, terse_bytes, n_values,
+                                              n_frames, block, &g))
+        return rc;
     const size_t ws_bytes = trpx_decode_dot_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_maps);
     if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad dtype/sizes");
     if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot_host: frames of >= 2^32 bits");
@@ -1419,20 +1396,15 @@ int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
     if (const int rc = enter("trpx_decode_dot_host", device, &hs)) return rc;
     // the maps and the sums in one device block: [weights] [dots]
     const size_t w_bytes = 4 * (size_t)n_maps * n_values, out_at = trpx::align_up(w_bytes, 16), out_bytes = 8 * n_frames * (size_t)n_maps;
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_st = nullptr;
-    void *d_out = nullptr, *d_ws = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = status_slot(&d_st)) || (frame_offsets && (rc = upload_offsets(hs, frame_offsets, n_frames, 0, &d_off)))) return rc;
-    HIP_TRY(arena().get(Arena::kPixels, out_at + out_bytes, &d_out));
-    HIP_TRY(arena().get(Arena::kWorkspace, ws_bytes, &d_ws));
-    char* o = static_cast<char*>(d_out);
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_at + out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    char* o = static_cast<char*>(d.out);
     HIP_TRY(copy_sync(hs, o, weights, w_bytes, hipMemcpyHostToDevice));
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_dot(dtype, d_in, terse_bytes, d_off, nullptr, n_values, n_frames, block, reinterpret_cast<const int32_t*>(o), n_maps,
-                         reinterpret_cast<int64_t*>(o + out_at), d_st, d_ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_decode_dot_host", st))) return rc;
+    rc = trpx_decode_dot(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const int32_t*>(o), n_maps,
+                         reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_dot_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, dots_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
@@ -1479,16 +1451,8 @@ int trpx_encode_sparse_host(int dtype, const uint64_t* row_offsets, const uint32
     rc = trpx_encode_sparse(dtype, reinterpret_cast<const uint64_t*>(in), n_events ? reinterpret_cast<const uint32_t*>(in + pos_at) : nullptr,
                             n_events ? in + val_at : nullptr, n_events, n_values, n_frames, block, static_cast<uint8_t*>(d_out), cap, d_off,
                             d_st, d_ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d_st, st)) || (rc = status_result("trpx_encode_sparse_host", st))) return rc;
-    std::vector<uint64_t> offs(n_frames + 1);
-    HIP_TRY(copy_sync(hs, offs.data(), d_off, 8 * (n_frames + 1), hipMemcpyDeviceToHost));
-    const size_t total = (size_t)offs[n_frames];
-    if (total > out_capacity) return fail(TRPX_ERR_CAPACITY, "trpx_encode_sparse_host: need %zu bytes, have %zu", total, out_capacity);
-    HIP_TRY(copy_sync(hs, out, d_out, total, hipMemcpyDeviceToHost));
-    *total_bytes = total;
-    if (frame_offsets) memcpy(frame_offsets, offs.data(), 8 * (n_frames + 1));
-    if (prolix_bits) *prolix_bits = st[1];
-    return TRPX_OK;
+    if (rc || (rc = finish("trpx_encode_sparse_host", hs, d_st, st))) return rc;
+    return download_stream("trpx_encode_sparse_host", hs, d_off, d_out, n_frames, st, out, out_capacity, total_bytes, frame_offsets, prolix_bits);
 }
 
 int trpx_group_states_host(const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
@@ -1503,18 +1467,13 @@ int trpx_group_states_host(const uint8_t* terse, size_t terse_bytes, const uint6
         return fail(TRPX_ERR_INVALID_ARG, "trpx_group_states_host: bad sizes");
     const int dtype = max_bits <= 8 ? TRPX_U8 : max_bits <= 16 ? TRPX_U16 : TRPX_U32;
     const size_t ib = trpx_index_bytes(dtype, n_values, n_frames, block), ng = n_frames * (size_t)g.n_tiles;
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;                                                 // the offsets, then the states
-    uint32_t* d_st = nullptr;
-    void* d_idx = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = upload_offsets(hs, frame_offsets, n_frames, 8 * ng, &d_off)) || (rc = status_slot(&d_st))) return rc;
-    HIP_TRY(arena().get(Arena::kWorkspace, ib, &d_idx));
-    uint64_t* d_states = d_off + (n_frames + 1);
+    Staged d;                                                                  // (the offsets slot: the offsets, then the states; the workspace: the index)
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, true, 8 * ng, 0, ib, &d);
+    if (rc) return rc;
+    uint64_t* d_states = d.offs + (n_frames + 1);
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_build_index(dtype, d_in, terse_bytes, d_off, n_values, n_frames, block, d_idx, d_st, hs);
-    if (rc || (rc = trpx_index_group_states(d_idx, n_values, n_frames, block, d_states, hs)) || (rc = read_status(hs, d_st, st)) ||
-        (rc = status_result("trpx_group_states_host", st)))
+    rc = trpx_build_index(dtype, d.terse, terse_bytes, d.offs, n_values, n_frames, block, d.ws, d.status, hs);
+    if (rc || (rc = trpx_index_group_states(d.ws, n_values, n_frames, block, d_states, hs)) || (rc = finish("trpx_group_states_host", hs, d.status, st)))
         return rc;
     HIP_TRY(copy_sync(hs, group_states, d_states, 8 * ng, hipMemcpyDeviceToHost));
     return TRPX_OK;
@@ -1534,25 +1493,20 @@ int trpx_decode_host_grouped(int stream_signed, int out_dtype, const uint8_t* te
     if (!terse || !terse_bytes || !pixels_out) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_host_grouped: bad argument");
     const size_t out_bytes = n_values * n_frames * trpx_dtype_size(out_dtype), ng = n_frames * (size_t)g.n_tiles;
     const size_t ib = trpx_index_bytes(out_dtype, n_values, n_frames, block);
-    const uint8_t* d_in = nullptr;
-    uint64_t* d_off = nullptr;                                                 // the offsets, then the states
-    uint32_t* d_st = nullptr;
-    void *d_out = nullptr, *d_idx = nullptr;
-    int rc = upload_stream(hs, terse, terse_bytes, &d_in);
-    if (rc || (rc = upload_offsets(hs, frame_offsets, n_frames, 8 * ng, &d_off)) || (rc = status_slot(&d_st))) return rc;
-    HIP_TRY(arena().get(Arena::kPixels, out_bytes, &d_out));
-    HIP_TRY(arena().get(Arena::kWorkspace, ib, &d_idx));
-    uint64_t* d_states = d_off + (n_frames + 1);
+    Staged d;                                                                  // (the offsets slot: the offsets, then the states; the workspace: the index)
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, true, 8 * ng, out_bytes, ib, &d);
+    if (rc) return rc;
+    uint64_t* d_states = d.offs + (n_frames + 1);
     HIP_TRY(copy_sync(hs, d_states, group_states, 8 * ng, hipMemcpyHostToDevice));
     uint32_t st[TRPX_STATUS_WORDS];
     bool decoded = false;
-    rc = decode_walk_free(stream_signed, out_dtype, d_in, terse_bytes, d_off, d_states, n_values, n_frames, block, d_idx, d_out, d_st, hs,
+    rc = decode_walk_free(stream_signed, out_dtype, d.terse, terse_bytes, d.offs, d_states, n_values, n_frames, block, d.ws, d.out, d.status, hs,
                           false, st, &decoded);
     if (rc) return rc;
     if (!decoded)                      // the states do not describe this stream (or the data are wider than the output type): general route
         return trpx_decode_host(stream_signed, out_dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block, pixels_out, device);
     if ((rc = status_result("trpx_decode_host_grouped", st))) return rc;
-    HIP_TRY(copy_sync(hs, pixels_out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_sync(hs, pixels_out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 
@@ -1625,7 +1579,7 @@ int trpx_stack_open(trpx_stack** handle, int stream_signed, const uint8_t* terse
         int rc = trpx_locate_frames(static_cast<const uint8_t*>(s->d_terse), terse_bytes, n_values, n_frames, block,
                                     max_bits ? max_bits : 32, static_cast<uint64_t*>(s->d_offs),
                                     static_cast<uint32_t*>(s->d_status), d_lws, lb, hs);
-        if (rc || (rc = read_status(hs, static_cast<uint32_t*>(s->d_status), st)) || (rc = status_result("trpx_stack_open", st))) { stack_free(s); return rc; }
+        if (rc || (rc = finish("trpx_stack_open", hs, static_cast<uint32_t*>(s->d_status), st))) { stack_free(s); return rc; }
         if ((e = copy_sync(hs, s->offs.data(), s->d_offs, 8 * (n_frames + 1), hipMemcpyDeviceToHost)) != hipSuccess) return bail(e, "hipMemcpy(offsets)");
     }
     if (group_states && block == kBlock) {   // row f1: the file carried its group states

@@ -24,6 +24,22 @@ struct FrameGeom {
     uint32_t block;      // values per codec block: 12 on every tuned path; the generic kernels take any value
 };
 
+// A stack with its decode index, read only: what every consumer of the index takes (trpx_decode_sum / _roi / _sparse / _dot).
+// api.hip's consumer_front fills it; SparseArgs and DotArgs derive from it, SumArgs and RoiArgs hold its fields in their own order.
+struct IndexedStack {
+    const uint8_t*  terse;
+    uint64_t        terse_bytes;
+    const uint64_t* frame_offsets;  // n_frames + 1
+    FrameGeom       geom;
+    uint64_t        n_frames;
+    const uint8_t*  widths;         // decode index: width of every block
+    const uint64_t* tile_off;       // decode index: frame-relative bit offset of every 256-block group
+};
+template <class Args> inline void set_stack(Args& a, const IndexedStack& s) {
+    a.terse = s.terse; a.terse_bytes = s.terse_bytes; a.frame_offsets = s.frame_offsets; a.geom = s.geom; a.n_frames = s.n_frames;
+    a.widths = s.widths; a.tile_off = s.tile_off;
+}
+
 template <typename T> struct PixelTraits;
 template <> struct PixelTraits<uint8_t>  { using U = uint8_t;  static constexpr int bits = 8;  static constexpr bool is_signed = false; static constexpr int dtype = TRPX_U8; };
 template <> struct PixelTraits<int8_t>   { using U = uint8_t;  static constexpr int bits = 8;  static constexpr bool is_signed = true;  static constexpr int dtype = TRPX_I8; };

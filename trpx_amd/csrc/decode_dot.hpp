@@ -10,14 +10,7 @@ namespace trpx {
 
 constexpr uint32_t kDotMaxMaps = 16;
 
-struct DotArgs {
-    const uint8_t*  terse;
-    uint64_t        terse_bytes;
-    const uint64_t* frame_offsets;  // n_frames + 1
-    FrameGeom       geom;
-    uint64_t        n_frames;
-    const uint8_t*  widths;         // decode index: width of every block
-    const uint64_t* tile_off;       // decode index: frame-relative bit offset of every 256-block group
+struct DotArgs : IndexedStack {
     const int32_t*  weights;        // [n_maps][n_values]
     uint32_t        n_maps;
     uint32_t*       support;        // workspace, dot_support_words(): bit b = some map is non-zero on block b of a frame

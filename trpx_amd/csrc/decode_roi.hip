@@ -47,7 +47,8 @@ __device__ __forceinline__ void roi_unit(const RoiArgs& a, uint64_t unit) {
     // ---- widths -> bit offsets inside the group -> the group against the frame and the next group (group_front.hpp)
     uint32_t w[kGroupRows], off[kGroupRows], nb[kGroupRows];   // off: the block's first PAYLOAD bit, group-relative
     uint64_t fo, t_off;
-    if (!group_front<T>(w, off, nb, fo, t_off, a.widths, a.tile_off, a.frame_offsets, g, a.terse_bytes, frame, grp, lane)) {
+    const IndexedStack stack{a.terse, a.terse_bytes, a.frame_offsets, g, a.n_frames, a.widths, a.tile_off};
+    if (!group_front<T>(w, off, nb, fo, t_off, stack, frame, grp, lane)) {
         if (lane == 0) atomicMax(&a.status[0], kStatusCorrupt);
         return;
     }

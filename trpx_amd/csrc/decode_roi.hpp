@@ -11,6 +11,7 @@ namespace trpx {
 // geometry alone, never from the boxes' contents; the surplus units of a box exit.
 uint32_t roi_units_per_box(const FrameGeom& g, uint32_t width, uint32_t box_h, uint32_t box_w);
 
+// (the fields of IndexedStack in an order of its own, filled by set_stack: the layout k_decode_roi was measured with, LABNOTES.md 15)
 struct RoiArgs {
     const uint8_t*  terse;
     uint64_t        terse_bytes;

@@ -8,14 +8,7 @@
 
 namespace trpx {
 
-struct SparseArgs {
-    const uint8_t*  terse;
-    uint64_t        terse_bytes;
-    const uint64_t* frame_offsets;  // n_frames + 1
-    FrameGeom       geom;
-    uint64_t        n_frames;
-    const uint8_t*  widths;         // decode index: width of every block
-    const uint64_t* tile_off;       // decode index: frame-relative bit offset of every 256-block group
+struct SparseArgs : IndexedStack {
     int64_t         threshold;
     uint32_t        min_width;      // blocks narrower than this cannot hold an event (0: any block can)
     uint32_t*       counts;         // workspace, per (frame, group): events

@@ -23,6 +23,8 @@ struct SumPlan {
 };
 SumPlan sum_plan(int dtype, const FrameGeom& g, uint64_t n_frames, uint64_t group);
 
+// (the fields of IndexedStack in an order of its own, filled by set_stack: with the view as a base class k_sum_tiles' argument
+// loads moved and every call took 1 % longer, LABNOTES.md 15)
 struct SumArgs {
     const uint8_t*  terse;
     uint64_t        terse_bytes;

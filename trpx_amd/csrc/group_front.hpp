@@ -72,22 +72,22 @@ __device__ __forceinline__ bool group_offsets(uint32_t (&off)[kGroupRows], const
     return !bad;
 }
 
-// Group grp of frame `frame` from the decode index, both steps: w, nb, off as above; fo = the frame's first byte, t_off = the
+// Group grp of frame `frame` of the stack a, both steps: w, nb, off as above; fo = the frame's first byte, t_off = the
 // group's first bit in the frame.  False: the caller gives the verdict.  All 64 lanes call it.
 template <typename T>
 __device__ __forceinline__ bool group_front(uint32_t (&w)[kGroupRows], uint32_t (&off)[kGroupRows], uint32_t (&nb)[kGroupRows],
-                                            uint64_t& fo, uint64_t& t_off, const uint8_t* __restrict__ widths,
-                                            const uint64_t* __restrict__ tile_off, const uint64_t* __restrict__ frame_offsets,
-                                            const FrameGeom& g, uint64_t terse_bytes, uint64_t frame, uint32_t grp, uint32_t lane) {
+                                            uint64_t& fo, uint64_t& t_off, const IndexedStack& a, uint64_t frame, uint32_t grp,
+                                            uint32_t lane) {
+    const FrameGeom& g = a.geom;
     const uint64_t ti = frame * g.n_tiles + grp;
     const bool last = grp + 1 == g.n_tiles;
-    fo = frame_offsets[frame];
-    const uint64_t fe = frame_offsets[frame + 1];
-    t_off = tile_off[ti];
-    const uint64_t t_next = last ? 0 : tile_off[ti + 1];
+    fo = a.frame_offsets[frame];
+    const uint64_t fe = a.frame_offsets[frame + 1];
+    t_off = a.tile_off[ti];
+    const uint64_t t_next = last ? 0 : a.tile_off[ti + 1];
     uint32_t wp0[kGroupRows];
-    group_load_widths(w, nb, wp0, widths + frame * g.n_blocks, g, grp, lane);
-    return group_offsets<T>(off, w, nb, wp0, fo, fe, t_off, t_next, last, terse_bytes, lane);
+    group_load_widths(w, nb, wp0, a.widths + frame * g.n_blocks, g, grp, lane);
+    return group_offsets<T>(off, w, nb, wp0, fo, fe, t_off, t_next, last, a.terse_bytes, lane);
 }
 
 // Where a validated group's payload is read from: the dwords of the stream from the frame's first on (terse is 4-byte aligned).

@@ -35,9 +35,8 @@ struct Run {
     uint32_t g0, n;
     const uint8_t* __restrict__ wf;
 };
-// where the run lies (arithmetic only) ...  (Args: geom, widths, frame_offsets, tile_off)
-template <class Args>
-__device__ __forceinline__ Run run_place(const Args& a, uint64_t run, uint32_t runs_per_frame) {
+// where the run lies (arithmetic only) ...
+__device__ __forceinline__ Run run_place(const IndexedStack& a, uint64_t run, uint32_t runs_per_frame) {
     const FrameGeom& g = a.geom;
     Run r;
     r.frame = run / runs_per_frame;
@@ -48,8 +47,7 @@ __device__ __forceinline__ Run run_place(const Args& a, uint64_t run, uint32_t r
     return r;
 }
 // ... and what is loaded once for it
-template <class Args>
-__device__ __forceinline__ void run_load(Run& r, const Args& a, uint32_t lane) {
+__device__ __forceinline__ void run_load(Run& r, const IndexedStack& a, uint32_t lane) {
     r.fo = a.frame_offsets[r.frame];
     r.fe = a.frame_offsets[r.frame + 1];
     r.my_off = lane <= r.n && r.g0 + lane < a.geom.n_tiles ? a.tile_off[r.u0 + lane] : 0ull;

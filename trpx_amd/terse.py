@@ -163,8 +163,7 @@ class Terse:
         # a window of frames is expanded per device call and a call normally only copies its frame back
         if self._stack is None or self._stack_len != len(self._data):
             self._drop_stack()
-            buf = np.frombuffer(self._data, np.uint8)
-            offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+            buf, offs = self._stream_and_offsets()
             h = C.c_void_p()
             gs = self._states()
             check(lib().trpx_stack_open(C.byref(h), int(self._signed), buf.ctypes.data, buf.size, offs.ctypes.data,
@@ -219,8 +218,7 @@ class Terse:
         """Decode every frame in ONE GPU call; returns [n_frames, size]."""
         f = self.number_of_frames()
         out = np.empty((f, self._size), np.dtype(dtype))
-        buf = np.frombuffer(self._data, np.uint8)
-        offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+        buf, offs = self._stream_and_offsets()
         gs = self._states()
         check(lib().trpx_decode_host_grouped(int(self._signed), _code(dtype, True), buf.ctypes.data, buf.size, offs.ctypes.data,
                                              gs.ctypes.data if gs is not None else None, self._size, f, self._block,
@@ -242,11 +240,14 @@ class Terse:
         out = np.empty((-(-f // group) if f else 0, self._size), np.dtype(dtype))
         if f == 0:
             return out
-        buf = np.frombuffer(self._data, np.uint8)
-        offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+        buf, offs = self._stream_and_offsets()
         check(lib().trpx_decode_sum_host(stream, _code(dtype, True), buf.ctypes.data, buf.size, offs.ctypes.data, self._size,
                                          f, self._block, group, out.ctypes.data, self._device))
         return out
+
+    def _stream_and_offsets(self):
+        """The stream and its frame offsets as the host entry points take them: (uint8 array, uint64 [frames + 1])."""
+        return np.frombuffer(self._data, np.uint8), np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
 
     def _stream_type(self, what: str):
         """The narrowest stream type that holds the object's values: (dtype code, numpy dtype)."""
@@ -274,8 +275,7 @@ class Terse:
         if b.shape[0] == 0:
             return out
         b32 = np.ascontiguousarray(b, dtype=np.uint32)
-        buf = np.frombuffer(self._data, np.uint8)
-        offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+        buf, offs = self._stream_and_offsets()
         check(lib().trpx_decode_roi_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, self.number_of_frames(),
                                          self._block, width, b32.ctypes.data, b32.shape[0], h, w, out.ctypes.data, self._device))
         return out
@@ -299,8 +299,7 @@ class Terse:
         rows = np.zeros(f + 1, np.uint64)
         pos, val = np.empty(0, np.uint32), np.empty(0, dt)
         if f:
-            buf = np.frombuffer(self._data, np.uint8)
-            offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+            buf, offs = self._stream_and_offsets()
             found = C.c_size_t(0)
 
             def call(p, v, cap):
@@ -338,8 +337,7 @@ class Terse:
         f = self.number_of_frames()
         out = np.zeros((f, w.shape[0]), np.int64)
         if f:
-            buf = np.frombuffer(self._data, np.uint8)
-            offs = np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
+            buf, offs = self._stream_and_offsets()
             check(lib().trpx_decode_dot_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f, self._block,
                                              w.ctypes.data, w.shape[0], out.ctypes.data, self._device))
         return out
