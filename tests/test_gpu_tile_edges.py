@@ -1,17 +1,19 @@
 """GPU tests: stream edges of the tiled decoders -- k_unpack_tiles and k_sum_tiles, which are assembled from the tile front end of
 unpack_tile.hpp, and k_decode_roi, which keeps a front end of its own and shares only the helpers of codec_common.hpp: a
-stream whose device base is 4-byte but not 16-byte aligned (the dword-by-dword window loads), and a stream whose buffer ends
-exactly at its last byte (the last 16-byte load of the last tile is the guarded one).  3 frames of 12 * 1024 + 5 values: one
-full tile of k_unpack_tiles, two of the summing kernel, and a partial last block.  The truth is the original pixels and their
+stream whose device base is 4-byte but not 16-byte aligned (the dword-by-dword window loads; at 4, 8 and 12 mod 16), and a stream
+whose buffer ends exactly at its last byte (the last 16-byte load of the last tile is the guarded one).  3 frames of
+12 * 1024 + 5 values: one full tile of k_unpack_tiles, two of the summing kernel, and a partial last block.  The truth is the original pixels and their
 numpy int64 sums: the codec is lossless, so no decoder is trusted.
 
-What each case can tell: "base4" is the one that discriminates -- a decoder that took the 16-byte loads there would read
-misaligned and return wrong pixels.  "exact_end" runs the guarded last load on a buffer of exactly the stream's bytes and checks
-its values; it cannot tell a guarded load from an unguarded one, because the allocator rounds the block up and the bytes behind
+What each case can tell: "base4", "base8" and "base12" are the ones that discriminate -- a decoder that took the 16-byte loads
+there would read misaligned and return wrong pixels, and the bytes behind align4(total) are 0xFF (tests/alignment.py:
+carve_stream), so a load that crosses the stream's end and is used returns wrong pixels too.  "exact_end" runs the guarded
+last load on a buffer of exactly the stream's bytes and checks its values; it cannot tell a guarded load from an unguarded one, because the allocator rounds the block up and the bytes behind
 the stream are mapped (the same holds for every test that passes enc.stack())."""
 import numpy as np
 import pytest
 
+from alignment import carve_stream
 from test_gpu_decode_sum import _encode, _random, _to_np, truth
 
 pytestmark = pytest.mark.gpu
@@ -31,15 +33,16 @@ def stack(request):
     s = enc.stack()
     total = s.numel()
     assert total == enc.total_bytes()
-    room = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
-    room[4:4 + total] = s
-    off4 = room[4:4 + total]                             # 4 bytes into a larger buffer
-    exact = s.clone()                                    # a buffer of its own that ends with the stream
-    assert off4.data_ptr() % 16 == 4 and exact.numel() == total
-    return px, enc, {"base4": off4, "exact_end": exact}
+    streams = {}
+    for off in (4, 8, 12):                               # that far into a larger buffer, 0xFF behind align4(total)
+        streams[f"base{off}"], _, _ = carve_stream(s, off)
+        assert streams[f"base{off}"].data_ptr() % 16 == off and streams[f"base{off}"].numel() == total
+    streams["exact_end"] = s.clone()                     # a buffer of its own that ends with the stream
+    assert streams["exact_end"].numel() == total
+    return px, enc, streams
 
 
-CASES = ["base4", "exact_end"]
+CASES = ["base4", "base8", "base12", "exact_end"]
 
 
 @pytest.mark.parametrize("case", CASES)
