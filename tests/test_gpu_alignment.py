@@ -44,7 +44,7 @@ position-parallel locator takes (4), so the form without offsets is Walk::kSeria
   sum / roi / sparse / dot   index given: their own kernels alone; otherwise plan_index as build_index (and the serial locator)
 
 The stream-base tests run the same calls with the stream at 4, 8, 12 and 68 mod 128 (mod 16: 4, 8, 12, 4) and an aligned
-output, so that (base & 15) != 0 takes the guarded dword fills of every window (decode_frame.hip, decode_part.hip, walk_lds.hpp,
+output, so that (base & 15) != 0 takes the guarded dword fills of every window (decode_frame.hip, part_walk.hpp, walk_lds.hpp,
 unpack_tile.hpp) in place of the LDS-DMA / 16-byte ones."""
 import contextlib
 import functools

@@ -1351,7 +1351,8 @@ def _banded(px, rows, width, period, band, rng):
 @pytest.mark.parametrize("dtype,rows,width,frames", [(np.uint16, 1030, 1065, 6), (np.int32, 1211, 997, 3), (np.uint8, 2048, 2048, 2),
                                                        (np.int16, 613, 1999, 33)])
 def test_large_frames_are_cut_into_parts(gpu, oracle, dtype, rows, width, frames):
-    """Frames of more than 32 K blocks take the per-frame decoder part by part (decode_part.hip: start states inside runs of
+    """Frames of more than 32 K blocks are cut into parts (decode_part.hip, the index route; under selector 4
+    decode_part_sel4.hip, round 4's parts route; both on part_walk.hpp: start states inside runs of
     equal widths, a counting walk per part, repairs of the links that did not close, the part table).  Run-dominated frames,
     frames with header-dense bands (cuts without a run to start in, parts that are too dense: the frame falls back to the
     position-parallel walk), a frame of noise; pixel counts that are no multiple of 12, frames that start anywhere in the
@@ -1384,7 +1385,7 @@ def test_large_frames_are_cut_into_parts(gpu, oracle, dtype, rows, width, frames
     torch.cuda.synchronize()
     assert int(st[0].item()) == 0
     assert torch.equal(back.view(torch.uint8), px.view(torch.uint8).reshape(frames, -1))
-    # round 4's parts route (two walks; its header-dense frames are listed for the position-parallel walk, whose launches for a
+    # round 4's parts route (decode_part_sel4.hip: two walks; its header-dense frames are listed for the position-parallel walk, whose launches for a
     # list are one persistent kernel since round 5: k_seg_fallback) must give the same pixels
     from trpx_amd import _lib
     try:
@@ -1405,7 +1406,8 @@ def test_large_frames_are_cut_into_parts(gpu, oracle, dtype, rows, width, frames
 
 
 def test_large_frames_every_part_link_repaired(gpu, oracle, tmp_path):
-    """The same route in a test build whose cuts never find a run to start in (make weakparts: -DTRPX_PART_FORCE_WEAK):
+    """Both routes in a test build whose cuts never find a run to start in (make weakparts: -DTRPX_PART_FORCE_WEAK, decode_part.hip
+    and decode_part_sel4.hip):
     every part starts on a chain that is not the frame's, every link is open, and k_part_repair has to count every part
     again from the true state up to the checkpoint where the chains have merged.  The frames change their width every 16
     blocks (a chain that is not the frame's merges at an explicit header it meets on a block start; in a frame of long runs

@@ -1,4 +1,4 @@
-"""Verdicts of k_part_resolve (decode_part.hip) for a leg: `TRPX_LIB=tools/variants/libtrpx_partstats.so python3 tools/part_stats.py <leg>`."""
+"""Verdicts of k_part_resolve (decode_part_sel4.hip) for a leg: `TRPX_LIB=tools/variants/libtrpx_partstats.so python3 tools/part_stats.py <leg>`."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -227,9 +227,6 @@ trpx::PlanInput plan_input(trpx::Entry entry, int dtype, size_t es, const trpx::
 #ifdef TRPX_CHAIN_EXTRACT_TILES
     in.chain_extract = TRPX_CHAIN_EXTRACT_TILES;                               // (make chainextract)
 #endif
-#ifdef TRPX_INDEXED_LARGE_TILES
-    in.indexed_large_tiles = true;
-#endif
 #ifdef TRPX_DIAGNOSTICS
     static const bool no_defer = getenv("TRPX_NO_DEFER") != nullptr;
     static const bool lds_walk = getenv("TRPX_WALK") && strcmp(getenv("TRPX_WALK"), "lds") == 0;

@@ -154,12 +154,6 @@ struct DenseLink {
     }
 };
 
-#ifdef TRPX_DENSE_STAMPS
-// diagnostic build (tools/r6_variant.sh ... -DTRPX_DENSE_STAMPS): per-frame phase times (10 ns ticks) folded into the status block --
-// [3] max total, [4] max link, [5] sum of link / 16, [6] sum of total / 16, [7] max spec
-#define TRPX_DENSE_STAMP_PRINT() do { if (threadIdx.x == 0) { const uint32_t tot = (uint32_t)(__builtin_amdgcn_s_memrealtime() - st_t0), lnk = (uint32_t)(st_t2 - st_t1); \
-    atomicMax(&status[3], tot); atomicMax(&status[4], lnk); atomicAdd(&status[5], lnk >> 4); atomicAdd(&status[6], tot >> 4); atomicMax(&status[7], (uint32_t)(st_t1 - st_t0)); (void)st_t3; (void)st_depths; } } while (0)
-#endif
 template <uint32_t W>
 __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const uint8_t* __restrict__ terse, uint64_t terse_bytes,
                                                             const uint64_t* __restrict__ frame_offsets, FrameGeom g, uint32_t max_w,
@@ -204,11 +198,6 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
     DenseRec* const rec = rec_all + seg0 * kDenseSlots;
     uint64_t* const g_out = out_all + seg0;
 
-#ifdef TRPX_DENSE_STAMPS
-    const uint64_t st_t0 = __builtin_amdgcn_s_memrealtime();
-    uint64_t st_t1 = 0, st_t2 = 0, st_t3 = 0;
-    uint32_t st_depths = 0;
-#endif
     // ---- spec: every lane walks its region from a guess ------------------------------------------------------------------------
     const bool walks = j < jl;
     uint64_t in = seg_pack(j * c.L, 0u);
@@ -251,10 +240,6 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
     g_out[j] = out; s_cnt[j] = walks ? n : 0u; s_bnd[j] = B;
     __syncthreads();
 
-#ifdef TRPX_DENSE_STAMPS
-    st_t1 = __builtin_amdgcn_s_memrealtime();
-
-#endif
     // ---- link: on from the OUT state into the regions behind, until the chain meets the walk of the lane that owns the region ----
     // (the lane's windows simply go on: with L a multiple of the window advance the grids of all regions coincide, window t of this
     // lane is window t - (s - j) L / 768 of region s)
@@ -273,16 +258,9 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
         const uint32_t t_start = ~wave_max(~t_mine);
         if (t_start != 0xFFFFFFFFu)
             seg_walk<false, DenseLink>(c, win, 64u * k, hk.have && !done2, end2, false, pos, w, n, nullptr, nullptr, bad, nullptr, &hk, t_start);
-#ifdef TRPX_DENSE_STAMPS
-        st_depths = hk.depth;
-#endif
     }
     __syncthreads();
 
-#ifdef TRPX_DENSE_STAMPS
-    st_t2 = __builtin_amdgcn_s_memrealtime();
-
-#endif
     // ---- resolve: the true walk of every region, its first block, its start state ---------------------------------------------------
     uint32_t tbl = kDenseIdent, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
     DenseRec r1{}, r2{}, r3{}, r4{}, r5{}, r6{};
@@ -334,9 +312,6 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
     if (lane == 0u) t_in = k > 0u ? s_exit[k - 1u] : 0ull;
     if (j == 0u) t_in = 0ull;
 
-#ifdef TRPX_DENSE_STAMPS
-    st_t3 = __builtin_amdgcn_s_memrealtime();
-#endif
     // ---- write (and, for a frame that does not close, the serial walk) ----------------------------------------------------------------
     for (uint32_t attempt = 0; attempt < 2u; ++attempt) {
         const bool serial = attempt == 1u;
@@ -368,9 +343,6 @@ __global__ __launch_bounds__(64 * W, W >= 4 ? 1 : 2) void k_dense_frames(const u
             __syncthreads();
         }
     }
-#ifdef TRPX_DENSE_STAMPS
-    TRPX_DENSE_STAMP_PRINT();
-#endif
 }
 
 hipError_t launch_dense_listed(const DecodeArgs& a, uint32_t max_w, void* dense_ws, const uint32_t* list, hipStream_t st) {

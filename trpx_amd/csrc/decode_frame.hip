@@ -27,40 +27,25 @@
 
 namespace trpx {
 
-#ifndef TRPX_FRAME_WAVES
-#define TRPX_FRAME_WAVES 4
-#endif
-constexpr int kFrameWaves = TRPX_FRAME_WAVES;           // waves per workgroup: 1 walker + the extraction waves
+constexpr int kFrameWaves = 4;           // waves per workgroup: 1 walker + the extraction waves
 constexpr int kFrameThreads = kFrameWaves * kWave;
 
-#ifndef TRPX_FRAME_CHUNK_DW
-#define TRPX_FRAME_CHUNK_DW 2048
-#endif
 #ifndef TRPX_IDX_TOUCH
 #define TRPX_IDX_TOUCH 1        // MODE 1: the filler touches the stream lines of the super-step it has just laid out (A/B: make idxtouch)
 #endif
 template <typename T>
 struct FrameCfg {
-#ifdef TRPX_FRAME_GPW
-    static constexpr int kGpw = TRPX_FRAME_GPW;
-#else
     static constexpr int kGpw = 4;                                       // 64-block groups per extraction wave and super-step (LDS: 20 KB per workgroup, 24.6 KB for 32-bit pixels)
-#endif
     static constexpr int kStepGroups = (kFrameWaves - 1) * kGpw;
     static constexpr int kStepBlocks = kStepGroups * kWave;              // 768 / 1152
     // walker's stream window: 8 KB.  Stream cache-resident (decode after decode): 2 / 4 / 8 / 16 KB -> 0.31 / 0.32 / 0.30 /
     // 0.30 ms; cold (decode after an encode, the bench's round trip): 0.40 / 0.37 / 0.35 / 0.40 ms -- the extraction waves
     // re-read the window's lines from L2, and 250 workgroups per XCD x 16 KB is all of its 4 MB
-    static constexpr int kChunkDw = TRPX_FRAME_CHUNK_DW;
+    static constexpr int kChunkDw = 2048;
     // Pixels leave through the extraction wave's LDS row, 16 bytes per lane and store: every store instruction writes whole
     // 128-byte lines.  (Lane-owned 24-byte runs as 16 + 8 byte stores leave every line to be merged from two instructions in
     // L2; with 2048 frames in flight lines were written back half merged -- WRITE_SIZE 1.17 x the pixels -- and the kernel fell
-    // from 0.26 to 0.38 ms.  TRPX_DEC_DIRECT_STORES: the round-2 stores for 8/16-bit pixels, A/B only.)
-#ifdef TRPX_DEC_DIRECT_STORES
-    static constexpr bool kOutStaged = sizeof(T) == 4;
-#else
-    static constexpr bool kOutStaged = true;
-#endif
+    // from 0.26 to 0.38 ms.)
     static constexpr int kRawDw = 4 * RawQuads<T>::n;                    // stream dwords a lane loads for its block
     static constexpr int kOutDw = kWave * kBlock * (int)sizeof(T) / 4;   // an extraction wave's output row: 64 blocks of pixels
     static_assert(kChunkDw % (kWave * 4) == 0, "window = whole 1 KB pieces");
@@ -96,12 +81,8 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
     __shared__ uint32_t s_pos[2][kPosEntries];
     uint32_t* const s_posx = &s_pos[0][0];
     constexpr uint32_t kPosBits = 26, kPosMask = (1u << kPosBits) - 1u;
-    __shared__ __attribute__((aligned(16))) uint32_t s_out[kFrameWaves - 1][Cfg::kOutStaged ? Cfg::kOutDw + kStageCarryDw : 4];  // a group's pixels as an image of its cache lines (store_group_lines), per extraction wave
+    __shared__ __attribute__((aligned(16))) uint32_t s_out[kFrameWaves - 1][Cfg::kOutDw + kStageCarryDw];  // a group's pixels as an image of its cache lines (store_group_lines), per extraction wave
     __shared__ uint32_t s_err;
-#ifdef TRPX_DEC_LDS_PAD
-    __shared__ uint32_t s_pad[TRPX_DEC_LDS_PAD / 4];   // diagnostic build: fewer workgroups per CU
-    if (terse_bytes == 1) s_pad[threadIdx.x] = 0;
-#endif
     __shared__ uint32_t s_role[kFrameWaves];
     // What only the epilogue needs (status / list pointers, the frame number) waits in LDS: as live scalar registers across the
     // super-step loop they were spilled to a VGPR's lanes (the kernel sits at the 80-SGPR limit of eight workgroups per CU).
@@ -183,27 +164,18 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
     // offset of the frame's first pixel inside its 128-byte line = that of every 64-block group (768 pixels: whole lines)
     const uint32_t out_c = LINES ? (uint32_t)((uintptr_t)fout & 127u) : 0u;
 
-#ifdef TRPX_DEC_NO_STORE
-    uint32_t diag_acc = 0;
-#endif
     // walker state (wave-uniform)
     int32_t c_lo = 0, c_hi = 0;                        // the window holds dwords [c_lo, c_hi) of the frame
     uint32_t b = 0, w_prev = pw0, pos = 0;             // next block, width of the block before it, bit position of its header (all relative to the unit)
-#ifndef TRPX_DEC_WALK_PRIO
-#define TRPX_DEC_WALK_PRIO 3
-#endif
-#ifndef TRPX_DEFER_NUM                               // hand-over line: more than NUM width changes in DEN blocks
-#define TRPX_DEFER_NUM 2
-#define TRPX_DEFER_DEN 9
-#endif
-    if (wave == 0) __builtin_amdgcn_s_setprio(TRPX_DEC_WALK_PRIO);      // the walk is the critical path
+    constexpr uint64_t kDeferNum = 2, kDeferDen = 9;   // hand-over line: more than kDeferNum width changes in kDeferDen blocks
+    if (wave == 0) __builtin_amdgcn_s_setprio(3);      // the walk is the critical path
     // MODE 1: the widths of the super-step after the one being filled wait in LDS (s_wnext[chunk * 64 + lane]); the filler
     // requests them before it computes and parks them behind -- in registers across the loop they would be live in the
     // extraction waves' code too (spills at 64 VGPRs)
     // (requested four widths per lane and load -- one unaligned dword: three registers in flight per 768 blocks, not twelve)
     constexpr int kIdxChunks = IDX ? kStepBlocks / kWave : 1;
     constexpr int kIdxQuads = IDX ? kStepBlocks / (4 * kWave) : 1;
-    static_assert(!IDX || kStepBlocks % (4 * kWave) == 0, "the width prefetch covers a super-step in whole quads of 64 lanes (TRPX_FRAME_GPW: a multiple of 4 per three extraction waves)");
+    static_assert(!IDX || kStepBlocks % (4 * kWave) == 0, "the width prefetch covers a super-step in whole quads of 64 lanes (kGpw: a multiple of 4 per three extraction waves)");
     __shared__ __attribute__((aligned(4))) uint8_t s_wnext[IDX ? kStepBlocks : 4];
     [[maybe_unused]] auto idx_load = [&](uint32_t ss, uint32_t (&dst)[kIdxQuads]) {
         const uint8_t* __restrict__ wfl = idx_widths + frame * g.n_blocks + pb0;
@@ -521,14 +493,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
                     }
                     // (3: listed WITHOUT a search for runs -- a frame past this line has runs of four or five blocks, nothing the run
                     // guess of decode_seg.hip could start in: the search cost every Poisson(3) frame 44 of 350 us)
-                    if (d_chg * (uint64_t)TRPX_DEFER_DEN > (uint64_t)TRPX_DEFER_NUM * d_blk && lane == 0) s_err = 3u;
-#ifdef TRPX_DEFER_STATS
-                    if (lane == 0) {       // diagnostic build: status[2..4] = frames handed over after super-step 0 / 3 / 11, [5] = decisions by the stack's count, [6] = sum of own densities (per mille) at step 0
-                        if (d_chg * (uint64_t)TRPX_DEFER_DEN > (uint64_t)TRPX_DEFER_NUM * d_blk) atomicAdd(status + (s == 0u ? 2 : s == 3u ? 3 : 4), 1u);
-                        if (d_blk != blk) atomicAdd(status + 5, 1u);
-                        if (s == 0u) atomicAdd(status + 6, chg * 1000u / blk);
-                    }
-#endif
+                    if (d_chg * kDeferDen > kDeferNum * d_blk && lane == 0) s_err = 3u;
                 }
             }
         } else if (s >= 1) {
@@ -538,9 +503,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
             // from super-step to super-step, in opposite phase for odd and even wave slots, gives every workgroup the same
             // share over time: all finish within 20 % of each other, the kernel 6 % sooner.  (Three levels, rotating the
             // walkers' priority as well, or a rotation every second super-step: no better.)
-#ifndef TRPX_DEC_PRIO_FLAT
             if (((hw_slot + s) & 1u) != 0u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
             // ---- extraction of super-step s-1: this wave's groups, one after the other ----------------------------------
             // One LDS read gives a lane the end of its block's payload and the block's width (H of the NEXT block).  Every
             // lane loads the stream dwords of its own block straight from L2 (the walker has just pulled them through):
@@ -557,11 +520,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
             const uint32_t step0 = step_begin(s - 1u);
             const uint32_t step1 = step_begin(s) < n_blocks ? step_begin(s) : n_blocks;
             const uint32_t* const ent = s_posx + pbuf * kPosEntries;
-#ifdef TRPX_DEC_WALK_ONLY
-            const uint32_t gpw = 0;                                                   // diagnostic build (tools): time the walker alone
-#else
             const uint32_t gpw = (step_begin(s) - step0) / (uint32_t)((kFrameWaves - 1) * kWave);   // groups per wave in this super-step: 1 or kGpw
-#endif
             // (blocks in front of n_whole are full blocks of this super-step: a group of 64 of them leaves as whole lines)
             [[maybe_unused]] const uint32_t n_whole = nb_last == (uint32_t)kBlock || step1 < n_blocks ? step1 : step1 - 1u;
             [[maybe_unused]] bool carry_live = false;                                 // the row's front holds the group's first out_c bytes
@@ -603,14 +562,10 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
                         raw[i] = d < n_dw ? s32[d] : 0u;
                     }
                 }
-#ifdef TRPX_DEC_NO_EXTRACT
-                if (q == 0xFFFFFFFFu) fout[0] = (T)(w + raw[0]);                      // (diagnostic build: loads only)
-                continue;
-#endif
                 const bool full = blk < step1 && (blk + 1 < n_blocks || nb_last == (uint32_t)kBlock);
                 T* __restrict__ dst = fout + (uint64_t)blk * kBlock;
                 uint64_t todo = __ballot(full);
-                if (Cfg::kOutStaged && todo == ~0ull) {
+                if (todo == ~0ull) {
                     // 64 full blocks of 32-bit pixels: every lane leaves its 12 pixels in the wave's LDS row, then the wave
                     // stores the group 16 bytes per lane -- whole lines per store instruction instead of 48-byte runs
                     uint32_t* const stage = s_out[wave - 1] + kStageCarryDw;            // (head room in front: store_group_lines)
@@ -668,11 +623,7 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
                         if (mine) UnpackRegsDispatch<T, 0, PixelTraits<T>::bits>::run(raw, ss, wd, o);
                         todo &= ~__ballot(mine);
                     }
-#ifdef TRPX_DEC_NO_STORE
-                    if (full) diag_acc ^= o[0];
-#else
                     if (full) store_packed<T>(dst, o);
-#endif
                 }
                 if (blk + 1 == n_blocks && blk < step1 && !full) {                    // the frame's last, partial block
                     const uint32_t mask = field_mask(w);
@@ -705,9 +656,6 @@ __device__ __forceinline__ void decode_frame_body(const uint8_t* __restrict__ te
         dbg[5] = xcc;
         dbg[6] = dbg[7] = 0;
     }
-#endif
-#ifdef TRPX_DEC_NO_STORE
-    if (diag_acc == 0x12345678u) fout[threadIdx.x] = (T)diag_acc;
 #endif
     if (threadIdx.x == 0 && s_err != 0u) {
         asm volatile("" ::: "memory");                                     // (the LDS copies, not the registers they came from)
@@ -754,11 +702,7 @@ __global__ __launch_bounds__(kFrameThreads, sizeof(T) == 4 ? 6 : 8) void k_decod
         if (blockIdx.x >= list[0] || status[0] != 0u) return;
         frame = list[1u + blockIdx.x] & 0x7FFFFFFFu;
     }
-#ifdef TRPX_IDX_LINES                                     // (experiment: line images in the indexed kernel, as k_decode_frames<T, true> writes them)
-    decode_frame_body<T, 1, false, true>(terse, terse_bytes, frame_offsets, g, pixels_out, nullptr, status, frame, widths, group_off);
-#else
     decode_frame_body<T, 1>(terse, terse_bytes, frame_offsets, g, pixels_out, nullptr, status, frame, widths, group_off);
-#endif
 }
 
 // Large frames whose index is known, in units of `unit_blocks` blocks (a multiple of 256 and of a super-step): the same body, one
@@ -838,9 +782,6 @@ hipError_t launch_index_frames(uint32_t max_w, const DecodeArgs& a, bool clear_s
 
 template <typename T>
 static hipError_t launch_decode_frames_indexed_t(const DecodeArgs& a, const uint32_t* list, hipStream_t st) {
-#ifdef TRPX_IDX_AS_UNITS                                  // (experiment: the units instantiation on whole small frames)
-    if (!list) return launch_decode_units_indexed_t<T>(a, st, nullptr);
-#endif
     if (!list && a.geom.n_blocks > 8u * FrameCfg<T>::kStepBlocks) {
         // A frame count a little over a multiple of what the GPU holds leaves the last round of whole frames nearly empty: units of
         // the frames -- the same body -- where their rounds come out at least a tenth cheaper.

@@ -40,7 +40,7 @@ struct PlanInput {
     bool     locate_fits = false;      // ... and its scratch fits behind tile_off
     // compile-time switches of api.hip (A/B and diagnostic builds)
     int      chain_extract = -1;       // TRPX_CHAIN_EXTRACT_TILES: 1 = tiles, 0 = units, -1 = by type and size
-    bool     indexed_large_tiles = false;   // TRPX_INDEXED_LARGE_TILES
+    bool     indexed_large_tiles = false;   // (no build sets it; tests/cpp/decode_plan_test.cpp pins what it would route)
     bool     no_defer = false;         // TRPX_DIAGNOSTICS, $TRPX_NO_DEFER: the per-frame decoder keeps every frame
     bool     lds_walk = false;         // TRPX_DIAGNOSTICS, $TRPX_WALK = lds: every index by the one-wavefront-per-frame walk
 };

@@ -42,23 +42,11 @@ namespace trpx {
 // round 3, eight 4096^2 int32 frames: 2 @ 6..8 / 3 @ 5 / 4 @ 4 / 5 @ 4 / 6 @ 3 -> 0.29 / 0.208 / 0.173 / 0.164 / 0.166 ms, 1000 noisy
 // 512^2 int32 frames 0.39-0.44 / 0.333 / 0.272 / 0.249 / 0.260 ms: a 32-bit tile's fixed costs (look-back, flush, two barriers) weigh
 // more than the workgroups its registers cost.
-#ifndef TRPX_FUSED_SUB32
-#define TRPX_FUSED_SUB32 5
-#endif
-#ifndef TRPX_FUSED_SUB16
-#define TRPX_FUSED_SUB16 4
-#endif
-template <typename T> constexpr int sub_tiles() { return sizeof(T) <= 2 ? TRPX_FUSED_SUB16 : TRPX_FUSED_SUB32; }
+template <typename T> constexpr int sub_tiles() { return sizeof(T) <= 2 ? 4 : 5; }
 // Workgroups per CU (what the VGPR budget and the half-size LDS image of fused_phase_rounds() allow).  8/16-bit pixels: eight
 // (13.4 KB image; 64 VGPRs once a round's block metadata share one register: 0.268 -> 0.258 ms per 2000-frame u16 stack against
 // seven).  32-bit pixels: four (five sub-tiles: 38.4 KB image, 117 VGPRs; with three sub-tiles: five workgroups, 83 VGPRs).
-#ifndef TRPX_FUSED_OCC16
-#define TRPX_FUSED_OCC16 8
-#endif
-#ifndef TRPX_FUSED_OCC32
-#define TRPX_FUSED_OCC32 4
-#endif
-template <typename T> constexpr int fused_occupancy() { return sizeof(T) == 1 ? 8 : (sizeof(T) == 2 ? TRPX_FUSED_OCC16 : TRPX_FUSED_OCC32); }   // workgroups per CU (LDS image + VGPR budget)
+template <typename T> constexpr int fused_occupancy() { return sizeof(T) <= 2 ? 8 : 4; }   // workgroups per CU (LDS image + VGPR budget)
 // Every wait on another tile is bounded in WALL time: a poll loop gives up kWaitTicks of the 100 MHz realtime counter
 // after it started (0.25 s; the whole 2000-frame launch takes 0.3 ms, so this only ever triggers when tiles do not
 // make progress at all), checked every 64 polls.  The caller then sees TRPX_ERR_TIMEOUT in status[0]
@@ -159,10 +147,7 @@ __device__ bool lookback(const uint64_t* __restrict__ desc, int64_t idx, int64_t
 // frames (six frames: ONE line) queued for 20 us, every frame's base waited for the last of them, and the encoder ran at 0.29 of
 // the HBM peak on such a stack against 0.60 on 512 x 512 frames (200 x (1030 x 1065): 0.187 -> 0.125 ms, 128 x 2048^2: 0.557 -> 0.343).
 constexpr int kAccShift = 40;                                            // bits < 2^40, tiles per frame < 2^24
-#ifndef TRPX_FUSED_ACC_LINES
-#define TRPX_FUSED_ACC_LINES 2
-#endif
-constexpr uint32_t kAccLines = TRPX_FUSED_ACC_LINES;
+constexpr uint32_t kAccLines = 2;
 __host__ __device__ inline uint32_t fused_acc_lines(uint32_t tiles_per_frame) {                    // ~32 tiles and more per line
     const uint32_t k = (tiles_per_frame + 31u) / 32u;
     return k < 1u ? 1u : (k > kAccLines ? kAccLines : k);
@@ -708,9 +693,6 @@ __device__ __forceinline__ void encode_fused_body(const T* __restrict__ pixels, 
     uint64_t img_p0 = 0;                                                 // absolute bit of image bit 0 in the current phase
     uint32_t bias = 0;                                                   // tile-relative bit of image bit 0
     bool writable = false;
-#ifndef TRPX_ABLATE
-#define TRPX_ABLATE 0
-#endif
 #define TRPX_WSTAMP(slot) do { if ((TRPX_DIAG(a) & 8u) && lane == 0 && tile < 4096) a.stamps[tile * 32 + wave * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
     // Full blocks: header + payload as ONE bit string, one pass per distinct width present in the wavefront (w = 0:
     // the header alone), each with static shifts.  The frame's partial last block goes the generic way.
@@ -722,13 +704,13 @@ __device__ __forceinline__ void encode_fused_body(const T* __restrict__ pixels, 
         const uint32_t wr = mr & 0xFFu;
         const uint32_t hv_top = wr == ((mr >> 8) & 0xFFu) ? 0x80000000u : s_hdr[wr];   // header code, top aligned (Terse.hpp:517-535)
         const bool full = (mr >> 24) & 1u;
-        if (((mr >> 25) & 1u) && !full && !(TRPX_ABLATE & 2)) {         // the frame's partial last block
+        if (((mr >> 25) & 1u) && !full) {                                   // the frame's partial last block
             const uint64_t hx = (uint64_t)(hv_top >> (32u - hl)) << (pos & 31u);
             atomicOr(&s_stage[pos >> 5], (uint32_t)hx);
             if ((uint32_t)(hx >> 32)) atomicOr(&s_stage[(pos >> 5) + 1], (uint32_t)(hx >> 32));
             if (wr) pack_payload_generic<T>(s_stage, pos + hl, wr, (int)nb_tail, pv);
         }
-        uint64_t todo = (TRPX_ABLATE & 1) ? 0ull : __ballot(full);
+        uint64_t todo = __ballot(full);
         while (todo) {
             const int l0 = __builtin_ctzll(todo);
             const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)wr, l0);
@@ -855,7 +837,7 @@ __device__ __forceinline__ void encode_fused_body(const T* __restrict__ pixels, 
         // 16-byte groups: one thread turns two aligned ds_read_b128 into one 16-byte aligned non-temporal store (the
         // image-side misalignment m is tile-uniform: four specialised bodies behind scalar branches).  The <= 7 dwords in
         // front of / behind the aligned groups go one per thread.
-        if (!(TRPX_ABLATE & 4) && writable) {
+        if (writable) {
             typedef uint32_t u4 __attribute__((ext_vector_type(4)));
             uint32_t al = (0u - ((uint32_t)((uintptr_t)out32 >> 2) + (uint32_t)d_first)) & 3u;
             if (head_pending && al == 0) al = 4;                              // dword 0 is k_stitch's: keep it out of the groups
@@ -872,11 +854,6 @@ __device__ __forceinline__ void encode_fused_body(const T* __restrict__ pixels, 
             const uint32_t m = kk0 & 3u;
             const u4* pad4 = reinterpret_cast<const u4*>(s_stage_pad) + (kk0 >> 2);
             u4* dst = reinterpret_cast<u4*>(out32 + d_first + al);
-#ifdef TRPX_ENC_PLAIN_STORES
-#define TRPX_STREAM_STORE(v, p) (*(p) = (v))
-#else
-#define TRPX_STREAM_STORE(v, p) __builtin_nontemporal_store(v, p)
-#endif
 #define TRPX_FLUSH_GROUPS(M)                                                                                   \
             for (uint32_t gq = tid; gq < n4; gq += kThreads) {                                                 \
                 const u4 A = pad4[gq], B = pad4[gq + 1];                                                       \
@@ -886,7 +863,7 @@ __device__ __forceinline__ void encode_fused_body(const T* __restrict__ pixels, 
                 x.y = __builtin_amdgcn_alignbit(e[M + 2], e[M + 1], sh);                                       \
                 x.z = __builtin_amdgcn_alignbit(e[M + 3], e[M + 2], sh);                                       \
                 x.w = __builtin_amdgcn_alignbit(e[M + 4], e[M + 3], sh);                                       \
-                TRPX_STREAM_STORE(x, dst + gq);                                                                \
+                __builtin_nontemporal_store(x, dst + gq);                                                      \
             }
             if (m == 0) { TRPX_FLUSH_GROUPS(0) } else if (m == 1) { TRPX_FLUSH_GROUPS(1) }
             else if (m == 2) { TRPX_FLUSH_GROUPS(2) } else { TRPX_FLUSH_GROUPS(3) }

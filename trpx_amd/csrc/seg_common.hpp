@@ -7,10 +7,7 @@
 
 namespace trpx {
 
-#ifndef TRPX_SEG_LOAD_DW
-#define TRPX_SEG_LOAD_DW 64
-#endif
-constexpr uint32_t kSegLoadDw = TRPX_SEG_LOAD_DW;    // dwords loaded per lane and window: 32 (128 bytes, eight lanes x 16 bytes) or 64
+constexpr uint32_t kSegLoadDw = 64;               // dwords loaded per lane and window: 32 (128 bytes, eight lanes x 16 bytes) or 64
 constexpr uint32_t kSegPieces = kSegLoadDw / 32;     // 16-byte loads per lane and row
 constexpr uint32_t kSegAdv = 32 * kSegLoadDw - 256;  // bits a window advances: 768 (1792)
 //                                                   (127 (alignment) + advance + 44 (peek) bits <= the bits loaded, and a multiple of 128)
@@ -206,7 +203,7 @@ __device__ __forceinline__ void seg_walk(const SegCtx& c, uint32_t* __restrict__
 #ifdef TRPX_SEG_STATS
             if (lane == 0u) atomicAdd(c.stat + 3, 1u);
 #endif
-#if !defined(TRPX_SEG_STATS) && !defined(TRPX_SEG_PLAIN_STEP)
+#ifndef TRPX_SEG_STATS
             if (!WRITE) {
                 // Counting steps, hand-scheduled.  A walking wavefront is bound by the LATENCY of its step -- every instruction
                 // hangs on the one before it, ~8 cycles each, plus the LDS read -- so the loop is software-pipelined around the
@@ -351,11 +348,7 @@ __device__ __forceinline__ void seg_walk(const SegCtx& c, uint32_t* __restrict__
                     "v_max_u32 %[wmax], %[wmax], %[t2]\n\t"                                                                     \
                     "v_cmp_eq_u32 vcc, 1, %[t]\n\t"                                                                             \
                     "s_branch 4" #K "b\n"
-#ifndef TRPX_SEG_NO_STORE
 #define TRPX_SEG_WIDTH_STORE "v_add_u32 %[t], -4, %[n]\n\t" "global_store_dword %[t], %[acc], %[wf]\n\t"   /* width[n - 4 .. n - 1] */
-#else
-#define TRPX_SEG_WIDTH_STORE ""                            /* (timing experiment: tools/r6_segvariant.sh nostore -DTRPX_SEG_NO_STORE) */
-#endif
                 asm volatile(
                     "s_mov_b64 %[ex], exec\n\t"
                     "v_cmpx_lt_u32 vcc, %[pw], %[stop]\n\t"
@@ -412,9 +405,7 @@ __device__ __forceinline__ void seg_walk(const SegCtx& c, uint32_t* __restrict__
                     bad = bad || wide;
                     if (n + rep > c.n_blocks) { bad = true; done = true; }
                     else {
-#ifndef TRPX_SEG_NO_STORE
                         if (wn) wf[n] = (uint8_t)wn;
-#endif
                         const uint32_t m = (n + (uint32_t)kTileBlocks - 1u) & ~((uint32_t)kTileBlocks - 1u);
                         if (m < n + rep) tf[m / kTileBlocks] = pos + (m - n);               // rep > 1 only for 1-bit blocks
                     }

@@ -11,16 +11,11 @@ template <typename T> constexpr int unpack_sub_tiles() { return sizeof(T) <= 2 ?
 // Pixels leave through a per-wavefront LDS row as whole 128-byte lines (store_group) for every pixel type: lane-owned 8..24-byte
 // runs leave each line to be merged from several store instructions in L2, and under load the lines are written back half
 // merged (decode_frame.hip).  2000 x 512 x 512 u16 with the decode index: 0.327 ms direct, 0.291 ms staged (five instead of six
-// workgroups per CU for the rows); eight 4096 x 4096 int32 frames: 0.29 -> 0.12 ms.  TRPX_UNPACK_DIRECT: A/B build.
-#ifdef TRPX_UNPACK_DIRECT
-template <typename T> constexpr bool unpack_staged() { return sizeof(T) == 4; }
-#else
-template <typename T> constexpr bool unpack_staged() { return true; }
-#endif
+// workgroups per CU for the rows); eight 4096 x 4096 int32 frames: 0.29 -> 0.12 ms.
 // (rows at a stride of one group behind one head room: store_group_lines reads up to 127 bytes in front of a row and uses only
 // what lies inside the row when no group continues another, as here -- the bytes in front may be the neighbour's)
 template <typename T> constexpr int unpack_stage_row_dwords() { return kWave * kBlock * (int)sizeof(T) / 4; }
-template <typename T> constexpr int unpack_stage_dwords() { return unpack_staged<T>() ? 4 * unpack_stage_row_dwords<T>() + kStageCarryDw : 4; }
+template <typename T> constexpr int unpack_stage_dwords() { return 4 * unpack_stage_row_dwords<T>() + kStageCarryDw; }
 template <typename T>
 constexpr int unpack_image_dwords() { return unpack_sub_tiles<T>() * ((kThreads * max_block_bits<T>() + 31) / 32) + 12; }
 
@@ -186,7 +181,7 @@ __device__ __forceinline__ bool unpack_tile(const uint8_t* __restrict__ terse, u
         if (nb[r] && ((s_image[(q - hl[r]) >> 5] >> ((q - hl[r]) & 31u)) & 1u) != (hl[r] == 1u ? 1u : 0u)) atomicMax(&status[0], kStatusCorrupt);
         uint32_t u[kBlock];
         tile_extract_full<T>(u, s_image, q, w[r], nb[r]);
-        if (unpack_staged<T>() && __ballot(nb[r] == kBlock) == ~0ull) {   // the wavefront's 64 blocks are all full: staged, coalesced stores
+        if (__ballot(nb[r] == kBlock) == ~0ull) {   // the wavefront's 64 blocks are all full: staged, coalesced stores
             if (tile_too_wide<T>(w[r])) atomicMax(&status[0], kStatusCorrupt);
             uint32_t* const st = s_stage + kStageCarryDw + wave * unpack_stage_row_dwords<T>();
             T* const gdst = fout + (uint64_t)(b - (uint32_t)lane) * kBlock;
