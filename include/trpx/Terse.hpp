@@ -24,6 +24,7 @@
 #include <iterator>
 #include <limits>
 #include <numeric>
+#include <span>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -298,6 +299,36 @@ public:
         std::vector<std::int64_t> out(d_frame_sizes.size() * n_maps);
         prolix_dot(weights.data(), n_maps, out.data());
         return out;
+    }
+
+    /// A new object holding the frames `frames` of this one -- any order, repeats allowed, possibly more than the stack has --
+    /// in one device call, without decoding them (trpx_select_frames_host): the frames' bytes are copied, so the result is
+    /// what push_back of those frames' pixels makes.  dim(), signedness and block are copied; bits_per_val() is kept from the
+    /// source and is therefore an upper bound for the selected frames.  An entry that is no frame: std::invalid_argument.
+    Terse select(std::span<const std::uint32_t> frames) const {
+        Terse t;
+        t.d_signed = d_signed; t.d_block = d_block; t.d_size = d_size; t.d_prolix_bits = d_prolix_bits; t.d_dim = d_dim;
+        std::size_t bytes = 0;
+        for (std::uint32_t f : frames) {
+            if (f >= d_frame_sizes.size()) throw std::invalid_argument("select: frame index out of range");
+            bytes += d_frame_sizes[f];
+        }
+        if (frames.empty()) return t;
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0), out_offs(frames.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        t.d_terse_data.resize(bytes);
+        std::size_t total = 0;
+        detail::check(trpx_select_frames_host(TRPX_U8 + (d_signed ? 1 : 0), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                              d_frame_sizes.size(), d_block, frames.data(), frames.size(), t.d_terse_data.data(), bytes,
+                                              out_offs.data(), &total, -1), "Terse::select");
+        t.d_terse_data.resize(total);
+        for (std::size_t i = 0; i < frames.size(); ++i) t.d_frame_sizes.push_back(std::size_t(out_offs[i + 1] - out_offs[i]));
+        if (const std::uint64_t* gs = f_states()) {                                // the group states travel with their frames
+            const std::size_t groups = d_group_states.size() / d_frame_sizes.size();
+            for (std::uint32_t f : frames) t.d_group_states.insert(t.d_group_states.end(), gs + f * groups, gs + (f + 1) * groups);
+        }
+        return t;
     }
 
     /// Appends row_offsets.size() - 1 frames given as their events in CSR form -- what prolix_sparse returns -- in one device

@@ -482,6 +482,61 @@ int trpx_encode_sparse_host(int dtype, const uint64_t* row_offsets, const uint32
                             uint32_t* prolix_bits, int device);
 
 /*
+ * Select frames of a stack into a new stack without decoding them: keep the hits, drop the blanks, reorder or repeat frames -- the
+ * stack -> stack step behind trpx_decode_dot / trpx_decode_sparse and in front of everything that takes a stack.  Every frame
+ * starts byte aligned and its stream does not depend on its neighbours (Terse.hpp:502-505, :359), so the stack of any list of
+ * frames is the concatenation of those frames' bytes: out, out_offsets and the zeroed bytes [total, align4(total)) are byte for
+ * byte what trpx_encode leaves for pixels[frames].  Only bytes move -- no pixel is decoded --, so the call takes every block in
+ * 1..4096 and every integer dtype, 64-bit containers included; dtype, n_values and block matter only for the index.
+ *   terse          DEVICE const uint8_t[terse_bytes], 4-byte aligned
+ *   frame_offsets  DEVICE const uint64_t[n_frames + 1], 8-byte aligned, MANDATORY as for trpx_decode_indexed (an index-free stack:
+ *                  trpx_locate_frames first)
+ *   frames         DEVICE const uint32_t[n_select], 4-byte aligned: the list, in any order, repeats allowed, n_select may exceed
+ *                  n_frames (a repeated frame makes the result larger than the source).  A device array on purpose: a picker on
+ *                  the GPU feeds it, and a captured graph is replayed with a new list in the same buffer
+ *   index, out_index
+ *                  both or neither (one without the other: TRPX_ERR_INVALID_ARG); both need block 12 and a dtype of up to 32 bits
+ *                  (TRPX_ERR_UNSUPPORTED otherwise).  index: the source's decode index; out_index: DEVICE, 16-byte aligned,
+ *                  trpx_index_bytes(dtype, n_values, n_select, block): receives the widths row and the group-offset row of each
+ *                  selected frame, and is accepted by trpx_decode_indexed and by every consumer of an index
+ *   out_offsets    DEVICE uint64_t[n_select + 1], 8-byte aligned: [i] = first byte of the i-th selected frame, [n_select] = total
+ *   out, out_capacity
+ *                  as for trpx_encode (out 16-byte aligned).  A stack that does not fit: status word 0 = TRPX_ERR_CAPACITY,
+ *                  out_offsets is still complete and valid, nothing at or behind out_capacity is touched; out_capacity ==
+ *                  align4(total) is success.  A sizes-only query passes out = NULL with out_capacity 0 (status word 0 is then
+ *                  TRPX_ERR_CAPACITY, as trpx_encode's).  out MUST NOT OVERLAP terse: in-place compaction is not supported
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  THE LIST AND THE OFFSETS ARE CHECKED ON THE DEVICE, ALWAYS: word 0 =
+ *                  TRPX_ERR_INVALID_ARG for a list entry >= n_frames, TRPX_ERR_CORRUPT for a selected frame whose offsets
+ *                  decrease or end beyond terse_bytes (CORRUPT where both occur).  Such a frame counts as empty in out_offsets,
+ *                  and `out` (and out_index) are then not written.  Both win over TRPX_ERR_CAPACITY.  Word 1 is 0: the call
+ *                  does not know prolix_bits
+ *   workspace      DEVICE, 8-byte aligned, trpx_select_frames_workspace_bytes(): the selected sizes and the scan's scratch, 8
+ *                  bytes per list entry + 4 per 256 of them -- arithmetic on n_frames and n_select, never proportional to the
+ *                  bytes moved (0 for sizes the call refuses)
+ * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)), frame_offsets[0 .. n_frames], frames
+ * and the index is read, nothing outside out[0, out_capacity), out_offsets[0 .. n_select], out_index, status and the workspace is
+ * written, whatever the lists hold.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block outside 1..4096 and the index rule above;
+ * TRPX_ERR_INVALID_ARG for an unknown or float dtype, zero sizes, n_select 0 or above 2^31 - 1, n_frames > terse_bytes, null or
+ * misaligned pointers, out NULL with a capacity; TRPX_ERR_CAPACITY for a workspace that is too small.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the host
+ * from n_select, n_frames, terse_bytes and out_capacity alone, never from the list or the offsets.  No atomics touch the output:
+ * bit-identical from run to run.
+ * trpx_select_frames_host: host terse / frame_offsets / frames / out / out_offsets (or NULL); checks its arguments AND the list on
+ * the host, before a device is looked for (TRPX_ERR_INVALID_ARG for an entry out of range, TRPX_ERR_CORRUPT for offsets that decrease
+ * or leave the stream, TRPX_ERR_CAPACITY for out_capacity < total), stages, calls trpx_select_frames, synchronises; sets
+ * *total_bytes.
+ */
+size_t trpx_select_frames_workspace_bytes(size_t n_frames, size_t n_select);
+int trpx_select_frames(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                       size_t n_values, size_t n_frames, unsigned block, const uint32_t* frames, size_t n_select,
+                       uint8_t* out, size_t out_capacity, uint64_t* out_offsets, void* out_index,
+                       uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_select_frames_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                            size_t n_values, size_t n_frames, unsigned block, const uint32_t* frames, size_t n_select,
+                            uint8_t* out, size_t out_capacity, uint64_t* out_offsets, size_t* total_bytes, int device);
+
+/*
  * synth-v1 frame generator (SURVEY.md section 8 row d) -- bench/test utility so that the GPU
  * box regenerates exactly the pixels the oracle anchors were computed on.  dtype U16 or I32.
  */

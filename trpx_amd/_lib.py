@@ -71,6 +71,9 @@ SYMBOLS = {
     "trpx_encode_sparse_bound_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
     "trpx_encode_sparse": (_I, [_I, _P, _P, _P, _SZ, _SZ, _SZ, _U, _P, _SZ, _P, _P, _P, _SZ, _P]),
     "trpx_encode_sparse_host": (_I, [_I, _P, _P, _P, _SZ, _SZ, _SZ, _U, _P, _SZ, C.POINTER(_SZ), _P, C.POINTER(_U), _I]),
+    "trpx_select_frames_workspace_bytes": (_SZ, [_SZ, _SZ]),
+    "trpx_select_frames": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
+    "trpx_select_frames_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _P, _SZ, _P, _SZ, _P, C.POINTER(_SZ), _I]),
     "trpx_gather_workspace_bytes": (_SZ, [_SZ, _I]),
     "trpx_gather_frame_offsets": (_I, [_P, _P, _SZ, _SZ, _P, _P, _P, _P, _P, _SZ, _P]),
     "trpx_encode_sharded_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _I]),

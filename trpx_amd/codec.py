@@ -442,3 +442,59 @@ def decode_dot(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
         check(lib().trpx_decode_dot(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
                                     n_values, n_frames, block, weights.data_ptr(), n_maps, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
     return out, status
+
+
+def select_frames_workspace_bytes(n_frames: int, n_select: int) -> int:
+    return lib().trpx_select_frames_workspace_bytes(n_frames, n_select)
+
+
+def select_frames(terse: torch.Tensor, frame_offsets: torch.Tensor, frames: torch.Tensor, n_values: int, n_frames: int, dtype,
+                  index: torch.Tensor | None = None, out: torch.Tensor | None = None, workspace: Workspace | None = None,
+                  status: torch.Tensor | None = None, out_offsets: torch.Tensor | None = None, block: int = BLOCK) -> Encoded:
+    """The frames ``frames`` of a stack resident on the GPU as a new stack (trpx_select_frames), without decoding them: the
+    result is byte for byte what ``encode`` writes for ``pixels[frames]``.  Only bytes move, so every block size and every
+    integer dtype is taken; ``dtype``, ``n_values`` and ``block`` matter only for the index.
+
+    ``frames``: a contiguous uint32 / int32 device tensor, any order, repeats allowed, possibly longer than the stack;
+    ``frame_offsets`` is mandatory (``locate_frames`` for an index-free stack).  With ``index`` (the source's decode index; block
+    12, pixels of up to 32 bits) the result carries ``.index``, its own decode index.  Returns an ``Encoded`` of ``len(frames)``
+    frames; ``Encoded.check()`` (synchronises) raises on status[0]: 1 for an entry that is no frame of the stack, 5 for a selected
+    frame whose offsets decrease or leave the stream, 3 when ``out`` is too small (the offsets are still complete).  status[1]
+    is 0: the call does not know prolix_bits.
+
+    With ``out`` given: ONE call, asynchronous on the current stream (capturable into a graph; a replay takes a new list from
+    the same ``frames`` buffer).  With ``out=None`` the call SYNCHRONISES: a sizes-only call, one read of the total, a tensor of
+    its own, a second call.  ``out`` must not overlap ``terse``."""
+    tdt = torch_dtype(dtype)
+    code = dtype_code(tdt)
+    dev = terse.device
+    if not terse.is_cuda:
+        raise ValueError("select_frames: the stack must live on the GPU (use trpx_amd.Terse.select for host data)")
+    if frames.dtype not in (torch.uint32, torch.int32) or frames.dim() != 1 or not frames.is_contiguous() or frames.device != dev:
+        raise TypeError(f"select_frames: frames must be a contiguous 1-d uint32 / int32 tensor on {dev}")
+    n_select = frames.numel()
+    if out_offsets is None:
+        out_offsets = torch.empty(n_select + 1, dtype=torch.int64, device=dev)
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, select_frames_workspace_bytes(n_frames, n_select))
+    out_index = None
+    if index is not None:
+        out_index = torch.empty(index_bytes(tdt, n_values, n_select, block), dtype=torch.uint8, device=dev)
+
+    def call(o):
+        with torch.cuda.device(dev):
+            check(lib().trpx_select_frames(code, terse.data_ptr(), terse.numel(), frame_offsets.data_ptr(), _ptr(index), n_values,
+                                           n_frames, block, frames.data_ptr(), n_select, _ptr(o), o.numel() if o is not None else 0,
+                                           out_offsets.data_ptr(), _ptr(out_index), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _stream_ptr(terse)))
+
+    if out is None:
+        call(None)
+        total = int(out_offsets[-1].item())                  # (synchronises)
+        if int(status[0].item()) in (_lib.OK, _lib.ERR_CAPACITY):
+            out = torch.empty(max((total + 15) // 16 * 16, 16), dtype=torch.uint8, device=dev)
+    if out is not None:
+        call(out)
+    else:
+        out = torch.empty(0, dtype=torch.uint8, device=dev)
+    return Encoded(out, out_offsets, status, n_values, n_select, tdt, out_index)

@@ -20,6 +20,7 @@
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
+#include "select_map.hpp"
 #include "sparse_events.hpp"
 
 namespace trpx {
@@ -1047,6 +1048,66 @@ int trpx_encode_sparse(int dtype, const uint64_t* row_offsets, const uint32_t* p
     return TRPX_OK;
 }
 
+// ---- frames of a stack into a new stack (select_frames.hip): bytes move, no pixel is touched -------------------------------------
+}  // extern "C"
+namespace {
+// what the device-pointer and the host-pointer entry point refuse alike, behind their dtype / block / geometry checks
+int select_sizes(const char* fn, size_t terse_bytes, size_t n_frames, size_t n_select) {
+    if (!terse_bytes || !n_select || n_select > 0x7FFFFFFFull || n_frames > terse_bytes)   // every frame is at least one byte (Terse.hpp:547)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes terse_bytes=%zu n_frames=%zu n_select=%zu", fn, terse_bytes, n_frames, n_select);
+    return TRPX_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t trpx_select_frames_workspace_bytes(size_t n_frames, size_t n_select) {
+    if (!n_frames || !n_select || n_select > 0x7FFFFFFFull) return 0;
+    return trpx::select_workspace_bytes(n_select);
+}
+
+int trpx_select_frames(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                       size_t n_values, size_t n_frames, unsigned block, const uint32_t* frames, size_t n_select, uint8_t* out,
+                       size_t out_capacity, uint64_t* out_offsets, void* out_index, uint32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    if (const int rc = check_args("trpx_select_frames", kDtypeFirst | kHasStream, dtype, trpx_dtype_size(dtype), 0, terse_bytes, n_values, n_frames,
+                                  block, {{terse, 4}, {frame_offsets, 8}, {frames, 4}, {out_offsets, 8}, {status, 8}, {workspace, 8},
+                                          {out, 16, out_capacity != 0}, {index, 16, false}, {out_index, 16, false}}, &g))
+        return rc;
+    if (const int rc = select_sizes("trpx_select_frames", terse_bytes, n_frames, n_select)) return rc;
+    if ((index == nullptr) != (out_index == nullptr)) return fail(TRPX_ERR_INVALID_ARG, "trpx_select_frames: index and out_index go together");
+    if (index && (block != kBlock || is64(dtype)))
+        return fail(TRPX_ERR_UNSUPPORTED, "trpx_select_frames: the decode index needs block=12 and pixels of <= 32 bits");
+    if (index && !sizes_ok(g, n_select)) return fail(TRPX_ERR_INVALID_ARG, "trpx_select_frames: no index for n_select=%zu frames", n_select);
+    const size_t need = trpx::select_workspace_bytes(n_select);
+    if (workspace_bytes < need) return fail(TRPX_ERR_CAPACITY, "trpx_select_frames: workspace %zu < %zu", workspace_bytes, need);
+
+    trpx::fused_ws_forget(workspace, workspace_bytes);
+    trpx::SelectArgs a{};
+    a.terse = terse;
+    a.terse_bytes = terse_bytes;
+    a.frame_offsets = frame_offsets;
+    a.n_frames = (uint32_t)n_frames;
+    a.frames = frames;
+    a.n_select = (uint32_t)n_select;
+    a.out = out;
+    a.out_capacity = out_capacity;
+    a.out_offsets = out_offsets;
+    a.status = status;
+    a.workspace = workspace;
+    if (index) {                                                                // rows of the source's index into the result's
+        const DecLayout in = idx_layout(g, n_frames, trpx_dtype_size(dtype)), ol = idx_layout(g, n_select, trpx_dtype_size(dtype));
+        a.n_blocks = g.n_blocks;
+        a.n_tiles = g.n_tiles;
+        a.widths = static_cast<const uint8_t*>(index) + in.widths;
+        a.tile_off = reinterpret_cast<const uint64_t*>(static_cast<const char*>(index) + in.tile_off);
+        a.out_widths = static_cast<uint8_t*>(out_index) + ol.widths;
+        a.out_tile_off = reinterpret_cast<uint64_t*>(static_cast<char*>(out_index) + ol.tile_off);
+    }
+    HIP_TRY(trpx::launch_select_frames(a, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
 // ---- host-pointer convenience wrappers ---------------------------------------------------
 // The callers of the reference's API work frame by frame from host memory (src/terse.cpp:63-69 pushes one image at a
 // time, src/prolix.cpp:69-92 expands one frame at a time): a device allocation per call would cost more than the
@@ -1450,6 +1511,42 @@ int trpx_encode_sparse_host(int dtype, const uint64_t* row_offsets, const uint32
                             d_st, d_ws, ws_bytes, hs);
     if (rc || (rc = finish("trpx_encode_sparse_host", hs, d_st, st))) return rc;
     return download_stream("trpx_encode_sparse_host", hs, d_off, d_out, n_frames, st, out, out_capacity, total_bytes, frame_offsets, prolix_bits);
+}
+
+int trpx_select_frames_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                            size_t n_frames, unsigned block, const uint32_t* frames, size_t n_select, uint8_t* out, size_t out_capacity,
+                            uint64_t* out_offsets, size_t* total_bytes, int device) {
+    // (the argument checks and the list's need no device: they come first)
+    trpx::FrameGeom g;
+    if (!trpx_dtype_size(dtype) || !terse || !frame_offsets || !frames || !out || !total_bytes)
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_select_frames_host: bad argument");
+    if (!geom_of(n_values, block, &g)) return fail(block == 0 || block > kMaxBlock ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "trpx_select_frames_host: unsupported sizes/block (block=%u)", block);
+    if (!sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "trpx_select_frames_host: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (const int rc = select_sizes("trpx_select_frames_host", terse_bytes, n_frames, n_select)) return rc;
+    uint64_t bad_slot = 0, total = 0;
+    if (const uint32_t code = trpx::select_check_list(frames, n_select, frame_offsets, n_frames, terse_bytes, &bad_slot, &total))
+        return fail((int)code, code == TRPX_ERR_INVALID_ARG ? "trpx_select_frames_host: entry %llu of the list is not a frame of the stack"
+                                                            : "trpx_select_frames_host: the frame of entry %llu has decreasing offsets or leaves the stream",
+                    (unsigned long long)bad_slot);
+    if (total > out_capacity) return fail(TRPX_ERR_CAPACITY, "trpx_select_frames_host: need %llu bytes, have %zu", (unsigned long long)total, out_capacity);
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_select_frames_host", device, &hs)) return rc;
+    // the result and the list in one device block: [out] [out_offsets] [frames]
+    const size_t cap = trpx::align_up(total, 16), off_at = cap, list_at = off_at + 8 * (n_select + 1);
+    const size_t ws_bytes = trpx::select_workspace_bytes(n_select);
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, true, 0, list_at + 4 * n_select, ws_bytes, &d);
+    if (rc) return rc;
+    char* o = static_cast<char*>(d.out);
+    HIP_TRY(copy_sync(hs, o + list_at, frames, 4 * n_select, hipMemcpyHostToDevice));
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_select_frames(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const uint32_t*>(o + list_at),
+                            n_select, reinterpret_cast<uint8_t*>(o), cap, reinterpret_cast<uint64_t*>(o + off_at), nullptr, d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_select_frames_host", hs, d.status, st))) return rc;
+    if (total) HIP_TRY(copy_sync(hs, out, o, total, hipMemcpyDeviceToHost));
+    if (out_offsets) HIP_TRY(copy_sync(hs, out_offsets, o + off_at, 8 * (n_select + 1), hipMemcpyDeviceToHost));
+    *total_bytes = total;
+    return TRPX_OK;
 }
 
 int trpx_group_states_host(const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,

@@ -101,6 +101,28 @@ struct SparseEncodeArgs {
     uint32_t*       tile_lo;       // n_frames * n_tiles: events of the frame in front of the tile
 };
 hipError_t launch_encode_sparse(int dtype, const SparseEncodeArgs& a, hipStream_t st);
+// select_frames.hip: the frames frames[0 .. n_select) of a stack into a new stack, bytes only (trpx_select_frames)
+struct SelectArgs {
+    const uint8_t*  terse;         // device, the source stack
+    size_t          terse_bytes;
+    const uint64_t* frame_offsets; // device, n_frames + 1
+    uint32_t        n_frames;
+    const uint32_t* frames;        // device, n_select list entries
+    uint32_t        n_select;
+    uint8_t*        out;           // device, compact stack (NULL: sizes only)
+    size_t          out_capacity;
+    uint64_t*       out_offsets;   // device, n_select + 1
+    uint32_t*       status;        // device, 8 words
+    void*           workspace;     // select_workspace_bytes(n_select)
+    // the decode index of the source and of the result (all four or none)
+    uint32_t        n_blocks, n_tiles;
+    const uint8_t*  widths;
+    const uint64_t* tile_off;
+    uint8_t*        out_widths;
+    uint64_t*       out_tile_off;
+};
+size_t select_workspace_bytes(size_t n_select);   // [size u64 x n_select] [verdict u32 x ceil(n_select / 256)]
+hipError_t launch_select_frames(const SelectArgs& a, hipStream_t st);
 // any block size (encode.hip, correct-first kernels): geom.block != 12
 hipError_t launch_encode_generic(int dtype, const EncodeArgs& a, hipStream_t st);
 // single-pass encoder (encode_fused.hip); `ws` = fused_workspace_bytes() of descriptor words

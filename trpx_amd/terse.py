@@ -342,6 +342,41 @@ class Terse:
                                              w.ctypes.data, w.shape[0], out.ctypes.data, self._device))
         return out
 
+    def select(self, frames) -> "Terse":
+        """A new object holding the frames ``frames`` of this one, in ONE GPU call (trpx_select_frames_host), without decoding
+        them: the frames' bytes are copied, so the result is what ``push_back_stack(pixels[frames])`` would make.  ``frames``: a
+        sequence of frame numbers -- any order, repeats allowed, possibly longer than the stack -- or a boolean mask of
+        ``number_of_frames()`` entries.  ``dim()``, signedness and block are copied; ``bits_per_val()`` is kept from the source and
+        is therefore an UPPER BOUND for the selected frames (the call never looks at a pixel)."""
+        f = self.number_of_frames()
+        idx = np.asarray(frames)
+        if idx.dtype == np.bool_:
+            if idx.shape != (f,):
+                raise ValueError("select: a mask needs one entry per frame")
+            idx = np.flatnonzero(idx)
+        idx = idx.reshape(-1)
+        if idx.size and (idx.dtype.kind not in "iu" or idx.min() < 0 or idx.max() >= f):
+            raise ValueError("select: frame index out of range")
+        t = Terse(block=self._block, device=self._device)
+        t._signed, t._size, t._prolix_bits, t._dim = self._signed, self._size, self._prolix_bits, list(self._dim)
+        if idx.size == 0:
+            return t
+        idx32 = np.ascontiguousarray(idx, dtype=np.uint32)
+        buf, offs = self._stream_and_offsets()
+        sizes = np.diff(offs)[idx32]
+        out = np.empty(int(sizes.sum()), np.uint8)
+        out_offs = np.empty(idx32.size + 1, np.uint64)
+        total = C.c_size_t(0)
+        check(lib().trpx_select_frames_host(_lib.U8 + int(self._signed), buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f,
+                                            self._block, idx32.ctypes.data, idx32.size, out.ctypes.data, out.size,
+                                            out_offs.ctypes.data, C.byref(total), self._device))
+        t._data = bytearray(out[: total.value].tobytes())
+        t._frame_sizes = [int(x) for x in np.diff(out_offs)]
+        gs = self._states()
+        if gs is not None:
+            t._group_states = np.ascontiguousarray(gs.reshape(f, -1)[idx32]).reshape(-1)
+        return t
+
     # ---- accessors (Terse.hpp:396-444) --------------------------------------------------------
     def size(self) -> int:
         return self._size
