@@ -53,6 +53,7 @@ import numpy as np
 import pytest
 
 from alignment import RESIDUES, STREAM_RESIDUES, align_up, carve, carve_copy, carve_stream, same_bytes, to_bytes
+from gpu_support import to_dev, torch_dt
 
 pytestmark = pytest.mark.gpu
 
@@ -108,28 +109,13 @@ def ladder(dtype, frames: int, n: int) -> np.ndarray:
     return px
 
 
-def _tdt(dt):
-    import torch
-    return {"uint8": torch.uint8, "int8": torch.int8, "uint16": torch.uint16, "int16": torch.int16, "uint32": torch.uint32,
-            "int32": torch.int32, "uint64": torch.uint64, "int64": torch.int64, "float32": torch.float32,
-            "float64": torch.float64}[np.dtype(dt).name]
-
-
-def to_dev(a: np.ndarray):
-    """A numpy array as an (aligned) device tensor of the same type."""
-    import torch
-    a = np.ascontiguousarray(a)
-    raw = torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
-    return raw.view(_tdt(a.dtype)).view(a.shape)
-
-
 class Stack:
     """One stack of the tests: its pixels, the oracle's stream of it, and both on the device.  Made once, never changed."""
 
     def __init__(self, dtype, frames, n):
         from oracle import oracle as O
         self.dtype, self.frames, self.n = np.dtype(dtype), frames, n
-        self.tdt = _tdt(dtype)
+        self.tdt = torch_dt(dtype)
         self.px = ladder(dtype, frames, n)
         self.O = O
         self._enc = {}
@@ -353,7 +339,7 @@ def convert_case(gpu, src, dst, off, stream_off=0, mark=None):
         else np.clip(st.px, np.iinfo(ddt).min, np.iinfo(ddt).max).astype(ddt)
     what = f"convert {src} -> {dst} out at {off}, stream at {stream_off} mod 128"
     terse, _, tcheck = carve_stream(d["stream"], stream_off)
-    out, room, check = carve(want.nbytes, _tdt(dst), off, gpu)
+    out, room, check = carve(want.nbytes, torch_dt(dst), off, gpu)
     status = torch.empty(_lib.STATUS_WORDS, dtype=torch.int32, device=gpu)
     ws_bytes = max(L.trpx_decode_workspace_bytes(c, S, 3, 12) for c in (_lib.U8, _lib.U32, _lib.U64))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=gpu)
@@ -435,7 +421,7 @@ def locate_cases(gpu, stacks=LOCATE_STACKS, residues=STREAM_RESIDUES, mark=None)
             terse, _, tcheck = carve_stream(d["stream"], off)
             for path in (0, 1):
                 what = f"locate_frames path {path} {_name(dtype)} ({frames}, {n}) stream at {off} mod 128"
-                out, room, check = carve(8 * (frames + 1), _tdt(np.int64), 8, gpu)
+                out, room, check = carve(8 * (frames + 1), torch_dt(np.int64), 8, gpu)
                 with selected("trpx_set_locate_path", path):
                     _mark(mark, what)
                     _, status = codec.locate_frames(terse, n, frames, st.tdt, out=out)
@@ -528,9 +514,9 @@ def consumer_cases(gpu, dtype, frames, n, stream_residues, out_residues, mark=No
             tag = f"{form} {_name(dtype)} ({frames}, {n}) stream at {s_off}, outputs at {out_residues} mod 128"
             for odt, o_off in ((np.int32, off4), (np.int64, off8)):
                 what = f"decode_sum into {_name(odt)} {tag}"
-                out, room, check = carve(sums[odt].nbytes, _tdt(odt), o_off, gpu)
+                out, room, check = carve(sums[odt].nbytes, torch_dt(odt), o_off, gpu)
                 _mark(mark, what)
-                _, status = codec.decode_sum(terse, offs, n, frames, st.tdt, 2, out_dtype=_tdt(odt), index=index, out=out, workspace=ws)
+                _, status = codec.decode_sum(terse, offs, n, frames, st.tdt, 2, out_dtype=torch_dt(odt), index=index, out=out, workspace=ws)
                 _ok(status, what)
                 same_bytes(out, sums[odt], what)
                 check(what)
@@ -543,8 +529,8 @@ def consumer_cases(gpu, dtype, frames, n, stream_residues, out_residues, mark=No
             same_bytes(out, roi, what)
             check(what)
             what = f"decode_sparse {tag}"
-            r_out, _, r_check = carve(s_rows.nbytes, _tdt(np.int64), off8, gpu)
-            p_out, _, p_check = carve(4 * n_ev, _tdt(np.uint32), off4, gpu)
+            r_out, _, r_check = carve(s_rows.nbytes, torch_dt(np.int64), off8, gpu)
+            p_out, _, p_check = carve(4 * n_ev, torch_dt(np.uint32), off4, gpu)
             v_out, _, v_check = carve(s_val.nbytes, st.tdt, t_off, gpu)
             _mark(mark, what)
             _, _, _, status = codec.decode_sparse(terse, offs, n, frames, st.tdt, thr, index=index, capacity=n_ev, row_offsets=r_out,
@@ -555,7 +541,7 @@ def consumer_cases(gpu, dtype, frames, n, stream_residues, out_residues, mark=No
                 same_bytes(got, want, f"{what}: {part}")
                 chk(f"{what}: {part}")
             what = f"decode_dot {tag}"
-            out, room, check = carve(dots.nbytes, _tdt(np.int64), off8, gpu)
+            out, room, check = carve(dots.nbytes, torch_dt(np.int64), off8, gpu)
             _mark(mark, what)
             _, status = codec.decode_dot(terse, offs, n, frames, st.tdt, d_maps, index=index, out=out.view(dots.shape), workspace=ws)
             _ok(status, what)

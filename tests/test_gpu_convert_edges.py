@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import convert_edges as ce
+from gpu_support import to_dev, torch_dt
 
 pytestmark = pytest.mark.gpu
 
@@ -21,27 +22,11 @@ _pair_id = lambda p: f"{_name(p[0])}-{_name(p[1])}"
 
 
 # ---- plumbing -----------------------------------------------------------------------------------------------------------
-def _torch_dt(dt):
-    import torch
-    return {"uint8": torch.uint8, "int8": torch.int8, "uint16": torch.uint16, "int16": torch.int16, "uint32": torch.uint32,
-            "int32": torch.int32, "uint64": torch.uint64, "int64": torch.int64, "float32": torch.float32,
-            "float64": torch.float64}[_name(dt)]
-
-
-def _to_dev(a: np.ndarray):
-    import torch
-    a = np.array(a, order="C")                              # (a writable copy: the shared cases are read-only)
-    if a.dtype.kind == "u" and a.itemsize > 1:              # (torch takes the unsigned wide types through a view)
-        return torch.from_numpy(a.view(np.dtype(f"i{a.itemsize}"))).cuda().view(_torch_dt(a.dtype))
-    return torch.from_numpy(a).cuda()
-
-
 def _stream_dev(stream: np.ndarray):
     """The stack in device memory, padded to whole dwords (the decoders read aligned 32-bit words)."""
-    import torch
     buf = np.zeros((stream.size + 3) // 4 * 4 + 16, np.uint8)
     buf[: stream.size] = stream
-    return torch.from_numpy(buf).cuda()
+    return to_dev(buf)
 
 
 class _Guarded:
@@ -55,7 +40,7 @@ class _Guarded:
 
     def tensor(self, shape):
         a, b = GUARD * self.dt.itemsize, (GUARD + self.n) * self.dt.itemsize
-        return self.raw[a:b].view(_torch_dt(self.dt)).view(*shape)
+        return self.raw[a:b].view(torch_dt(self.dt)).view(*shape)
 
     def check(self):
         a, b = GUARD * self.dt.itemsize, (GUARD + self.n) * self.dt.itemsize
@@ -79,7 +64,7 @@ def _device_decode(entry: str, stream_signed: bool, dst, d_stream, terse_bytes: 
     st = torch.full((_lib.STATUS_WORDS,), 0x7F7F7F7F, dtype=torch.int32, device="cuda")
     ws_bytes = max(L.trpx_decode_workspace_bytes(c, n, frames, block) for c in (_lib.U8, _lib.U32, _lib.U64))
     ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device="cuda")
-    d_offs = _to_dev(np.asarray(offs, np.uint64)) if offs is not None else None
+    d_offs = to_dev(np.asarray(offs, np.uint64)) if offs is not None else None
     rc = getattr(L, entry)(int(stream_signed), _code(dst, True), d_stream.data_ptr(), terse_bytes,
                            d_offs.data_ptr() if d_offs is not None else None, n, frames, block, out.ptr, st.data_ptr(),
                            ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
@@ -130,7 +115,7 @@ def test_decode_convert_on_device_memory(gpu, oracle, pair):
     for block in (12, 7):
         px, stream, offs, want = _edge_case(src, dst, block)
         frames, n = px.shape
-        enc = codec.encode(_to_dev(px), block=block)
+        enc = codec.encode(to_dev(px), block=block)
         torch.cuda.synchronize()
         enc.check()
         assert enc.stack().cpu().numpy().tobytes() == stream.tobytes(), ("encode", _pair_id(pair), block)
@@ -331,7 +316,7 @@ def test_decode_sum_on_designed_sums(gpu, oracle, src):
         for group in groups:
             px = ce.sum_stack(src, frames, n, group, seed=group)
             want_stream, sizes, _ = oracle.encode_stack(px)
-            enc = codec.encode(_to_dev(px), index=True)
+            enc = codec.encode(to_dev(px), index=True)
             torch.cuda.synchronize()
             enc.check()
             assert enc.stack().cpu().numpy().tobytes() == want_stream.tobytes()
@@ -343,7 +328,7 @@ def test_decode_sum_on_designed_sums(gpu, oracle, src):
                 for mode in ("index", "offsets", "none"):
                     out = _Guarded(n_out * n, dst)
                     _, st = codec.decode_sum(enc.stack(), None if mode == "none" else enc.frame_offsets, n, frames, src, group,
-                                             out_dtype=_torch_dt(dst), index=enc.index if mode == "index" else None,
+                                             out_dtype=torch_dt(dst), index=enc.index if mode == "index" else None,
                                              out=out.tensor((n_out, n)))
                     torch.cuda.synchronize()
                     out.check()
@@ -377,7 +362,7 @@ def test_decode_sum_ties_beyond_2_53(gpu, src):
         assert base + 1 <= hi and int(px[:, c].sum()) == t
     px = px.astype(src)
     n = px.shape[1]
-    enc = codec.encode(_to_dev(px), index=True)
+    enc = codec.encode(to_dev(px), index=True)
     torch.cuda.synchronize()
     enc.check()
     for dst in (np.float32, np.float64, np.int64, np.int32):
@@ -385,7 +370,7 @@ def test_decode_sum_ties_beyond_2_53(gpu, src):
         for mode in ("index", "offsets", "none"):
             out = _Guarded(n, dst)
             _, st = codec.decode_sum(enc.stack(), None if mode == "none" else enc.frame_offsets, n, BIG_FRAMES, src, BIG_FRAMES,
-                                     out_dtype=_torch_dt(dst), index=enc.index if mode == "index" else None, out=out.tensor((1, n)))
+                                     out_dtype=torch_dt(dst), index=enc.index if mode == "index" else None, out=out.tensor((1, n)))
             torch.cuda.synchronize()
             out.check()
             assert int(st[0].item()) == 0, (_name(src), _name(dst), mode)

@@ -10,94 +10,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import CORRUPT, OK, Guarded, encode, input_forms, ladder, ladder_holds_every_width, mixed, status_block, torch_dt
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
-GUARD = 64
 SENTINEL = 0x5A5A5A5A5A5A5A5A
-OK, CORRUPT = 0, 5
 I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 WIDTH = 37                                                  # the row length the 2-D maps use: no multiple or divisor of 12
-
-
-def _torch_dt(dt):
-    import torch
-    return {np.dtype(np.uint8): torch.uint8, np.dtype(np.int8): torch.int8, np.dtype(np.uint16): torch.uint16,
-            np.dtype(np.int16): torch.int16, np.dtype(np.uint32): torch.uint32, np.dtype(np.int32): torch.int32}[np.dtype(dt)]
-
-
-def _to_np(t):
-    import torch
-    if t.dtype in (torch.uint16, torch.uint32):             # (numpy() of the unsigned wide types: through a view)
-        sv = {torch.uint16: torch.int16, torch.uint32: torch.int32}[t.dtype]
-        un = {torch.uint16: np.uint16, torch.uint32: np.uint32}[t.dtype]
-        return t.cpu().view(sv).numpy().view(un)
-    return t.cpu().numpy()
-
-
-def _to_dev(a: np.ndarray):
-    import torch
-    a = np.ascontiguousarray(a)
-    un = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}
-    if a.dtype in un:
-        return torch.from_numpy(a.view(un[a.dtype])).cuda().view(_torch_dt(a.dtype))
-    return torch.from_numpy(a).cuda()
-
-
-def _encode(px: np.ndarray):
-    """px: [frames, values]"""
-    from trpx_amd import codec
-    import torch
-    enc = codec.encode(_to_dev(px), index=True)
-    enc.check()
-    torch.cuda.synchronize()
-    return enc
-
-
-def _random(dt, shape, seed):
-    """Mixed magnitudes: small values (narrow blocks), full-range runs (wide blocks) and a stretch of zeros (width-0 blocks)."""
-    n, v = shape
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    big = rng.integers(info.min, int(info.max) + 1, size=(n, v), dtype=np.int64)
-    small = rng.integers(-3 if info.min < 0 else 0, 4, size=(n, v), dtype=np.int64)
-    sel = (np.arange(v) // 97) % 3 == 0
-    out = np.where(sel[None, :], big, small)
-    out[:, v // 2: v // 2 + v // 7] = 0
-    return out.astype(dt)
-
-
-def _ladder(dt, shape, seed):
-    """A width ladder: block b holds one value of exactly 2^w - 1 (signed: 2^(w - 1) - 1, and -2^(w - 1) + 1 as well) at
-    position b % 12 and nothing larger in magnitude, w cycling through 0 .. bits: every width occurs."""
-    n, v = shape
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    nblk = -(-v // 12)
-    b = np.arange(nblk)
-    out = np.empty((n, nblk, 12), np.int64)
-    for f in range(n):
-        w = (b + 5 * f) % (info.bits + 1)
-        hi = np.where(w == 0, 0, (1 << np.maximum(w - (1 if info.min < 0 else 0), 0).astype(np.int64)) - 1).astype(np.int64)
-        r = rng.random((nblk, 12))
-        if info.min < 0:
-            vals = np.floor((2 * r - 1) * hi[:, None]).astype(np.int64)
-            vals[b, (b + 5) % 12] = -hi
-        else:
-            vals = np.floor(r * hi[:, None]).astype(np.int64)
-        vals = np.clip(vals, -hi[:, None], hi[:, None])
-        vals[b, b % 12] = hi
-        out[f] = vals
-    return np.ascontiguousarray(out.reshape(n, nblk * 12)[:, :v]).astype(dt)
-
-
-def _assert_ladder_holds_every_width(px):
-    """A check of the fixture, not of the code: for every width w the largest value a w-bit block can hold is there."""
-    info = np.iinfo(px.dtype)
-    for w in range(1, info.bits + 1):
-        top = (1 << (w - 1 if info.min < 0 else w)) - 1
-        assert (px == top).any() and (info.min == 0 or (px == -top).any()), (px.dtype, w)
 
 
 def truth(px: np.ndarray, w: np.ndarray) -> np.ndarray:
@@ -162,21 +83,17 @@ def _dot(enc, dt, w, mode="index", first=0, n_frames=None, ws=None, w_dev=None):
     k = w.shape[0]
     if w_dev is None:
         w_dev = torch.from_numpy(np.ascontiguousarray(w, dtype=np.int32)).cuda()
-    out_all = torch.full((n_frames * k + 2 * GUARD,), SENTINEL, dtype=torch.int64, device="cuda")
-    out = out_all[GUARD:GUARD + n_frames * k]
-    status = torch.full((8,), 77, dtype=torch.int32, device="cuda")
+    out = Guarded(n_frames * k, np.int64, SENTINEL)
+    status = status_block()
     ws = _ws(enc, n_frames) if ws is None else ws
     stack = enc.stack()
-    offs = None if mode == "none" else enc.frame_offsets[first:]
-    index = enc.index if mode == "index" else None
+    offs, index = input_forms(enc, mode, first)
     rc = _lib.lib().trpx_decode_dot(dtype_code(dt), stack.data_ptr(), stack.numel(), offs.data_ptr() if offs is not None else None,
                                     index.data_ptr() if index is not None else None, enc.n_values, n_frames, 12, w_dev.data_ptr(), k,
-                                    out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+                                    out.view.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
     assert rc == 0, _lib.lib().trpx_last_error_string()
     torch.cuda.synchronize()
-    a = out_all.cpu().numpy()
-    assert (a[:GUARD] == SENTINEL).all() and (a[GUARD + n_frames * k:] == SENTINEL).all(), "written outside dots_out"
-    return a[GUARD:GUARD + n_frames * k].reshape(n_frames, k).copy(), int(status[0].item())
+    return out.check("dots_out").reshape(n_frames, k).copy(), int(status[0].item())
 
 
 def _check(enc, px, w, mode="index", what="", want=None, **kw):
@@ -200,10 +117,10 @@ def test_exactness_matrix(dt, v):
     n = FRAME_COUNTS[(N_VALUES.index(v) + DTYPES.index(dt)) % 3]           # (every size with every count over the six types)
     sets = map_sets(v, seed=v)
     assert sorted({w.shape[0] for _, w in sets}) == [1, 2, 3, 16]
-    for what, px in (("mixed", _random(dt, (n, v), seed=n * 1000 + v % 1000)), ("ladder", _ladder(dt, (n, v), seed=v))):
+    for what, px in (("mixed", mixed(dt, (n, v), seed=n * 1000 + v % 1000, zero_stretch=True)), ("ladder", ladder(dt, (n, v), seed=v))):
         if what == "ladder" and v >= 12 * 3 * 33:            # (three cycles of the widths 0 .. 32)
-            _assert_ladder_holds_every_width(px)
-        enc = _encode(px)
+            ladder_holds_every_width(px)
+        enc = encode(px)
         ws = _ws(enc, n)
         for name, w in sets:
             got = _check(enc, px, w, what=f"{what} / {name}", ws=ws)
@@ -214,8 +131,8 @@ def test_exactness_matrix(dt, v):
 @pytest.mark.parametrize("v", N_VALUES)
 def test_every_frame_count_on_every_size(v):
     for n in FRAME_COUNTS:
-        px = _random(np.int16 if v % 2 else np.uint32, (n, v), seed=n)
-        enc = _encode(px)
+        px = mixed(np.int16 if v % 2 else np.uint32, (n, v), seed=n, zero_stretch=True)
+        enc = encode(px)
         for name, w in map_sets(v, seed=n):
             _check(enc, px, w, what=name)
 
@@ -229,7 +146,7 @@ def test_wrap_is_modulo_two_to_the_64():
         assert v * abs(pv) * abs(wv) > (1 << 63)            # the sum leaves int64
         want = truth_mod64(px, w)
         assert np.array_equal(want, truth(px, w))           # numpy's int64 arithmetic wraps alike
-        enc = _encode(px)
+        enc = encode(px)
         for mode in ("index", "offsets", "none"):
             _check(enc, px, w, mode, what="wrap", want=want)
 
@@ -238,8 +155,8 @@ def test_maps_that_are_four_byte_aligned_only():
     """Maps at an address that is 4 but not 16 bytes aligned, with n_values % 4 == 0: the value-by-value path alone."""
     import torch
     v, n = 3072 * 2, 3
-    px = _random(np.uint16, (n, v), seed=5)
-    enc = _encode(px)
+    px = mixed(np.uint16, (n, v), seed=5, zero_stretch=True)
+    enc = encode(px)
     sets = map_sets(v, seed=5)
     for name, w in sets:
         buf = torch.zeros(w.size + 8, dtype=torch.int32, device="cuda")
@@ -252,8 +169,8 @@ def test_maps_that_are_four_byte_aligned_only():
 @pytest.mark.parametrize("dt", [np.uint16, np.int32], ids=lambda d: np.dtype(d).name)
 def test_input_forms_runs_and_sub_stacks_agree(dt):
     n, v = 5, 49157
-    px = _random(dt, (n, v), seed=17)
-    enc = _encode(px)
+    px = mixed(dt, (n, v), seed=17, zero_stretch=True)
+    enc = encode(px)
     for name, w in map_sets(v, seed=17)[3:]:
         outs = [_check(enc, px, w, mode, what=f"forms / {name}") for mode in ("index", "offsets", "none")]
         outs.append(_check(enc, px, w, "index", what="second run"))
@@ -279,9 +196,9 @@ def test_support_rule_does_not_skip_validation():
     is fetched from -- a width byte of the index, a frame-offset table whose end is short -- is still found."""
     import torch
     n, v = 3, 7000
-    px = _random(np.uint16, (n, v), seed=31)
+    px = mixed(np.uint16, (n, v), seed=31, zero_stretch=True)
     px[:, :12] = np.arange(1, 13)                           # (the one block the maps see holds something)
-    enc = _encode(px)
+    enc = encode(px)
     w = np.zeros((3, v), np.int32)
     w[0, 5], w[1, 0], w[2, 11] = 7, -3, I32_MIN
     for mode in ("index", "offsets", "none"):
@@ -334,7 +251,7 @@ def test_noncanonical_streams(dtname):
         offs = torch.from_numpy(S.offsets.astype(np.int64)).cuda()
         code = dtype_code(np.dtype(dtname))
         index = torch.zeros(codec.index_bytes(np.dtype(dtname), v, n), dtype=torch.uint8, device="cuda")
-        st = torch.full((8,), 77, dtype=torch.int32, device="cuda")
+        st = status_block()
         assert _lib.lib().trpx_build_index(code, terse.data_ptr(), nbytes, offs.data_ptr(), v, n, 12, index.data_ptr(), st.data_ptr(),
                                            torch.cuda.current_stream().cuda_stream) == 0
         torch.cuda.synchronize()
@@ -342,7 +259,7 @@ def test_noncanonical_streams(dtname):
         if e["kind"] in ("K0", "K2"):
             assert have_index
         enc = dataclasses.make_dataclass("Stack", ["data", "frame_offsets", "index", "n_values", "n_frames", "dtype", "stack"])(
-            terse, offs, index, v, n, _torch_dt(dtname), lambda: terse[:nbytes])
+            terse, offs, index, v, n, torch_dt(dtname), lambda: terse[:nbytes])
         for name, w in map_sets(v, seed=3)[3:]:
             want = truth(S.px, w)
             for mode in ("index", "offsets", "none"):
@@ -364,9 +281,9 @@ def test_weights_behind_the_maps_are_never_read(v):
     behind a map's n_values (the partial last block) would pick up the next map's head, or the guard's."""
     import torch
     n = 3
-    px = _random(np.uint16, (n, v), seed=v)
+    px = mixed(np.uint16, (n, v), seed=v, zero_stretch=True)
     px[:, -1] = 65535
-    enc = _encode(px)
+    enc = encode(px)
     rng = np.random.default_rng(v)
     for k in (1, 2, 16):
         w = rng.integers(I32_MIN, I32_MAX + 1, size=(k, v), dtype=np.int64).astype(np.int32)
@@ -379,8 +296,8 @@ def test_graph_capture_replays_with_new_maps():
     from trpx_amd import codec
     import torch
     n, v = 6, 511 * 513
-    px = _random(np.uint16, (n, v), seed=9)
-    enc = _encode(px)
+    px = mixed(np.uint16, (n, v), seed=9, zero_stretch=True)
+    enc = encode(px)
     maps = [np.concatenate([disc_map(v, 513, 40), np.stack([np.arange(v) % 513, np.arange(v) // 513]).astype(np.int32)]),
             np.concatenate([disc_map(v, 513, 90) * -5, np.stack([np.arange(v) // 513, np.ones(v, np.int64)]).astype(np.int32)]),
             np.zeros((3, v), np.int32)]
@@ -421,7 +338,7 @@ def test_python_surfaces():
     px[:, 100:240] = rng.integers(0, 65536, size=(3, 140))
     w = np.concatenate([disc_map(h * wd, wd, 6), np.stack([np.arange(h * wd) % wd, np.arange(h * wd) // wd]).astype(np.int32)])
     want = truth(px, w)
-    enc = _encode(px)
+    enc = encode(px)
     abi, status = _dot(enc, px.dtype, w)
     assert status == OK and np.array_equal(abi, want)
     # the device-resident wrapper, [K, n_values] and [K, H, W]

@@ -2,63 +2,17 @@
 compared byte for byte: the codec is lossless, so no decoder is trusted."""
 import dataclasses
 import os
-import statistics
 import subprocess
 
 import numpy as np
 import pytest
 
+from gpu_support import Guarded, encode, events_median, input_forms, mixed, to_np, torch_dt
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
-GUARD = 64                                                  # guard elements on either side of pixels_out
-
-
-def _torch_dt(dt):
-    import torch
-    return {np.dtype(np.uint8): torch.uint8, np.dtype(np.int8): torch.int8, np.dtype(np.uint16): torch.uint16,
-            np.dtype(np.int16): torch.int16, np.dtype(np.uint32): torch.uint32, np.dtype(np.int32): torch.int32}[np.dtype(dt)]
-
-
-def _to_np(t):
-    import torch
-    if t.dtype in (torch.uint16, torch.uint32):             # (numpy() of the unsigned wide types: through a view)
-        sv = {torch.uint16: torch.int16, torch.uint32: torch.int32}[t.dtype]
-        un = {torch.uint16: np.uint16, torch.uint32: np.uint32}[t.dtype]
-        return t.cpu().view(sv).numpy().view(un)
-    return t.cpu().numpy()
-
-
-def _to_dev(a: np.ndarray):
-    import torch
-    a = np.ascontiguousarray(a)
-    un = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}
-    if a.dtype in un:
-        return torch.from_numpy(a.view(un[a.dtype])).cuda().view(_torch_dt(a.dtype))
-    return torch.from_numpy(a).cuda()
-
-
-def _encode(px: np.ndarray):
-    """px: [frames, height, width]"""
-    from trpx_amd import codec
-    import torch
-    enc = codec.encode(_to_dev(px.reshape(px.shape[0], -1)), index=True)
-    enc.check()
-    torch.cuda.synchronize()
-    return enc
-
-
-def _random(dt, shape, seed):
-    n, h, w = shape
-    v = h * w
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    # mixed magnitudes: small values (narrow blocks) and full-range runs (wide blocks; 32-bit types: blocks of width 32)
-    big = rng.integers(info.min, int(info.max) + 1, size=(n, v), dtype=np.int64)
-    small = rng.integers(-3 if info.min < 0 else 0, 4, size=(n, v), dtype=np.int64)
-    sel = (np.arange(v) // 97) % 3 == 0
-    return np.where(sel[None, :], big, small).astype(dt).reshape(n, h, w)
 
 
 def truth(px, boxes, bh, bw):
@@ -74,20 +28,14 @@ def _roi(enc, px, boxes, bh, bw, mode="index", first=0, n_frames=None):
     """Decodes into the middle of a guarded allocation; returns (pixels, status word 0) after checking the guards."""
     from trpx_amd import codec
     import torch
-    tdt = _torch_dt(px.dtype)
-    n = len(boxes) * bh * bw
-    sentinel = 0x5A
-    whole = _to_dev(np.full(n + 2 * GUARD, sentinel, px.dtype))
-    out = whole[GUARD:GUARD + n].view(len(boxes), bh, bw)
-    offs = None if mode == "none" else enc.frame_offsets[first:]
-    index = enc.index if mode == "index" else None
+    guarded = Guarded(len(boxes) * bh * bw, px.dtype, 0x5A)
+    offs, index = input_forms(enc, mode, first)
     n_frames = enc.n_frames - first if n_frames is None else n_frames
-    got, st = codec.decode_roi(enc.stack(), offs, enc.n_values, n_frames, tdt, px.shape[2], _boxes_dev(boxes), (bh, bw),
-                               index=index, out=out)
+    got, st = codec.decode_roi(enc.stack(), offs, enc.n_values, n_frames, torch_dt(px.dtype), px.shape[2], _boxes_dev(boxes), (bh, bw),
+                               index=index, out=guarded.view.view(len(boxes), bh, bw))
     torch.cuda.synchronize()
-    edge = _to_np(whole)
-    assert (edge[:GUARD] == sentinel).all() and (edge[GUARD + n:] == sentinel).all(), "written outside pixels_out"
-    return _to_np(got), int(st[0].item())
+    guarded.check("pixels_out")
+    return to_np(got), int(st[0].item())
 
 
 def _check(enc, px, boxes, bh, bw, mode="index", what=""):
@@ -143,8 +91,8 @@ SHAPES = [(3, 70, 100),     # 7000 pixels: three groups, the last one short, blo
 @pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_exactness_matrix(dt, shape):
-    px = _random(dt, shape, seed=shape[0] * 1000 + shape[1])
-    enc = _encode(px)
+    px = mixed(dt, shape, seed=shape[0] * 1000 + shape[1])
+    enc = encode(px)
     for what, bh, bw, boxes in box_sets(shape):
         _check(enc, px, boxes, bh, bw, what=what)
 
@@ -152,8 +100,8 @@ def test_exactness_matrix(dt, shape):
 @pytest.mark.parametrize("dt", [np.uint16, np.int32], ids=lambda d: np.dtype(d).name)
 @pytest.mark.parametrize("shape", [(3, 70, 100), (5, 511, 513)], ids=lambda s: "x".join(map(str, s)))
 def test_input_forms_agree(dt, shape):
-    px = _random(dt, shape, seed=17)
-    enc = _encode(px)
+    px = mixed(dt, shape, seed=17)
+    enc = encode(px)
     for what, bh, bw, boxes in box_sets(shape, seed=2):
         outs = []
         for mode in ("index", "offsets", "none"):
@@ -167,8 +115,8 @@ def test_input_forms_agree(dt, shape):
 def test_sub_stack():
     """Frames [a, b) alone: frame_offsets + a, n_frames = b - a, no index; box frame numbers are relative to a."""
     shape = (9, 70, 100)
-    px = _random(np.int16, shape, seed=11)
-    enc = _encode(px)
+    px = mixed(np.int16, shape, seed=11)
+    enc = encode(px)
     rng = np.random.default_rng(5)
     for a, b in ((0, 9), (2, 7), (8, 9), (3, 4)):
         boxes = [(int(rng.integers(b - a)), int(rng.integers(70 - 20 + 1)), int(rng.integers(100 - 33 + 1))) for _ in range(40)]
@@ -184,7 +132,7 @@ def test_data_kinds(kind):
     v = h * w
     dt = np.uint16
     if kind == "synth":
-        px = _to_np(codec.synth(np.uint16, 0, n, v))
+        px = to_np(codec.synth(np.uint16, 0, n, v))
     elif kind == "poisson":
         px = workloads.poisson_u16_np(3.0, 0, n, v).astype(dt)
     elif kind == "blank":
@@ -193,7 +141,7 @@ def test_data_kinds(kind):
         info = np.iinfo(dt)
         px = np.where((np.arange(v) % 2 == 0)[None, :], info.max, info.min).astype(dt).repeat(n, axis=0).reshape(n, v)
     px = np.ascontiguousarray(px).reshape(n, h, w)
-    enc = _encode(px)
+    enc = encode(px)
     rng = np.random.default_rng(23)
     boxes = [(int(rng.integers(n)), int(rng.integers(h - 32 + 1)), int(rng.integers(w - 48 + 1))) for _ in range(50)]
     _check(enc, px, boxes, 32, 48, what=kind)
@@ -207,7 +155,7 @@ def test_large_int32_frames():
     h = w = 4096
     px = (rng.poisson(3.0, size=(2, h, w)) - 1).astype(np.int32)
     px[1, : h // 3] = rng.integers(-(1 << 31), (1 << 31) - 1, size=(h // 3, w), dtype=np.int64).astype(np.int32)
-    enc = _encode(px)
+    enc = encode(px)
     boxes = [(f, y, x) for f in (0, 1) for y in (0, 48 - 64 + 48, 48 * 20 - 64, 48 * 43 - 127, h - 128)
              for x in (0, 3072 - 64, w - 128)]
     boxes += [(int(rng.integers(2)), int(rng.integers(h - 127)), int(rng.integers(w - 127))) for _ in range(64 - len(boxes))]
@@ -218,8 +166,8 @@ def test_large_int32_frames():
 
 def test_bad_boxes_are_reported_and_the_others_are_exact():
     shape = (3, 70, 100)
-    px = _random(np.uint16, shape, seed=29)
-    enc = _encode(px)
+    px = mixed(np.uint16, shape, seed=29)
+    enc = encode(px)
     bh, bw = 9, 14
     rng = np.random.default_rng(3)
     good = [(int(rng.integers(3)), int(rng.integers(70 - bh + 1)), int(rng.integers(100 - bw + 1))) for _ in range(30)]
@@ -237,8 +185,8 @@ def test_corrupt_index_and_short_offsets_are_rejected():
     from trpx_amd import codec
     import torch
     shape = (3, 70, 100)
-    px = _random(np.uint16, shape, seed=31)
-    enc = _encode(px)
+    px = mixed(np.uint16, shape, seed=31)
+    enc = encode(px)
     groups = 3                                              # ceil(ceil(7000 / 12) / 256)
     boxes = [(f, 0, 0) for f in range(3)]                   # whole frames: every group is touched
     got, code = _roi(enc, px, boxes, 70, 100)
@@ -263,8 +211,8 @@ def test_graph_capture_replays_with_new_boxes():
     from trpx_amd import codec
     import torch
     shape = (6, 511, 513)
-    px = _random(np.uint16, shape, seed=9)
-    enc = _encode(px)
+    px = mixed(np.uint16, shape, seed=9)
+    enc = encode(px)
     stack = enc.stack()
     rng = np.random.default_rng(41)
     bh, bw, nb = 24, 40, 60
@@ -291,7 +239,7 @@ def test_graph_capture_replays_with_new_boxes():
         g.replay()
         torch.cuda.synchronize()
         assert int(status[0].item()) == 0
-        assert np.array_equal(_to_np(out), truth(px, lst, bh, bw))
+        assert np.array_equal(to_np(out), truth(px, lst, bh, bw))
 
 
 def test_python_host_surface():
@@ -328,21 +276,6 @@ def test_cpp_class_prolix_roi():
     assert r.returncode == 0 and "OK roi example" in r.stdout, r.stdout + r.stderr
 
 
-def _events_median(fn, reps=20, warm=3):
-    import torch
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
-
-
 def test_faster_than_decoding_everything():
     """2000 x 512^2 u16 synth-v1 with the encoder's index, resident; one 64 x 64 box per frame.  The baseline is what a caller
     has to run without this entry point, before any cropping: trpx_decode_indexed of the same stack, in the same process."""
@@ -361,10 +294,10 @@ def test_faster_than_decoding_everything():
     pix = torch.empty((n, v), dtype=torch.uint16, device="cuda")
     out = torch.empty((n, 64, 64), dtype=torch.uint16, device="cuda")
     st = torch.empty(8, dtype=torch.int32, device="cuda")
-    t_full = _events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, index=enc.index))
+    t_full = events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, index=enc.index), 20)
     assert int(st[0].item()) == 0
-    t_roi = _events_median(lambda: codec.decode_roi(stack, enc.frame_offsets, v, n, torch.uint16, w, boxes, (64, 64), index=enc.index,
-                                                    out=out, status=st))
+    t_roi = events_median(lambda: codec.decode_roi(stack, enc.frame_offsets, v, n, torch.uint16, w, boxes, (64, 64), index=enc.index,
+                                                   out=out, status=st), 20)
     assert int(st[0].item()) == 0
     b = boxes.cpu().numpy()
     rows = torch.from_numpy(b[:, 1].astype(np.int64)).cuda()[:, None] + torch.arange(64, device="cuda")[None, :]

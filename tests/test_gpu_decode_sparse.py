@@ -3,89 +3,20 @@ compared byte for byte: the codec is lossless, so no decoder is trusted.  Every 
 allocation, 64 sentinel elements on either side of row_offsets, positions and values."""
 import dataclasses
 import os
-import statistics
 import subprocess
 
 import numpy as np
 import pytest
 
+from gpu_support import CAPACITY, CORRUPT, OK, Guarded, encode, events_median, input_forms, ladder, ladder_holds_every_width, mixed
+from gpu_support import sparse_truth as truth
+from gpu_support import status_block, to_np
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
-GUARD = 64
 ROW_SENTINEL, POS_SENTINEL, VAL_SENTINEL = 0x5A5A5A5A5A5A5A5A, 0x5A5A5A5A, 0x5A
-OK, CAPACITY, CORRUPT = 0, 3, 5
-
-
-def _torch_dt(dt):
-    import torch
-    return {np.dtype(np.uint8): torch.uint8, np.dtype(np.int8): torch.int8, np.dtype(np.uint16): torch.uint16,
-            np.dtype(np.int16): torch.int16, np.dtype(np.uint32): torch.uint32, np.dtype(np.int32): torch.int32}[np.dtype(dt)]
-
-
-def _to_np(t):
-    import torch
-    if t.dtype in (torch.uint16, torch.uint32):             # (numpy() of the unsigned wide types: through a view)
-        sv = {torch.uint16: torch.int16, torch.uint32: torch.int32}[t.dtype]
-        un = {torch.uint16: np.uint16, torch.uint32: np.uint32}[t.dtype]
-        return t.cpu().view(sv).numpy().view(un)
-    return t.cpu().numpy()
-
-
-def _to_dev(a: np.ndarray):
-    import torch
-    a = np.ascontiguousarray(a)
-    un = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}
-    if a.dtype in un:
-        return torch.from_numpy(a.view(un[a.dtype])).cuda().view(_torch_dt(a.dtype))
-    return torch.from_numpy(a).cuda()
-
-
-def _encode(px: np.ndarray):
-    """px: [frames, values]"""
-    from trpx_amd import codec
-    import torch
-    enc = codec.encode(_to_dev(px), index=True)
-    enc.check()
-    torch.cuda.synchronize()
-    return enc
-
-
-def _random(dt, shape, seed):
-    """The mixed-magnitude generator of test_gpu_decode_roi: small values (narrow blocks) and full-range runs (wide blocks)."""
-    n, v = shape
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    big = rng.integers(info.min, int(info.max) + 1, size=(n, v), dtype=np.int64)
-    small = rng.integers(-3 if info.min < 0 else 0, 4, size=(n, v), dtype=np.int64)
-    sel = (np.arange(v) // 97) % 3 == 0
-    return np.where(sel[None, :], big, small).astype(dt)
-
-
-def _ladder(dt, shape, seed):
-    """A width ladder: block b holds one value of exactly 2^w - 1 (signed: 2^(w - 1) - 1, and -2^(w - 1) + 1 as well) at
-    position b % 12 and nothing larger in magnitude, w cycling through 0 .. bits: the largest value a block of every width can
-    hold is an event in some block, which is where the skip rule's boundary lies."""
-    n, v = shape
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    nblk = -(-v // 12)
-    b = np.arange(nblk)
-    out = np.empty((n, nblk, 12), np.int64)
-    for f in range(n):
-        w = (b + 5 * f) % (info.bits + 1)
-        hi = np.where(w == 0, 0, (1 << np.maximum(w - (1 if info.min < 0 else 0), 0).astype(np.int64)) - 1).astype(np.int64)
-        r = rng.random((nblk, 12))
-        if info.min < 0:
-            vals = np.floor((2 * r - 1) * hi[:, None]).astype(np.int64)
-            vals[b, (b + 5) % 12] = -hi
-        else:
-            vals = np.floor(r * hi[:, None]).astype(np.int64)
-        vals = np.clip(vals, -hi[:, None], hi[:, None])
-        vals[b, b % 12] = hi
-        out[f] = vals
-    return np.ascontiguousarray(out.reshape(n, nblk * 12)[:, :v]).astype(dt)
 
 
 def thresholds(dt):
@@ -99,19 +30,6 @@ def thresholds(dt):
     if lo < 0:
         ts.append(-1)
     return sorted({min(max(t, lo), hi + 1) for t in ts})
-
-
-def truth(px: np.ndarray, t: int):
-    """(row_offsets int64 [n + 1], positions uint32, values) of px [n, v] at threshold t: numpy on the original pixels"""
-    info = np.iinfo(px.dtype)
-    if t <= info.min:
-        m = np.ones(px.shape, bool)
-    elif t > info.max:
-        m = np.zeros(px.shape, bool)
-    else:
-        m = px >= px.dtype.type(t)
-    rows = np.concatenate([[0], np.cumsum(m.sum(axis=1))]).astype(np.int64)
-    return rows, np.nonzero(m)[1].astype(np.uint32), px[m]
 
 
 def _ws(enc, n_frames):
@@ -129,29 +47,21 @@ def _sparse(enc, dt, t, mode="index", capacity=0, null_outputs=False, first=0, n
     import torch
     dt = np.dtype(dt)
     n_frames = enc.n_frames - first if n_frames is None else n_frames
-    rows_all = torch.full((n_frames + 1 + 2 * GUARD,), ROW_SENTINEL, dtype=torch.int64, device="cuda")
-    pos_all = _to_dev(np.full(capacity + 2 * GUARD, POS_SENTINEL, np.uint32))
-    val_all = _to_dev(np.full(capacity + 2 * GUARD, VAL_SENTINEL, dt))
-    rows, pos, val = rows_all[GUARD:GUARD + n_frames + 1], pos_all[GUARD:GUARD + capacity], val_all[GUARD:GUARD + capacity]
-    status = torch.full((8,), 77, dtype=torch.int32, device="cuda")
+    rows = Guarded(n_frames + 1, np.int64, ROW_SENTINEL)
+    pos, val = Guarded(capacity, np.uint32, POS_SENTINEL), Guarded(capacity, dt, VAL_SENTINEL)
+    status = status_block()
     ws = _ws(enc, n_frames) if ws is None else ws
     stack = enc.stack()
-    offs = None if mode == "none" else enc.frame_offsets[first:]
-    index = enc.index if mode == "index" else None
+    offs, index = input_forms(enc, mode, first)
     rc = _lib.lib().trpx_decode_sparse(dtype_code(dt), stack.data_ptr(), stack.numel(), offs.data_ptr() if offs is not None else None,
                                        index.data_ptr() if index is not None else None, enc.n_values, n_frames, 12, int(t),
-                                       rows.data_ptr(), None if null_outputs else pos.data_ptr(), None if null_outputs else val.data_ptr(),
-                                       capacity, status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+                                       rows.view.data_ptr(), None if null_outputs else pos.view.data_ptr(),
+                                       None if null_outputs else val.view.data_ptr(), capacity, status.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), torch.cuda.current_stream().cuda_stream)
     assert rc == 0, _lib.lib().trpx_last_error_string()
     torch.cuda.synchronize()
-    r, p, v = rows_all.cpu().numpy(), _to_np(pos_all), _to_np(val_all)
-    assert (r[:GUARD] == ROW_SENTINEL).all() and (r[GUARD + n_frames + 1:] == ROW_SENTINEL).all(), "written outside row_offsets"
-    assert (p[:GUARD] == POS_SENTINEL).all() and (p[GUARD + capacity:] == POS_SENTINEL).all(), "written outside positions"
-    sv = np.full(1, VAL_SENTINEL, dt)[0]
-    assert (v[:GUARD] == sv).all() and (v[GUARD + capacity:] == sv).all(), "written outside values"
-    if null_outputs:
-        assert (p == POS_SENTINEL).all() and (v == sv).all()
-    return r[GUARD:GUARD + n_frames + 1], p[GUARD:GUARD + capacity], v[GUARD:GUARD + capacity], int(status[0].item())
+    untouched = 0 if null_outputs else None
+    return (rows.check("row_offsets"), pos.check("positions", untouched), val.check("values", untouched), int(status[0].item()))
 
 
 def _same(got, want):
@@ -181,28 +91,19 @@ SHAPES = [(3, 7000),        # three groups, the last one short
 @pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_exactness_matrix(dt, shape):
-    for what, px in (("mixed", _random(dt, shape, seed=shape[0] * 1000 + shape[1] % 1000)), ("ladder", _ladder(dt, shape, seed=shape[1]))):
+    for what, px in (("mixed", mixed(dt, shape, seed=shape[0] * 1000 + shape[1] % 1000)), ("ladder", ladder(dt, shape, seed=shape[1]))):
         if what == "ladder" and shape[1] >= 12 * 3 * 33:     # (three cycles of the widths 0 .. 32)
-            _assert_ladder_holds_every_width_boundary(px)
-        enc = _encode(px)
+            ladder_holds_every_width(px)
+        enc = encode(px)
         ws = _ws(enc, enc.n_frames)
         for t in thresholds(dt):
             _check(enc, px, t, what=what, ws=ws)
 
 
-def _assert_ladder_holds_every_width_boundary(px):
-    """The ladder data set does what it is for (a check of the fixture, not of the code): for every width w the largest value a
-    w-bit block can hold is there."""
-    info = np.iinfo(px.dtype)
-    for w in range(1, info.bits + 1):
-        top = (1 << (w - 1 if info.min < 0 else w)) - 1
-        assert (px == top).any() and (info.min == 0 or (px == -top).any()), (px.dtype, w)
-
-
 def test_capacity():
     shape = (3, 7000)
-    px = _random(np.uint16, shape, seed=3)
-    enc = _encode(px)
+    px = mixed(np.uint16, shape, seed=3)
+    enc = encode(px)
     t = 2
     rows, pos, val = truth(px, t)
     total = int(rows[-1])
@@ -220,8 +121,8 @@ def test_capacity():
 @pytest.mark.parametrize("dt", [np.uint16, np.int32], ids=lambda d: np.dtype(d).name)
 @pytest.mark.parametrize("shape", [(3, 7000), (5, 511 * 513)], ids=lambda s: "x".join(map(str, s)))
 def test_input_forms_agree(dt, shape):
-    px = _random(dt, shape, seed=17)
-    enc = _encode(px)
+    px = mixed(dt, shape, seed=17)
+    enc = encode(px)
     for t in (1, 1 << 7):
         outs = [_check(enc, px, t, mode, what="forms") for mode in ("index", "offsets", "none")]
         outs.append(_check(enc, px, t, "index", what="second run"))
@@ -231,8 +132,8 @@ def test_input_forms_agree(dt, shape):
 
 def test_sub_stack():
     """Frames [a, b) alone: frame_offsets + a, n_frames = b - a, no index."""
-    px = _random(np.int16, (9, 7000), seed=11)
-    enc = _encode(px)
+    px = mixed(np.int16, (9, 7000), seed=11)
+    enc = encode(px)
     for a, b in ((0, 9), (2, 7), (8, 9), (3, 4)):
         _check(enc, px[a:b], 3, "offsets", what=f"frames [{a}, {b})", first=a, n_frames=b - a)
 
@@ -244,7 +145,7 @@ def test_data_kinds(kind):
     dt = np.uint16
     info = np.iinfo(dt)
     if kind == "synth":
-        px, ts = _to_np(codec.synth(np.uint16, 0, n, v)), [64]
+        px, ts = to_np(codec.synth(np.uint16, 0, n, v)), [64]
     elif kind == "poisson":
         px, ts = workloads.poisson_u16_np(3.0, 0, n, v).astype(dt), [8]
     elif kind == "blank":
@@ -252,7 +153,7 @@ def test_data_kinds(kind):
     else:
         px, ts = np.where((np.arange(v) % 2 == 0)[None, :], info.max, info.min).astype(dt).repeat(n, axis=0).reshape(n, v), [info.max]
     px = np.ascontiguousarray(px)
-    enc = _encode(px)
+    enc = encode(px)
     for t in ts:
         _check(enc, px, t, what=kind)
 
@@ -264,7 +165,7 @@ def test_large_int32_frames():
     px = (rng.poisson(3.0, size=(2, h, w)) - 1).astype(np.int32)
     px[1, : h // 3] = rng.integers(-(1 << 31), (1 << 31) - 1, size=(h // 3, w), dtype=np.int64).astype(np.int32)
     px = px.reshape(2, -1)
-    enc = _encode(px)
+    enc = encode(px)
     for mode in ("index", "offsets", "none"):
         _check(enc, px, 1 << 30, mode, what="large frames")
 
@@ -274,8 +175,8 @@ def test_corrupt_index_and_short_offsets_are_rejected():
     frame-offset table whose end is short.  Status CORRUPT, nothing written outside the outputs (checked in _sparse)."""
     import torch
     shape = (3, 7000)
-    px = _random(np.uint16, shape, seed=31)
-    enc = _encode(px)
+    px = mixed(np.uint16, shape, seed=31)
+    enc = encode(px)
     groups = 3                                              # ceil(ceil(7000 / 12) / 256)
     rows, _, _ = truth(px, 2)
     total = int(rows[-1])
@@ -296,8 +197,8 @@ def test_graph_capture_replays_with_new_stacks():
     import torch
     shape = (6, 511 * 513)
     t = 3
-    stacks = [_random(np.uint16, shape, seed=s) for s in (9, 10, 12)]
-    encs = [_encode(px) for px in stacks]
+    stacks = [mixed(np.uint16, shape, seed=s) for s in (9, 10, 12)]
+    encs = [encode(px) for px in stacks]
     truths = [truth(px, t) for px in stacks]
     capacity = max(int(tr[0][-1]) for tr in truths) + 7
     data, offs, index = encs[0].data.clone(), encs[0].frame_offsets.clone(), encs[0].index.clone()   # (capacity-sized: one geometry)
@@ -328,7 +229,7 @@ def test_graph_capture_replays_with_new_stacks():
         total = int(r[-1])
         assert int(status[0].item()) == OK
         assert np.array_equal(rows.cpu().numpy(), r)
-        assert _same(_to_np(pos)[:total], p) and _same(_to_np(val)[:total], v)
+        assert _same(to_np(pos)[:total], p) and _same(to_np(val)[:total], v)
 
 
 def test_python_surfaces():
@@ -354,11 +255,11 @@ def test_python_surfaces():
     with pytest.raises(ValueError):
         t.prolix_sparse(1, frames=[3])
     # the device-resident wrapper, sizing its outputs itself (synchronises)
-    enc = _encode(px)
+    enc = encode(px)
     r, p, v, st = codec.decode_sparse(enc.stack(), enc.frame_offsets, 700, 3, torch.uint16, 2500, index=enc.index)
     tr = truth(px, 2500)
     assert int(st[0].item()) == OK and p.numel() == int(tr[0][-1])
-    assert np.array_equal(r.cpu().numpy(), tr[0]) and _same(_to_np(p), tr[1]) and _same(_to_np(v), tr[2])
+    assert np.array_equal(r.cpu().numpy(), tr[0]) and _same(to_np(p), tr[1]) and _same(to_np(v), tr[2])
     r, p, v, st = codec.decode_sparse(enc.stack(), None, 700, 3, torch.uint16, 70000)
     assert int(st[0].item()) == OK and p.numel() == 0 and v.numel() == 0 and int(r[-1].item()) == 0
 
@@ -369,21 +270,6 @@ def test_cpp_class_prolix_sparse():
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "-f", "sparse_example.mk"])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "OK sparse example" in r.stdout, r.stdout + r.stderr
-
-
-def _events_median(fn, reps=20, warm=3):
-    import torch
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
 
 
 def test_faster_than_decoding_and_compacting():
@@ -402,7 +288,7 @@ def test_faster_than_decoding_and_compacting():
     pix = torch.empty((n, v), dtype=torch.uint16, device="cuda")
     st = torch.empty(8, dtype=torch.int32, device="cuda")
     ws = codec.Workspace("cuda")
-    t_decode = _events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, index=enc.index))
+    t_decode = events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, index=enc.index), 20)
     assert int(st[0].item()) == OK
     p16 = pix.view(torch.int16)                             # (values stay below 4096: the signed view compares alike)
     assert int(p16.max().item()) < 4096
@@ -414,14 +300,14 @@ def test_faster_than_decoding_and_compacting():
     def sparse():
         codec.decode_sparse(stack, enc.frame_offsets, v, n, torch.uint16, t, index=enc.index, capacity=total, row_offsets=rows,
                             positions=pos, values=val, workspace=ws, status=st)
-    t_sparse = _events_median(sparse)
+    t_sparse = events_median(sparse, 20)
     assert int(st[0].item()) == OK
     assert int(rows[-1].item()) == total
 
     def compact():
         nz = torch.nonzero(p16 >= t)
         return nz, p16[nz[:, 0], nz[:, 1]]
-    t_compact = _events_median(compact)
+    t_compact = events_median(compact, 20)
     nz, vals = compact()
     assert torch.equal(pos.view(torch.int32).to(torch.int64), nz[:, 1])
     assert torch.equal(val.view(torch.int16), vals)

@@ -1,11 +1,14 @@
 """GPU tests: trpx_decode_sum (decode_sum.hip).  The truth is the numpy sum, in int64, of the ORIGINAL
 pixels, clamped or rounded per output type: the codec is lossless, so no decoder is trusted."""
 import os
-import statistics
 import subprocess
 
 import numpy as np
 import pytest
+
+from gpu_support import encode, events_median, input_forms, mixed, to_np, torch_dt
+from gpu_support import sum_truth as truth
+from tiff_layout import parse_tiff
 
 pytestmark = pytest.mark.gpu
 
@@ -18,61 +21,14 @@ def _legal_outs(dt):
     return [o for o in OUTS if not (np.dtype(dt).kind == "i" and np.dtype(o).kind == "u")]
 
 
-def truth(px: np.ndarray, group: int, out_dt) -> np.ndarray:
-    n = px.shape[0]
-    p64 = px.reshape(n, -1).astype(np.int64)
-    s = np.stack([p64[j:j + group].sum(axis=0) for j in range(0, n, group)])
-    o = np.dtype(out_dt)
-    if o.kind in "iu" and o.itemsize == 4:
-        info = np.iinfo(o)
-        return np.clip(s, info.min, info.max).astype(o)
-    return s.astype(o)
-
-
-def _torch_dt(dt):
-    import torch
-    return {np.dtype(np.uint8): torch.uint8, np.dtype(np.int8): torch.int8, np.dtype(np.uint16): torch.uint16,
-            np.dtype(np.int16): torch.int16, np.dtype(np.uint32): torch.uint32, np.dtype(np.int32): torch.int32,
-            np.dtype(np.int64): torch.int64, np.dtype(np.uint64): torch.uint64, np.dtype(np.float32): torch.float32,
-            np.dtype(np.float64): torch.float64}[np.dtype(dt)]
-
-
-def _to_np(t):
-    import torch
-    if t.dtype in (torch.uint16, torch.uint32, torch.uint64):   # (numpy() of the unsigned wide types: through a view)
-        sv = {torch.uint16: torch.int16, torch.uint32: torch.int32, torch.uint64: torch.int64}[t.dtype]
-        un = {torch.uint16: np.uint16, torch.uint32: np.uint32, torch.uint64: np.uint64}[t.dtype]
-        return t.cpu().view(sv).numpy().view(un)
-    return t.cpu().numpy()
-
-
-def _to_dev(a: np.ndarray):
-    import torch
-    a = np.ascontiguousarray(a)
-    un = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
-    if a.dtype in un:
-        return torch.from_numpy(a.view(un[a.dtype])).cuda().view(_torch_dt(a.dtype))
-    return torch.from_numpy(a).cuda()
-
-
-def _encode(px: np.ndarray):
-    from trpx_amd import codec
-    import torch
-    enc = codec.encode(_to_dev(px), index=True)
-    enc.check()
-    torch.cuda.synchronize()
-    return enc
-
-
 def _sum(enc, group, out_dt, mode="index", **kw):
     from trpx_amd import codec
     import torch
-    offs = None if mode == "none" else enc.frame_offsets
-    index = enc.index if mode == "index" else None
-    sums, st = codec.decode_sum(enc.stack(), offs, enc.n_values, enc.n_frames, enc.dtype, group, out_dtype=_torch_dt(out_dt),
+    offs, index = input_forms(enc, mode)
+    sums, st = codec.decode_sum(enc.stack(), offs, enc.n_values, enc.n_frames, enc.dtype, group, out_dtype=torch_dt(out_dt),
                                 index=index, **kw)
     torch.cuda.synchronize()
-    return _to_np(sums), int(st[0].item())
+    return to_np(sums), int(st[0].item())
 
 
 def _check(px, enc, group, out_dt, mode="index"):
@@ -83,16 +39,6 @@ def _check(px, enc, group, out_dt, mode="index"):
     assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (px.dtype, px.shape, group, np.dtype(out_dt).name, mode)
 
 
-def _random(dt, n, v, seed):
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    # mixed magnitudes: small values (narrow blocks) and full-range runs (wide blocks)
-    big = rng.integers(info.min, int(info.max) + 1, size=(n, v), dtype=np.int64)
-    small = rng.integers(-3 if info.min < 0 else 0, 4, size=(n, v), dtype=np.int64)
-    sel = (np.arange(v) // 97) % 3 == 0
-    return np.where(sel[None, :], big, small).astype(dt)
-
-
 SHAPES = [(6, 512 * 512), (5, 513 * 511), (3, 1030 * 1065), (9, 7), (11, 12 * 37 + 5)]
 
 
@@ -100,8 +46,8 @@ SHAPES = [(6, 512 * 512), (5, 513 * 511), (3, 1030 * 1065), (9, 7), (11, 12 * 37
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_exactness_matrix(dt, shape):
     n, v = shape
-    px = _random(dt, n, v, seed=n * 1000 + v)
-    enc = _encode(px)
+    px = mixed(dt, shape, seed=n * 1000 + v)
+    enc = encode(px)
     for group in sorted({1, 3, max(2, n - 1), n, n + 5}):      # (n - 1: a group that does not divide n)
         for out_dt in _legal_outs(dt):
             _check(px, enc, group, out_dt)
@@ -114,7 +60,7 @@ def test_data_kinds(kind, dt):
     n, v = 17, 513 * 511
     if kind == "synth":
         base = codec.synth(np.uint16 if np.dtype(dt).itemsize <= 2 else np.int32, 0, n, v).cpu()
-        px = _to_np(base).astype(np.int64)
+        px = to_np(base).astype(np.int64)
         info = np.iinfo(dt)
         px = np.clip(px, info.min, info.max).astype(dt)
     elif kind == "poisson":
@@ -124,7 +70,7 @@ def test_data_kinds(kind, dt):
     else:
         info = np.iinfo(dt)
         px = np.where((np.arange(v) % 2 == 0)[None, :], info.max, info.min).astype(dt).repeat(n, axis=0).reshape(n, v)
-    enc = _encode(px)
+    enc = encode(px)
     for group in (1, 4, n):
         for out_dt in (np.int32, np.int64, np.float32):
             _check(px, enc, group, out_dt)
@@ -137,7 +83,7 @@ def test_large_int32_frames():
     v = 4096 * 4096
     px = (rng.poisson(3.0, size=(4, v)) - 1).astype(np.int32)
     px[1, : v // 3] = rng.integers(-(1 << 31), (1 << 31) - 1, size=v // 3, dtype=np.int64).astype(np.int32)
-    enc = _encode(px)
+    enc = encode(px)
     for group in (1, 3, 4):
         for mode in ("index", "offsets", "none"):
             _check(px, enc, group, np.int64, mode)
@@ -151,7 +97,7 @@ def test_clamping_of_32bit_streams(dt, out_dt):
     px = np.full((5, 1000), info.max, dt)
     px[:, ::2] = info.min
     px[:, 1::4] = info.max // 3
-    enc = _encode(px)
+    enc = encode(px)
     for group in (1, 2, 5):
         _check(px, enc, group, out_dt)
         _check(px, enc, group, np.int64)
@@ -160,7 +106,7 @@ def test_clamping_of_32bit_streams(dt, out_dt):
 def test_u16_saturates_int32_past_32768_frames():
     n = 32769
     px = np.full((n, 40), 65535, np.uint16)
-    enc = _encode(px)
+    enc = encode(px)
     got, code = _sum(enc, n, np.int32)
     assert code == 0 and (got == np.iinfo(np.int32).max).all()
     got, code = _sum(enc, n, np.int64)
@@ -173,8 +119,8 @@ def test_input_forms_agree_and_file_round_trip(tmp_path):
     from trpx_amd.terse import Terse
     from trpx_amd import codec
     import torch
-    px = _random(np.uint16, 40, 513 * 511, seed=3)
-    enc = _encode(px)
+    px = mixed(np.uint16, (40, 513 * 511), seed=3)
+    enc = encode(px)
     outs = [_sum(enc, g, np.float32, mode)[0] for g in (7,) for mode in ("index", "offsets", "none")]
     assert all(np.array_equal(outs[0].view(np.uint32), o.view(np.uint32)) for o in outs)
     assert np.array_equal(outs[0], truth(px, 7, np.float32))
@@ -200,8 +146,8 @@ def test_input_forms_agree_and_file_round_trip(tmp_path):
 def test_sub_range():
     from trpx_amd import codec
     import torch
-    px = _random(np.int16, 30, 5000, seed=11)
-    enc = _encode(px)
+    px = mixed(np.int16, (30, 5000), seed=11)
+    enc = encode(px)
     for a, b in ((0, 30), (5, 17), (29, 30), (3, 4)):
         offs = enc.frame_offsets[a:]
         got, st = codec.decode_sum(enc.stack(), offs, enc.n_values, b - a, np.int16, 4, out_dtype=torch.int64)
@@ -211,8 +157,8 @@ def test_sub_range():
 
 
 def test_deterministic():
-    px = _random(np.uint32, 300, 512 * 512 // 4, seed=5)
-    enc = _encode(px)
+    px = mixed(np.uint32, (300, 512 * 512 // 4), seed=5)
+    enc = encode(px)
     for group, out_dt in ((300, np.float32), (300, np.uint64), (7, np.float32)):
         a, _ = _sum(enc, group, out_dt)
         b, _ = _sum(enc, group, out_dt, mode="offsets")
@@ -225,8 +171,8 @@ def test_deterministic():
 def test_graph_capture(mode):
     from trpx_amd import codec
     import torch
-    px = _random(np.uint16, 64, 513 * 511, seed=9)
-    enc = _encode(px)
+    px = mixed(np.uint16, (64, 513 * 511), seed=9)
+    enc = encode(px)
     stack = enc.stack()
     offs = enc.frame_offsets if mode == "offsets" else None
     ws = codec.Workspace(stack.device)
@@ -252,8 +198,8 @@ def test_graph_capture(mode):
 def test_corruption():
     from trpx_amd import codec
     import torch
-    px = _random(np.uint16, 12, 513 * 511, seed=13)
-    enc = _encode(px)
+    px = mixed(np.uint16, (12, 513 * 511), seed=13)
+    enc = encode(px)
     bad_index = enc.index.clone().fill_(0xFF)
     sums, st = codec.decode_sum(enc.stack(), enc.frame_offsets, enc.n_values, enc.n_frames, np.uint16, 3, index=bad_index)
     torch.cuda.synchronize()
@@ -274,11 +220,10 @@ def test_cli_and_cpp_class_sum(tmp_path):
     """prolix -sum N writes the grouped sums as a 32-bit TIFF (int32 / uint32, clamped); its -sum path is the C++
     Terse::prolix_sum."""
     from trpx_amd.terse import Terse
-    from test_cli_tiff import _parse_tiff
     prolix = os.path.join(ROOT, "trpx_amd", "bin", "prolix")
     assert os.path.exists(prolix), "build() builds the CLI tools"
     for dt, want_dt in ((np.uint16, np.uint32), (np.int16, np.int32)):
-        px = _random(dt, 10, 64 * 48, seed=17).reshape(10, 48, 64)
+        px = mixed(dt, (10, 64 * 48), seed=17).reshape(10, 48, 64)
         t = Terse()
         t.push_back_stack(px.reshape(10, -1))
         t.dim([64, 48])
@@ -290,24 +235,9 @@ def test_cli_and_cpp_class_sum(tmp_path):
         tifs = sorted(p for p in os.listdir(tmp_path) if p.startswith(f"s_{np.dtype(dt).name}") and p.endswith(".tif"))
         assert tifs, os.listdir(tmp_path)
         assert tifs == [f"s_{np.dtype(dt).name}.tif"]
-        got = _parse_tiff(str(tmp_path / tifs[0])).reshape(-1, 48 * 64)
+        got = parse_tiff(str(tmp_path / tifs[0])).reshape(-1, 48 * 64)
         want = truth(px, 4, want_dt)
         assert got.dtype.kind == want.dtype.kind and got.dtype.itemsize == 4 and np.array_equal(got, want)
-
-
-def _events_median(fn, reps=15, warm=3):
-    import torch
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
 
 
 def _speed_stack(kind):
@@ -336,9 +266,9 @@ def test_speed_with_index(kind, group, ceiling):
     ws = codec.Workspace(stack.device)
     ws.get(codec.decode_sum_workspace_bytes(stack.numel(), v, n, np.uint16, group))
     st = torch.empty(8, dtype=torch.int32, device="cuda")
-    t_dec = _events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, index=enc.index))
-    t_sum = _events_median(lambda: codec.decode_sum(stack, enc.frame_offsets, v, n, np.uint16, group, out=sums, index=enc.index,
-                                                    workspace=ws, status=st))
+    t_dec = events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, index=enc.index), 15)
+    t_sum = events_median(lambda: codec.decode_sum(stack, enc.frame_offsets, v, n, np.uint16, group, out=sums, index=enc.index,
+                                                   workspace=ws, status=st), 15)
     print(f"\n{kind} group {group}: decode_indexed {t_dec:.4f} ms, decode_sum {t_sum:.4f} ms, ratio {t_sum / t_dec:.3f}")
     assert int(st[0].item()) == 0
     assert t_sum <= ceiling * t_dec, (t_sum, t_dec)
@@ -356,8 +286,8 @@ def test_speed_without_index(kind):
     ws.get(max(codec.decode_sum_workspace_bytes(stack.numel(), v, n, np.uint16, 10),
                __import__("trpx_amd")._lib.lib().trpx_decode_workspace_bytes(2, v, n, 12)))
     st = torch.empty(8, dtype=torch.int32, device="cuda")
-    t_dec = _events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, workspace=ws))
-    t_sum = _events_median(lambda: codec.decode_sum(stack, enc.frame_offsets, v, n, np.uint16, 10, out=sums, workspace=ws, status=st))
+    t_dec = events_median(lambda: codec.decode(stack, enc.frame_offsets, v, n, torch.uint16, out=pix, status=st, workspace=ws), 15)
+    t_sum = events_median(lambda: codec.decode_sum(stack, enc.frame_offsets, v, n, np.uint16, 10, out=sums, workspace=ws, status=st), 15)
     print(f"\n{kind} no index: decode {t_dec:.4f} ms, decode_sum {t_sum:.4f} ms, ratio {t_sum / t_dec:.3f}")
     assert int(st[0].item()) == 0
     assert t_sum <= (2.7 if kind == "synth" else 1.7) * t_dec, (t_sum, t_dec)

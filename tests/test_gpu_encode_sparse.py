@@ -3,21 +3,18 @@ frames; the same frames through trpx_encode are a second witness; neither is cod
 on the stack (the zeroed bytes up to align4(total) included), the frame offsets, status word 0 and prolix_bits.  `out` and
 `frame_offsets` sit in the middle of guarded allocations, 64 sentinel elements on either side."""
 import os
-import statistics
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_gpu_decode_sparse import _ladder, _random, _to_dev, _to_np, _torch_dt
+from gpu_support import CAPACITY, INVALID_ARG, OK, Guarded, events_median, ladder, mixed, status_block, to_dev, torch_dt
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
-GUARD = 64
 OUT_SENTINEL, OFF_SENTINEL = 0xA5, 0x5A5A5A5A5A5A5A5A
-OK, INVALID_ARG, CAPACITY = 0, 1, 3
 TILE = 3072
 IDS = dict(ids=lambda d: np.dtype(d).name)
 
@@ -49,14 +46,14 @@ class Lists:
         self.dt = np.dtype(dt)
         self.n_events = int(len(pos))
         self.rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).cuda()
-        self.pos = _to_dev(np.asarray(pos, np.uint32)) if self.n_events else None
-        self.val = _to_dev(np.asarray(val, self.dt)) if self.n_events else None
+        self.pos = to_dev(np.asarray(pos, np.uint32)) if self.n_events else None
+        self.val = to_dev(np.asarray(val, self.dt)) if self.n_events else None
 
 
 def _ws(dt, n_values, n_frames, extra=0):
     from trpx_amd import codec
     import torch
-    need = codec.encode_sparse_workspace_bytes(_torch_dt(dt), n_values, n_frames)
+    need = codec.encode_sparse_workspace_bytes(torch_dt(dt), n_values, n_frames)
     assert need > 0
     return torch.empty(need + extra, dtype=torch.uint8, device="cuda")
 
@@ -69,28 +66,21 @@ def _call(ev: Lists, n_values, n_frames, capacity=None, null_out=False, first=0,
     import torch
     n_events = ev.n_events if n_events is None else n_events
     if capacity is None:
-        capacity = codec.encode_sparse_bound_bytes(_torch_dt(ev.dt), n_values, n_frames, n_events)
+        capacity = codec.encode_sparse_bound_bytes(torch_dt(ev.dt), n_values, n_frames, n_events)
         assert capacity > 0 and capacity % 16 == 0
-    out_all = torch.full((capacity + 2 * GUARD,), OUT_SENTINEL, dtype=torch.uint8, device="cuda")
-    off_all = torch.full((n_frames + 1 + 2 * GUARD,), OFF_SENTINEL, dtype=torch.int64, device="cuda")
-    out, offs = out_all[GUARD:GUARD + capacity], off_all[GUARD:GUARD + n_frames + 1]
-    status = torch.full((8,), 77, dtype=torch.int32, device="cuda")
+    out, offs = Guarded(capacity, np.uint8, OUT_SENTINEL), Guarded(n_frames + 1, np.int64, OFF_SENTINEL)
+    status = status_block()
     ws = _ws(ev.dt, n_values, n_frames, 64) if ws is None else ws
     rows = ev.rows[first:]
-    rc = _lib.lib().trpx_encode_sparse(dtype_code(_torch_dt(ev.dt)), rows.data_ptr(), ev.pos.data_ptr() if ev.pos is not None else None,
+    rc = _lib.lib().trpx_encode_sparse(dtype_code(torch_dt(ev.dt)), rows.data_ptr(), ev.pos.data_ptr() if ev.pos is not None else None,
                                        ev.val.data_ptr() if ev.val is not None else None, n_events, n_values, n_frames, 12,
-                                       None if null_out else out.data_ptr(), 0 if null_out else capacity, offs.data_ptr(),
+                                       None if null_out else out.view.data_ptr(), 0 if null_out else capacity, offs.view.data_ptr(),
                                        status.data_ptr(), ws.data_ptr() + ws_shift, ws.numel() - ws_shift,
                                        torch.cuda.current_stream().cuda_stream)
     assert rc == 0, _lib.lib().trpx_last_error_string()
     torch.cuda.synchronize()
-    o, r = out_all.cpu().numpy(), off_all.cpu().numpy()
-    assert (o[:GUARD] == OUT_SENTINEL).all() and (o[GUARD + capacity:] == OUT_SENTINEL).all(), "written outside out"
-    assert (r[:GUARD] == OFF_SENTINEL).all() and (r[GUARD + n_frames + 1:] == OFF_SENTINEL).all(), "written outside frame_offsets"
-    if null_out:
-        assert (o == OUT_SENTINEL).all()
     st = status.cpu().numpy()
-    return o[GUARD:GUARD + capacity], r[GUARD:GUARD + n_frames + 1], int(st[0]), int(st[1])
+    return out.check("out", 0 if null_out else None), offs.check("frame_offsets"), int(st[0]), int(st[1])
 
 
 class Truth:
@@ -104,7 +94,7 @@ class Truth:
         self.offs = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))]).astype(np.int64)
         self.total = int(self.offs[-1])
         self.bytes = np.concatenate([want, np.zeros(_align(self.total, 4) - self.total, np.uint8)])
-        enc = codec.encode(_to_dev(px))                      # the second witness
+        enc = codec.encode(to_dev(px))                      # the second witness
         enc.check()
         torch.cuda.synchronize()
         assert np.array_equal(enc.frame_offsets.cpu().numpy(), self.offs) and enc.prolix_bits() == self.pb
@@ -132,7 +122,7 @@ def _check(px, oracle, lists=None, ctx="", **kw):
 def _sparse_mixed(dt, shape, seed, occupancy=0.05):
     """Mixed magnitudes (narrow and full-width blocks, the type's minimum included) on `occupancy` of the pixels."""
     rng = np.random.default_rng(seed)
-    px = _random(dt, shape, seed)
+    px = mixed(dt, shape, seed)
     info = np.iinfo(dt)
     px[rng.random(shape) < 0.01] = info.min if info.min < 0 else info.max
     px[rng.random(shape) >= occupancy] = 0
@@ -206,7 +196,7 @@ def test_event_placement(oracle, dt, n_values):
 @pytest.mark.parametrize("dt", DTYPES, **IDS)
 def test_width_ladder(oracle, dt, n_values):
     """One block of each width 0 .. bits(T); signed types with negative values and the type's minimum."""
-    px = _ladder(dt, (3, n_values), seed=n_values)
+    px = ladder(dt, (3, n_values), seed=n_values)
     info = np.iinfo(dt)
     if info.min < 0:
         px[1, 7] = info.min
@@ -221,20 +211,20 @@ def test_every_pixel_an_event_and_round_trip(oracle, dt, n_values):
     Threshold 1 (unsigned) / the minimum (signed): the events that rebuild the original stream."""
     from trpx_amd import codec
     import torch
-    px = _random(dt, (4, n_values), seed=n_values + 1)
+    px = mixed(dt, (4, n_values), seed=n_values + 1)
     tr = Truth(px, oracle)
     info = np.iinfo(dt)
-    enc = codec.encode(_to_dev(px), index=True)
+    enc = codec.encode(to_dev(px), index=True)
     enc.check()
     for t in sorted({int(info.min), 1 if info.min == 0 else int(info.min)}):
-        rows, pos, val, st = codec.decode_sparse(enc.stack(), enc.frame_offsets, n_values, 4, _torch_dt(dt), t, index=enc.index)
+        rows, pos, val, st = codec.decode_sparse(enc.stack(), enc.frame_offsets, n_values, 4, torch_dt(dt), t, index=enc.index)
         assert int(st[0].item()) == OK
         if t <= info.min:
             assert pos.numel() == 4 * n_values
         ev = Lists([0], [], [], dt)
         ev.rows, ev.pos, ev.val, ev.n_events = rows, pos, val, pos.numel()      # int64 rows, uint32 positions: as returned
         _assert_exact(_call(ev, n_values, 4), tr, ("round trip", dt, n_values, t))
-        again = codec.encode_sparse(rows, pos, val, n_values, 4, _torch_dt(dt))  # the python surface, sizing `out` itself
+        again = codec.encode_sparse(rows, pos, val, n_values, 4, torch_dt(dt))  # the python surface, sizing `out` itself
         again.check()
         assert again.total_bytes() == tr.total and again.prolix_bits() == tr.pb
         assert np.array_equal(again.stack().cpu().numpy(), tr.bytes[:tr.total])
@@ -304,12 +294,12 @@ def test_bad_events_are_reported_and_bounded(oracle):
                  "row_offsets[n_frames] = n_events + 1"):
         r, p, n_events = bent(what)
         ev.rows.copy_(torch.from_numpy(r))
-        ev.pos.copy_(_to_dev(p))
+        ev.pos.copy_(to_dev(p))
         for cap in (None, 16):                               # INVALID_ARG wins over CAPACITY
             _, _, code, _ = _call(ev, n_values, n_frames, capacity=cap, n_events=n_events, ws=ws)    # (guards checked in there)
             assert code == INVALID_ARG, (what, cap)
         ev.rows.copy_(torch.from_numpy(rows))                # a good call on the same buffers is exact again
-        ev.pos.copy_(_to_dev(pos))
+        ev.pos.copy_(to_dev(pos))
         _assert_exact(_call(ev, n_values, n_frames, ws=ws), tr, "after " + what)
 
 
@@ -348,8 +338,8 @@ def test_graph_capture_replays_with_new_events(oracle):
     def load(k):
         r, p, v = lists[k]
         rows.copy_(torch.from_numpy(r))
-        pos[:len(p)].copy_(_to_dev(p))
-        val[:len(v)].copy_(_to_dev(v))
+        pos[:len(p)].copy_(to_dev(p))
+        val[:len(v)].copy_(to_dev(v))
 
     def call():
         codec.encode_sparse(rows, pos, val, n_values, n_frames, torch.uint16, out=out, workspace=ws, frame_offsets=offs, status=status)
@@ -407,21 +397,6 @@ def test_cpp_class_push_back_sparse():
 
 
 # ---- speed ----------------------------------------------------------------------------------------------------------------------
-def _events_median(fn, reps=20, warm=3):
-    import torch
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
-
-
 def test_faster_than_scattering_and_encoding():
     """2000 x 512^2 u16 Poisson(3), the events at threshold 8, resident.  The baseline is what a caller pays without this entry
     point: zero_ the dense stack, index_put_ the events, trpx_encode it -- in the same process, so no margin is needed.
@@ -444,7 +419,7 @@ def test_faster_than_scattering_and_encoding():
     want_offs = enc.frame_offsets.clone()
     out, offs, status = torch.empty_like(enc.data), torch.empty_like(enc.frame_offsets), torch.empty(8, dtype=torch.int32, device="cuda")
     del enc
-    t_dense = _events_median(lambda: codec.encode(px, out=out, workspace=ws, frame_offsets=offs, status=status))
+    t_dense = events_median(lambda: codec.encode(px, out=out, workspace=ws, frame_offsets=offs, status=status), 20)
     assert int(status[0].item()) == OK and torch.equal(offs, want_offs)
 
     frame = torch.repeat_interleave(torch.arange(n, device="cuda"), rows[1:] - rows[:-1])
@@ -455,13 +430,13 @@ def test_faster_than_scattering_and_encoding():
         p16.zero_()
         p16.index_put_((frame, col), v16)
         codec.encode(px, out=out, workspace=ws, frame_offsets=offs, status=status)
-    t_replaced = _events_median(replaced)
+    t_replaced = events_median(replaced, 20)
     assert int(status[0].item()) == OK and torch.equal(offs, want_offs) and torch.equal(out[:want.numel()], want)
 
     sws = codec.Workspace("cuda")
     sout = torch.empty(codec.encode_sparse_bound_bytes(torch.uint16, v, n, n_events), dtype=torch.uint8, device="cuda")
-    t_sparse = _events_median(lambda: codec.encode_sparse(rows, pos, val, v, n, torch.uint16, out=sout, workspace=sws,
-                                                          frame_offsets=offs, status=status))
+    t_sparse = events_median(lambda: codec.encode_sparse(rows, pos, val, v, n, torch.uint16, out=sout, workspace=sws,
+                                                         frame_offsets=offs, status=status), 20)
     assert int(status[0].item()) == OK and torch.equal(offs, want_offs) and torch.equal(sout[:want.numel()], want)
     print(f"\n2000 x 512^2 u16 Poisson(3), t = 8, {n_events} events, {want.numel()} bytes: encode_sparse {t_sparse:.4f} ms, "
           f"trpx_encode {t_dense:.4f} ms, zero_ + index_put_ + trpx_encode {t_replaced:.4f} ms, "

@@ -8,6 +8,8 @@ import io
 import numpy as np
 import pytest
 
+from gpu_support import encode
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
@@ -48,15 +50,6 @@ def _random_widths(dtype, frames, n, seed, gpu):
 def _wrap_signed(v, bits):
     v = v & ((1 << bits) - 1)
     return v - ((v >> (bits - 1)) << bits)
-
-
-def _encode(px):
-    import torch
-    from trpx_amd import codec
-    enc = codec.encode(px)
-    torch.cuda.synchronize()
-    enc.check()
-    return enc
 
 
 def py_locate(stream, n, frames, max_w, block=12):
@@ -112,7 +105,7 @@ def test_locate_matches_encoder_across_shapes(gpu, dtype):
              (1030 * 1065, 2), (1, 1), (5, 2), (13, 7), (512 * 512, 1)]
     for i, (n, frames) in enumerate(cases):
         px = _random_widths(dtype, frames, n, 1000 * i + DTYPES.index(dtype), gpu)
-        enc = _encode(px)
+        enc = encode(px, index=False)
         offs, st = _locate(enc.stack(), n, frames, dtype)
         assert st[0] == 0, (n, frames, st)
         assert (offs == enc.frame_offsets.cpu().numpy()).all(), (n, frames)
@@ -125,7 +118,7 @@ def test_locate_all_zero_and_saturated_frames(gpu):
     n, frames = 512 * 512, 40
     for fill in (0, -1):
         px = torch.full((frames, n), fill, dtype=torch.int16, device=gpu).view(torch.uint16)
-        enc = _encode(px)
+        enc = encode(px, index=False)
         offs, st = _locate(enc.stack(), n, frames, np.uint16)
         assert st[0] == 0 and (offs == enc.frame_offsets.cpu().numpy()).all(), fill
 
@@ -136,7 +129,7 @@ def test_locate_tiny_frames_between_header_dense_ones(gpu):
         frames = 60
         px = _random_widths(np.uint16, frames, n, 77, gpu)
         px.view(torch.int16)[0::2] = 0                                    # every other frame compresses to ~1 bit per block
-        enc = _encode(px)
+        enc = encode(px, index=False)
         offs, st = _locate(enc.stack(), n, frames, np.uint16)
         assert st[0] == 0 and (offs == enc.frame_offsets.cpu().numpy()).all(), n
 
@@ -154,7 +147,7 @@ def test_locate_frames_with_a_whole_pad_byte(gpu):
     nv[-1] = n - 12 * (w.shape[1] - 1)
     bits = (hl + nv[None, :] * w).sum(axis=1)
     assert (bits % 8 == 0).sum() >= 5
-    enc = _encode(px)
+    enc = encode(px, index=False)
     offs, st = _locate(enc.stack(), n, frames, np.uint16)
     assert st[0] == 0 and (offs == enc.frame_offsets.cpu().numpy()).all()
 
@@ -164,7 +157,7 @@ def test_locate_with_pad_bits_set(gpu):
     from oracle import oracle as O
     n, frames = 12 * 37 + 5, 120
     px = _random_widths(np.uint16, frames, n, 9, gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().cpu().numpy().copy()
     offs = enc.frame_offsets.cpu().numpy()
     host = px.cpu().numpy()
@@ -188,7 +181,7 @@ def test_locate_full_size_stacks(gpu, kind):
     from trpx_amd import codec, workloads
     n, frames = 512 * 512, 2000
     px = codec.synth(np.uint16, 0, frames, n, device=gpu) if kind == "synth" else workloads.poisson_u16(3.0, 0, frames, n, device=gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack()
     offs, st = codec.locate_frames(stack, n, frames, np.uint16)
     torch.cuda.synchronize()
@@ -205,7 +198,7 @@ def test_locate_hostile_streams(gpu):
     from trpx_amd import _lib
     n, frames = 12 * 85 + 7, 40
     px = _random_widths(np.uint16, frames, n, 21, gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().cpu().numpy().copy()
     offs = enc.frame_offsets.cpu().numpy()
     # truncated
@@ -245,7 +238,7 @@ def test_host_locate_and_stack_open_without_offsets(gpu):
     L = _lib.lib()
     n, frames = 12 * 300 + 1, 300
     px = _random_widths(np.uint16, frames, n, 31, gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = np.ascontiguousarray(enc.stack().cpu().numpy())
     want = enc.frame_offsets.cpu().numpy().astype(np.uint64)
     got = np.zeros(frames + 1, np.uint64)
@@ -285,7 +278,7 @@ def test_locate_and_decode_capture_into_hip_graph(gpu):
     from trpx_amd import codec, _lib
     n, frames = 512 * 512, 64
     px = codec.synth(np.uint16, 0, frames, n, device=gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().clone()
     ws_l, ws_d = codec.Workspace(gpu), codec.Workspace(gpu)
     L = _lib.lib()

@@ -6,6 +6,8 @@ the two 2000-frame stacks, 5.9 s for the decode without offsets)."""
 import numpy as np
 import pytest
 
+from gpu_support import encode
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
@@ -61,15 +63,6 @@ def _walk_block_starts(stack, fo, n, max_w):
     return starts
 
 
-def _encode(px):
-    import torch
-    from trpx_amd import codec
-    enc = codec.encode(px)
-    torch.cuda.synchronize()
-    enc.check()
-    return enc
-
-
 def _random_widths(dtype, frames, n, seed, gpu, keep_p=0.5):
     """Blocks of random widths (a share keep_p of them keeps the previous block's width)."""
     import torch
@@ -94,7 +87,7 @@ def _random_widths(dtype, frames, n, seed, gpu, keep_p=0.5):
 
 def _check_exact(px, dtype):
     n, frames = px[0].numel(), px.shape[0]
-    enc = _encode(px)
+    enc = encode(px, index=False)
     offs, st = _locate(enc.stack(), n, frames, dtype)
     assert st == 0, (n, frames, st)
     assert np.array_equal(offs, enc.frame_offsets.cpu().numpy()), (n, frames)
@@ -169,12 +162,12 @@ def test_parallel_locate_adversarial_streams(gpu):
     alt[::2] = workloads.poisson_u16(10.0, 0, 32, n, device=gpu)
     cases["alternating"] = alt
     for label, px in cases.items():
-        enc = _encode(px.contiguous())
+        enc = encode(px.contiguous(), index=False)
         got = _vs_serial(enc.stack(), n, px.shape[0], np.uint16, label)
         assert got[1] == 0 and np.array_equal(got[0], enc.frame_offsets.cpu().numpy()), label
     # pad bits set to garbage: the stack is no longer the encoder's, the serial route is the truth
     px = workloads.poisson_u16(3.0, 1, 64, n, device=gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().cpu().numpy().copy()
     offs = enc.frame_offsets.cpu().numpy()
     rng = np.random.default_rng(3)
@@ -186,7 +179,7 @@ def test_parallel_locate_adversarial_streams(gpu):
 def test_parallel_locate_hostile_streams(gpu):
     from trpx_amd import workloads
     n, frames = 128 * 128, 48
-    enc = _encode(workloads.poisson_u16(3.0, 2, frames, n, device=gpu))
+    enc = encode(workloads.poisson_u16(3.0, 2, frames, n, device=gpu), index=False)
     stack = enc.stack().cpu().numpy()
     offs = enc.frame_offsets.cpu().numpy()
     _vs_serial(stack[: offs[frames // 2] + 10], n, frames, np.uint16, "truncated")
@@ -219,7 +212,7 @@ def test_parallel_locate_graph_capture(gpu):
     n, frames = 128 * 128, 2000
     px_a = workloads.poisson_u16(3.0, 0, frames, n, device=gpu)
     px_b = px_a.flip(0).contiguous()                       # the same frames reversed: a different stack of the same length
-    a, b = _encode(px_a), _encode(px_b)
+    a, b = encode(px_a, index=False), encode(px_b, index=False)
     assert a.stack().numel() == b.stack().numel()
     buf = a.stack().clone()
     offs = torch.empty(frames + 1, dtype=torch.int64, device=gpu)
@@ -257,7 +250,7 @@ def test_parallel_locate_speed_ceiling(gpu, kind):
     from trpx_amd import codec, workloads
     n, frames = 512 * 512, 2000
     px = codec.synth(np.uint16, 0, frames, n, device=gpu) if kind == "synth" else workloads.poisson_u16(3.0, 0, frames, n, device=gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().clone()
     want = enc.frame_offsets.clone()
     del enc, px
@@ -289,7 +282,7 @@ def test_decode_without_offsets_exact(gpu, shape):
     from trpx_amd import codec, workloads
     frames, n = shape
     px = workloads.poisson_u16(3.0, 0, frames, n, device=gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().clone()
     del enc
     back, st = codec.decode(stack, None, n, frames, np.uint16)
@@ -302,7 +295,7 @@ def test_decode_without_offsets_corrupt(gpu):
     import torch
     from trpx_amd import codec, workloads
     n, frames = 128 * 128, 48
-    enc = _encode(workloads.poisson_u16(3.0, 4, frames, n, device=gpu))
+    enc = encode(workloads.poisson_u16(3.0, 4, frames, n, device=gpu), index=False)
     offs = enc.frame_offsets.cpu().numpy()
     truncated = enc.stack()[: int(offs[frames // 2]) + 10].clone()
     _, st = codec.decode(truncated, None, n, frames, np.uint16)
@@ -318,7 +311,7 @@ def test_decode_without_offsets_speed_ceiling(gpu):
     from trpx_amd import codec, workloads
     n, frames = 512 * 512, 2000
     px = workloads.poisson_u16(3.0, 0, frames, n, device=gpu)
-    enc = _encode(px)
+    enc = encode(px, index=False)
     stack = enc.stack().clone()
     del enc
     ws = codec.Workspace(gpu)

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import noncanonical as nc
+from gpu_support import sparse_truth, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -268,11 +269,6 @@ def _stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _up(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
 def _buf(nbytes):
     import torch
     return torch.full((nbytes + 2 * GB,), FILL, dtype=torch.uint8, device="cuda")
@@ -436,7 +432,7 @@ class Dev:
         b, h, w, want = self.boxes(which)
         out, st = _buf(want.nbytes), _status()
         ws = self._ws(L.trpx_decode_roi_workspace_bytes(self.code, self.nbytes, self.n, self.frames, 12))
-        db = _up(b)
+        db = to_dev(b)
         offs, index = self._forms(form, idx)
         rc = L.trpx_decode_roi(self.code, self.terse.data_ptr(), self.nbytes, offs, index, self.n, self.frames, 12, self.n, db.data_ptr(),
                                b.shape[0], h, w, _ptr(out), st.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
@@ -444,9 +440,8 @@ class Dev:
         return _verdict(rc, status, [_read(out, want.nbytes) + (want,)])
 
     def sparse(self, form, idx, t):
-        from test_gpu_decode_sparse import truth
         L = _L()
-        rows, pos, val = truth(self.S.px, t)
+        rows, pos, val = sparse_truth(self.S.px, t)
         total = int(rows[-1])
         r, p, v, st = _buf(rows.nbytes), _buf(pos.nbytes), _buf(val.nbytes), _status()
         ws = self._ws(L.trpx_decode_sparse_workspace_bytes(self.code, self.nbytes, self.n, self.frames, 12))
@@ -526,9 +521,8 @@ def _host_cells(S, D):
         rc = L.trpx_decode_roi_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, n, frames, 12, n, b.ctypes.data, b.shape[0], h_, w_,
                                     out.ctypes.data + GB, -1)
         cells[f"roi_host|offsets|0:{which}"] = _host_verdict(rc, [_hread(out, want.nbytes) + (want,)])
-    from test_gpu_decode_sparse import truth
     for thr in (1, 1 << 7):
-        rows, pos, val = truth(S.px, thr)
+        rows, pos, val = sparse_truth(S.px, thr)
         total = int(rows[-1])
         r_, p_, v_ = _hbuf(rows.nbytes), _hbuf(pos.nbytes), _hbuf(val.nbytes)
         found = C.c_size_t(0)

@@ -11,14 +11,13 @@ import numpy as np
 import pytest
 
 from alignment import align_up, carve, carve_copy, carve_stream, same_bytes, to_bytes
-from test_gpu_decode_dot import _random, _to_dev, _to_np
+from gpu_support import CAPACITY, CORRUPT, INVALID_ARG, OK, encode, mixed, to_dev, to_np
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 4096                                                # bytes of `out` a wavefront owns at a time (kSelChunk, select_map.hpp)
 LINE = 16                                                   # bytes of an output line
-OK, INVALID_ARG, CAPACITY, CORRUPT = 0, 1, 3, 5
 MISALIGN_SEED = 0                                           # chosen with the oracle encoder: see test_misalignment
 
 
@@ -29,11 +28,7 @@ def _code(dt):
 
 def _encode(px, block=12, index=None):
     """codec.encode of [frames, values] pixels: (stream bytes, offsets int64 [frames + 1], Encoded), on the host."""
-    import torch
-    from trpx_amd import codec
-    enc = codec.encode(_to_dev(px), block=block, index=index)
-    enc.check()
-    torch.cuda.synchronize()
+    enc = encode(px, index=index, block=block)
     return enc.stack().cpu().numpy().copy(), enc.frame_offsets.cpu().numpy().copy(), enc
 
 
@@ -111,7 +106,7 @@ def _lists(n, seed):
 # ---- misalignment: every (source residue, destination residue) pair ----------------------------------------------------------
 @pytest.fixture(scope="module")
 def small_u8(gpu):
-    px = _random(np.uint8, (48, 100), MISALIGN_SEED)
+    px = mixed(np.uint8, (48, 100), MISALIGN_SEED, zero_stretch=True)
     src, off, _ = _encode(px)
     return px, src, off
 
@@ -173,7 +168,7 @@ def test_every_container(gpu, oracle, dt):
     oracle's decoders (the project's own; the reference's where it is built) turn it into px[frames]."""
     import torch
     frames = np.array([6, 1, 1, 4, 0])
-    px = _random(dt, (7, 1000), 11)
+    px = mixed(dt, (7, 1000), 11, zero_stretch=True)
     if np.dtype(dt).itemsize == 4:
         # the reference's own decoder does not expand 32-bit wide fields (on the encoder's source stream either: checked with
         # oracle/_ref on the CPU), so the 32-bit containers carry values of up to 31 significant bits here
@@ -200,7 +195,7 @@ def test_int64_and_block_7_are_bytes_only(gpu):
     px64 = np.random.default_rng(12).integers(-(1 << 50), 1 << 50, size=(7, 1000)).astype(np.int64)
     src, off, _ = _encode(px64)
     select(src, off, [3, 3, 0, 6], 1000, np.int64)
-    px = _random(np.uint16, (7, 1000), 13)
+    px = mixed(np.uint16, (7, 1000), 13, zero_stretch=True)
     src, off, _ = _encode(px, block=7)
     select(src, off, [5, 2, 6, 6, 0], 1000, np.uint16, block=7)
 
@@ -245,13 +240,13 @@ def test_index(gpu, dt):
     L = _lib.lib()
     n = 7000                                                 # 584 blocks (rows end inside 16-byte lines), 3 groups
     frames = np.array([6, 1, 1, 4, 0, 6, 2, 3, 5])
-    px = _random(dt, (7, n), 21)
+    px = mixed(dt, (7, n), 21, zero_stretch=True)
     src, off, enc = _encode(px, index=True)
     d_out, d_out_off, d_index, total = select(src, off, frames, n, dt, index=enc.index)
     stack = d_out[:align_up(total, 4)].clone()               # (a fresh tensor: 256-byte aligned)
     back, st = codec.decode(stack[:total], d_out_off.clone(), n, frames.size, dt, index=d_index)
     torch.cuda.synchronize()
-    assert int(st[0].item()) == OK and np.array_equal(_to_np(back), px[frames])
+    assert int(st[0].item()) == OK and np.array_equal(to_np(back), px[frames])
     built = codec.build_index(stack[:total], d_out_off.clone(), n, frames.size, dt)
     groups = L.trpx_group_count(n, 12)
     states = [torch.zeros(frames.size * groups, dtype=torch.int64, device=gpu) for _ in range(2)]
@@ -260,7 +255,7 @@ def test_index(gpu, dt):
     torch.cuda.synchronize()
     assert torch.equal(states[0], states[1])
     w = np.random.default_rng(22).integers(-5, 6, size=(2, n)).astype(np.int32)
-    dots, st = codec.decode_dot(stack[:total], d_out_off.clone(), n, frames.size, dt, _to_dev(w), index=d_index)
+    dots, st = codec.decode_dot(stack[:total], d_out_off.clone(), n, frames.size, dt, to_dev(w), index=d_index)
     torch.cuda.synchronize()
     assert int(st[0].item()) == OK
     assert np.array_equal(dots.cpu().numpy(), (px[frames].astype(np.int64)[:, None, :] * w.astype(np.int64)[None]).sum(-1))
@@ -322,7 +317,7 @@ def test_codec_select_frames_sizes_itself(small_u8, gpu):
 
 def test_terse_select_with_a_mask_and_round_trip(gpu):
     from trpx_amd import Terse
-    px = _random(np.uint16, (9, 35 * 20), 31)
+    px = mixed(np.uint16, (9, 35 * 20), 31, zero_stretch=True)
     t = Terse()
     t.dim([35, 20])
     t.push_back_stack(px)

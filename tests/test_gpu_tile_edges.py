@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 from alignment import carve_stream
-from test_gpu_decode_sum import _encode, _random, _to_np, truth
+from gpu_support import encode, mixed, to_np
+from gpu_support import sum_truth as truth
 
 pytestmark = pytest.mark.gpu
 
@@ -28,8 +29,8 @@ assert VALUES == 12 * 1024 + 5
 def stack(request):
     """(pixels, encoded stack, {case: the stream as that case's device tensor}), made once per pixel type."""
     import torch
-    px = _random(request.param, FRAMES, VALUES, seed=41)
-    enc = _encode(px)
+    px = mixed(request.param, (FRAMES, VALUES), seed=41)
+    enc = encode(px)
     s = enc.stack()
     total = s.numel()
     assert total == enc.total_bytes()
@@ -57,7 +58,7 @@ def test_decode_indexed_tiled(stack, case):
     finally:
         _lib.lib().trpx_set_decode_path(0)
     assert int(st[0].item()) == 0
-    assert np.array_equal(_to_np(back), px)
+    assert np.array_equal(to_np(back), px)
 
 
 @pytest.mark.parametrize("group", [1, FRAMES])
@@ -70,7 +71,7 @@ def test_decode_sum(stack, case, group):
                                 index=enc.index)
     torch.cuda.synchronize()
     assert int(st[0].item()) == 0
-    assert np.array_equal(_to_np(sums), truth(px, group, np.int64))
+    assert np.array_equal(to_np(sums), truth(px, group, np.int64))
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -84,4 +85,4 @@ def test_decode_roi_last_rows(stack, case):
                                index=enc.index)
     torch.cuda.synchronize()
     assert int(st[0].item()) == 0
-    assert np.array_equal(_to_np(out)[0], px[FRAMES - 1].reshape(HEIGHT, WIDTH)[HEIGHT - box_h:])
+    assert np.array_equal(to_np(out)[0], px[FRAMES - 1].reshape(HEIGHT, WIDTH)[HEIGHT - box_h:])

@@ -12,7 +12,6 @@ One stack, one kind and one form under a kernel trace shows the support / runs /
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -20,23 +19,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trpx_amd import _lib, codec, workloads  # noqa: E402
+from timing import median_ms  # noqa: E402
 
 SIDE = 512
 V = SIDE * SIDE
-
-
-def median_ms(fn, reps, warm=3):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
 
 
 def maps_of(kind, k):

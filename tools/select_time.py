@@ -20,23 +20,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trpx_amd import _lib, codec, workloads  # noqa: E402
+from timing import median_ms, times_ms  # noqa: E402
 
 SIDE = 512
 V = SIDE * SIDE
-
-
-def median_ms(fn, reps, warm=3):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts), min(ts), max(ts)
 
 
 def list_of(kind, n, rng):
@@ -88,7 +75,7 @@ def main():
                 # the copy ceiling: the same number of bytes through the streaming copy kernel
                 src = s[:cap] if s.numel() >= cap else torch.empty(cap, dtype=torch.uint8, device="cuda")
                 stream = torch.cuda.current_stream().cuda_stream
-                row["copy_ceiling_ms"], _, _ = median_ms(lambda: _lib.check(L.trpx_bench_stream(2, src.data_ptr(), out.data_ptr(), cap, stream)), args.reps)
+                row["copy_ceiling_ms"] = median_ms(lambda: _lib.check(L.trpx_bench_stream(2, src.data_ptr(), out.data_ptr(), cap, stream)), args.reps)
                 call()                                       # (the ceiling wrote into `out`)
                 # the replaced route: decode everything, pick the pixels, encode them
                 pix = torch.empty((n, V), dtype=torch.uint16, device="cuda")
@@ -104,12 +91,13 @@ def main():
                 replaced()
                 torch.cuda.synchronize()
                 assert torch.equal(offs2, out_offs) and torch.equal(out2[:total], out[:total]), (name, kind)
-                row["replaced_route_ms"], _, _ = median_ms(replaced, max(3, args.reps // 4), warm=1)
+                row["replaced_route_ms"] = median_ms(replaced, max(3, args.reps // 4), warm=1)
                 del pix, out2
-            row["select_ms"], row["select_min_ms"], row["select_max_ms"] = median_ms(call, args.reps)
+            ts = times_ms(call, args.reps)
+            row["select_ms"], row["select_min_ms"], row["select_max_ms"] = statistics.median(ts), min(ts), max(ts)
             row["select_GBps"] = round(2 * total / row["select_ms"] / 1e6, 1)   # bytes read + bytes written
             if args.with_index:
-                row["select_with_index_ms"], _, _ = median_ms(lambda: call(idx), args.reps)
+                row["select_with_index_ms"] = median_ms(lambda: call(idx), args.reps)
             if not args.no_baselines:
                 row["vs_copy_ceiling"] = round(row["select_ms"] / row["copy_ceiling_ms"], 2)
                 row["vs_replaced_route"] = round(row["replaced_route_ms"] / row["select_ms"], 1)

@@ -9,7 +9,6 @@ One case under a kernel trace shows the bounds / tile-bits / scan / validate / p
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -17,22 +16,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trpx_amd import _lib, codec, workloads  # noqa: E402
+from timing import median_ms  # noqa: E402
 
 N, V = 2000, 512 * 512
-
-
-def median_ms(fn, reps, warm=3):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
 
 
 def main():

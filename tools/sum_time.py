@@ -7,7 +7,6 @@ summing decode: stream + decode index (when given) + sums.
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -15,20 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trpx_amd import _lib, codec, workloads  # noqa: E402
-
-
-def median_ms(fn, reps, warm=3):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return statistics.median(ts)
+from timing import median_ms  # noqa: E402
 
 
 def stack(name):
