@@ -10,18 +10,34 @@ consumer's data.
     ways a call can be given a stack;
   * events_median: HIP-event timing (tools/timing.py holds the same loop for the scripts under tools/, which do not import
     from tests/);
-  * sum_truth / sparse_truth: the numpy truths more than one module compares with.
+  * sum_truth / sparse_truth: the numpy truths more than one module compares with;
+  * selected: a route or path setter (trpx_set_decode_path / _encode_path / _locate_path) for a block, auto behind it;
+  * index_layout / index_parts / assert_same_index: the two defined parts of a decode index;
+  * assert_round_trip: status 0 and the pixels back, byte for byte;
+  * host_encode / host_decode: trpx_encode_host / trpx_decode_host on numpy arrays, into poisoned buffers;
+  * fuzz_stack, ALL_DTYPES, ROUTES: the width patterns, pixel types and forced decode routes of the route tests;
+  * run_case / run_variant: a program of tests/variant_cases/ in a child python, on the product or on a test build of the library.
 
-No fixtures, no library at import; everything but encode() works on CPU tensors: tests/test_gpu_support_model.py runs it there
-and shows that each check can fail."""
+No fixtures, no library at import; everything but encode(), the host_ calls and the child programs works on CPU tensors:
+tests/test_gpu_support_model.py and tests/test_support_checks_model.py run it there and show that each check can fail."""
+import contextlib
+import ctypes as C
+import os
 import statistics
+import subprocess
+import sys
 
 import numpy as np
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 64                                                  # sentinel elements on either side of a guarded output
 OK, INVALID_ARG, CAPACITY, CORRUPT = 0, 1, 3, 5              # status word 0 (include/trpx_hip.h)
 
 DTYPE_NAMES = ("uint8", "int8", "uint16", "int16", "uint32", "int32", "uint64", "int64", "float32", "float64")
+ALL_DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]          # the pixel types of the tuned kernels
+# trpx_set_decode_path (0 = auto).  4: large frames by round 4's parts route instead of the index route; = auto for small frames;
+# 5: auto with the listed frames' index by the dense walk, decode_dense.hip
+ROUTES = {"basic": 1, "tiles": 2, "frames": 3, "parts": 4, "dense": 5}
 
 
 # ---- dtype mapping and transfer ------------------------------------------------------------------------------------------------
@@ -194,3 +210,145 @@ def sparse_truth(px: np.ndarray, t: int):
         m = px >= px.dtype.type(t)
     rows = np.concatenate([[0], np.cumsum(m.sum(axis=1))]).astype(np.int64)
     return rows, np.nonzero(m)[1].astype(np.uint32), px[m]
+
+
+# ---- routes and paths ----------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def selected(setter: str, value: int, lib=None):
+    """trpx_set_decode_path / _encode_path / _locate_path for the block, 0 (auto) behind it -- also when the block raises: a
+    route left set makes every later test of the process fail for the wrong reason.  lib: the library (a stub in the CPU tier)."""
+    if lib is None:
+        from trpx_amd import _lib
+        lib = _lib.lib()
+    fn = getattr(lib, setter)
+    rc = fn(value)
+    assert rc == 0, (setter, value, rc)
+    try:
+        yield
+    finally:
+        fn(0)
+
+
+# ---- the decode index ------------------------------------------------------------------------------------------------------------
+def index_layout(n_values, n_frames):
+    """(bytes of group offsets, byte at which the widths start, bytes of widths) of a decode index at block 12: one 8-byte
+    offset per group of 256 blocks, padding up to a multiple of 16, one byte per block."""
+    nb = (n_values + 11) // 12
+    ng = (nb + 255) // 256
+    return 8 * n_frames * ng, (8 * n_frames * ng + 15) // 16 * 16, n_frames * nb
+
+
+def index_parts(index, n_values, n_frames):
+    """(group-offset bytes, width bytes) of a decode index, tensor or array.  The index is defined only where a group / a block
+    exists: the padding between the two parts belongs to neither."""
+    g, w_off, w = index_layout(n_values, n_frames)
+    return index[:g], index[w_off: w_off + w]
+
+
+def _same(a, b):
+    """Byte equality of two tensors (compared where they are) or of a tensor / an array and an array (on the host)."""
+    if not isinstance(a, np.ndarray) and not isinstance(b, np.ndarray):
+        import torch
+        return torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
+    a, b = (x if isinstance(x, np.ndarray) else to_np(x) for x in (a, b))
+    return np.array_equal(np.ascontiguousarray(a).reshape(-1).view(np.uint8), np.ascontiguousarray(b).reshape(-1).view(np.uint8))
+
+
+def assert_same_index(a, b, n_values, n_frames, ctx):
+    """Two decode indices agree in their group offsets and in their widths."""
+    for what, pa, pb in zip(("group offsets", "widths"), index_parts(a, n_values, n_frames), index_parts(b, n_values, n_frames)):
+        assert _same(pa, pb), (ctx, what)
+
+
+# ---- round trip ------------------------------------------------------------------------------------------------------------------
+def assert_round_trip(back, status, px, ctx):
+    """What a decode returned: status word 0 is 0, `back` has the type and the number of elements of `px` and holds its bytes
+    (through uint8, so that the unsigned wide types need no special case; [frames, values] against [frames, h, w] is the same
+    stack).  Tensors or arrays; the caller has synchronised."""
+    assert int(status[0]) == 0, (ctx, "status", int(status[0]))
+    kind = [str(x.dtype).split(".")[-1] for x in (back, px)]                # torch.uint16 / dtype('uint16') -> uint16
+    assert kind[0] == kind[1] and int(np.prod(back.shape)) == int(np.prod(px.shape)), (ctx, "type or size differ", kind, back.shape, px.shape)
+    assert _same(back, px), (ctx, "pixels differ")
+
+
+# ---- child programs --------------------------------------------------------------------------------------------------------------
+VARIANT_CASES = os.path.join(ROOT, "tests", "variant_cases")
+VARIANTS = os.path.join(ROOT, "tools", "variants")
+
+
+def run_case(case, *args, **env):
+    """tests/variant_cases/`case` (or a path) in a fresh child python with `env` added to the environment: it must exit 0 and
+    print OK within 600 s."""
+    r = subprocess.run([sys.executable, os.path.join(VARIANT_CASES, case), *args], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, **env))
+    assert r.returncode == 0 and "OK" in r.stdout, (case, args, env, r.stdout[-2000:], r.stderr[-3000:])
+
+
+def run_variant(name, case, *args, variants=VARIANTS):
+    """The case on the test build tools/variants/libtrpx_`name`.so (TRPX_LIB); skips where that build is absent -- looked for
+    when its turn comes, so that a failure on one build is not turned into a skip by the absence of the next."""
+    import pytest
+    variant = os.path.join(variants, f"libtrpx_{name}.so")
+    if not os.path.exists(variant):
+        pytest.skip(f"test variant not built (make -C trpx_amd/csrc {name})")
+    run_case(case, *args, TRPX_LIB=variant)
+
+
+# ---- the host entry points and the fuzz generator ----------------------------------------------------------------------------------
+def host_encode(px2d, block=12):
+    """[frames, n] numpy -> (stream bytes, offsets, prolix_bits) through trpx_encode_host."""
+    from trpx_amd import _lib
+    from trpx_amd.terse import _code
+    L = _lib.lib()
+    px2d = np.ascontiguousarray(px2d)
+    f, n = px2d.shape
+    cap = f * L.trpx_worst_case_bytes(_code(px2d.dtype), n, block)
+    out = np.full(cap, 0xAA, np.uint8)     # poisoned: every output byte must be written
+    total, pb = C.c_size_t(0), C.c_uint(0)
+    offs = np.zeros(f + 1, np.uint64)
+    _lib.check(L.trpx_encode_host(_code(px2d.dtype), px2d.ctypes.data, n, f, block, out.ctypes.data, cap,
+                                  C.byref(total), offs.ctypes.data, C.byref(pb), -1))
+    return out[: total.value].copy(), offs, int(pb.value)
+
+
+def host_decode(stream, offs, n, frames, dtype, block=12, stream_signed=None):
+    from trpx_amd import _lib
+    from trpx_amd.terse import _code
+    L = _lib.lib()
+    out = np.full((frames, n), 0x55, np.dtype(dtype))
+    stream = np.ascontiguousarray(stream)
+    _lib.check(L.trpx_decode_host(int(np.dtype(dtype).kind == "i") if stream_signed is None else int(stream_signed),
+                                  _code(dtype, True), stream.ctypes.data, stream.size,
+                                  offs.ctypes.data if offs is not None else None, n, frames, block,
+                                  out.ctypes.data, -1))
+    return out
+
+
+def fuzz_stack(rng, dt, kind, n, frames):
+    """tools/fuzz_paths.py's generator: width patterns that exercise runs, outliers, flips and long runs (inside D3)."""
+    top = 8 * dt.itemsize - (2 if dt.kind == "i" else (1 if dt.itemsize == 4 else 0))
+    nblk = (n + 11) // 12
+    if kind == 0:
+        hi = np.full((frames, nblk), rng.randint(0, top + 1))                                          # one width
+    elif kind == 1:
+        hi = rng.randint(0, top + 1, size=(frames, nblk))                                              # every block its own width
+    elif kind == 2:
+        hi = np.where(rng.rand(frames, nblk) < 0.02, rng.randint(0, top + 1, size=(frames, nblk)), 3 if top >= 3 else 1)   # runs + outliers
+    elif kind == 3:
+        hi = np.where(rng.rand(frames, nblk) < 0.5, 2, 3 if top >= 3 else 1)                          # flips every other block
+    elif kind == 5:                                                                                    # payloads of one bits: a header position
+        hi = np.repeat(rng.randint(0, min(top, 12) + 1, size=(frames, (nblk + 39) // 40)), 40, axis=1)[:, :nblk]   # may read 0xFFFFFFFF
+        sat = np.repeat(hi, 12, axis=1)[:, :n]
+        mag = np.where(rng.rand(frames, n) < 0.97, (1 << sat) - 1, 0).astype(np.int64)
+        mag[:, n // 2: n // 2 + n // 5] = 0                                                             # and a run of empty blocks
+        if dt.kind == "i":
+            return np.where(mag > 0, -1, 0).astype(dt) * (rng.rand(frames, n) < 0.9) + (rng.randint(-40, 40, size=(frames, n)) * (rng.rand(frames, n) < 0.01)).astype(dt)
+        return mag.astype(dt)
+    else:
+        hi = np.repeat(rng.randint(0, top + 1, size=(frames, (nblk + 299) // 300)), 300, axis=1)[:, :nblk]   # long runs of changing widths
+    mag = (rng.rand(frames, nblk * 12) * (2.0 ** np.repeat(hi, 12, axis=1))).astype(np.int64)[:, :n]
+    if kind % 2 == 0:
+        mag[:, : n // 3] = 0                                                                          # empty stretches
+    if dt.kind == "i":
+        mag = mag * rng.choice([-1, 1], size=mag.shape)
+    return mag.astype(dt)

@@ -1,5 +1,5 @@
 """Valid TERSE streams that no encoder here writes -- the one seeded generator behind tests/test_noncanonical_model.py (CPU),
-tests/test_gpu_noncanonical.py (GPU) and tests/golden/make_noncanonical.py.
+tests/test_gpu_noncanonical.py (GPU, through tests/noncanonical_dev.py) and tests/golden/make_noncanonical.py.
 
 The project's encoder and the oracle's write CANONICAL streams: a block whose width equals the one before gets the single
 "same width" bit, and no width is larger than the block's values need.  The decoder grammar (Terse.hpp:360-372) accepts more:
@@ -16,7 +16,7 @@ The stream kinds:
       (placement, run width) pair frame 0 gets, so that stacks of few frames reach every pair.
   K5  all explicit: every block carries an explicit header; even frames hold width-0 blocks only ("0000" each, no payload), odd
       frames one constant width.
-Data stay inside the reference's validity domain (SURVEY.md D3), with the `top` of tests/test_gpu_parity.py::_fuzz_stack.
+Data stay inside the reference's validity domain (SURVEY.md D3), with the `top` of tests/gpu_support.py::fuzz_stack.
 Truth is always the pixels returned here, never anything a decoder produced."""
 import dataclasses
 import zlib
@@ -32,7 +32,7 @@ GROUP_BLOCKS = 256
 
 
 def top_of(dt) -> int:
-    """The widest block the data use: _fuzz_stack's for 8 .. 32 bits; 30 for the 64-bit containers, beyond which the reference's
+    """The widest block the data use: fuzz_stack's for 8 .. 32 bits; 30 for the 64-bit containers, beyond which the reference's
     own 64-bit code is broken (tests/test_oracle.py::differential_cases: Terse.hpp:554 calls the C abs(int))."""
     dt = np.dtype(dt)
     if dt.itemsize == 8:

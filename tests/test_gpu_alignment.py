@@ -46,19 +46,18 @@ position-parallel locator takes (4), so the form without offsets is Walk::kSeria
 The stream-base tests run the same calls with the stream at 4, 8, 12 and 68 mod 128 (mod 16: 4, 8, 12, 4) and an aligned
 output, so that (base & 15) != 0 takes the guarded dword fills of every window (decode_frame.hip, part_walk.hpp, walk_lds.hpp,
 unpack_tile.hpp) in place of the LDS-DMA / 16-byte ones."""
-import contextlib
 import functools
 
 import numpy as np
 import pytest
 
 from alignment import RESIDUES, STREAM_RESIDUES, align_up, carve, carve_copy, carve_stream, same_bytes, to_bytes
-from gpu_support import to_dev, torch_dt
+from gpu_support import ALL_DTYPES as DTYPES
+from gpu_support import selected, to_dev, torch_dt
 
 pytestmark = pytest.mark.gpu
 
 S = 12 * 1024 + 5
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 WIDE = [np.uint64, np.int64]
 SMALL = [(3, S), (3, 12 * 1024), (1, 3072 + 12), (2, 7), (2, 12)]
 ROWS = {S: 647, 12 * 1024: 128, 1030 * 1065: 1065, 4096: 64, 2048 * 2048: 2048}      # row length of a frame, for the boxes
@@ -160,18 +159,6 @@ def _stack(name, frames, n):
 
 def stack(dtype, frames, n) -> Stack:
     return _stack(np.dtype(dtype).name, frames, n)
-
-
-@contextlib.contextmanager
-def selected(setter: str, value: int):
-    """trpx_set_decode_path / _encode_path / _locate_path for the block, 0 (auto) behind it."""
-    from trpx_amd import _lib
-    fn = getattr(_lib.lib(), setter)
-    _lib.check(fn(value))
-    try:
-        yield
-    finally:
-        fn(0)
 
 
 def _ok(status, what):

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import convert_edges as ce
-from gpu_support import to_dev, torch_dt
+from gpu_support import selected, to_dev, torch_dt
+from gpu_support import ROUTES as FORCED_ROUTES
 
 pytestmark = pytest.mark.gpu
 
@@ -163,7 +164,7 @@ def test_terse_class_containers(gpu, oracle, src):
 # ---- c. narrowing through the tuned routes --------------------------------------------------------------------------------
 NARROW = [(np.uint16, np.uint8), (np.int16, np.int8), (np.uint32, np.uint16), (np.int32, np.int16), (np.uint32, np.uint8),
           (np.int32, np.int8)]
-ROUTES = {"auto": 0, "basic": 1, "tiles": 2, "frames": 3, "parts": 4, "dense": 5}
+ROUTES = {"auto": 0, **FORCED_ROUTES}
 GEOMETRIES = [("flips", 3000, 140), ("runs", 40000, 130), ("runs", 12 * 34000 + 3, 3), ("dense", 256 * 512, 6)]
 
 
@@ -253,51 +254,50 @@ def test_narrowing_through_the_tuned_routes(gpu, oracle, pair, route):
     bits = 8 * dst.itemsize
     info = np.iinfo(dst)
     cases = _narrow_cases(pair[0], pair[1])
-    assert L.trpx_set_decode_path(ROUTES[route]) == 0
     try:
-        saw_parts = False
-        for (kind, n, frames), (px, streams, want) in zip(GEOMETRIES, cases):
-            nblk = (n + 11) // 12
-            sizes = np.array([s.size for s in streams], np.uint64)
-            offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-            stream = np.concatenate(streams)
-            d_stream = _stream_dev(stream)
-            # fits: the tuned decoders take the stream of the wider type into the narrow container
-            for given in (offs, None):
-                code, got = _device_decode("trpx_decode", signed, dst, d_stream, stream.size, given, n, frames)
-                assert code == 0, ("fits", route, kind, n, given is not None, code)
-                assert _same(got, want), ("fits", route, kind, n, given is not None)
-            where, P = _placements(oracle, L, route, px, streams, codec.dtype_code(dst))
-            saw_parts = saw_parts or P > 1
-            for k, (f, b) in enumerate(where):
-                # one value of the block needs one bit more than the container has: it clamps to the container's end
-                v = 1 << (bits - 1) if signed else 1 << bits
-                if signed and k % 2:
-                    v = -v - 1
-                i = b * 12 + (k * 5) % (min(12, n - b * 12))
-                frame_px = px[f].copy()
-                frame_px[i] = v
-                w = oracle.widths(frame_px)
-                assert (w > bits).sum() == 1 and w[b] == bits + 1                 # exactly one block, one bit wider
-                wide = oracle.encode(frame_px)[0]
-                parts = streams[:f] + [wide] + streams[f + 1:]
-                stream_w = np.concatenate(parts)
-                offs_w = np.concatenate([[0], np.cumsum([s.size for s in parts])]).astype(np.uint64)
-                d_wide = _stream_dev(stream_w)
-                for given in (offs_w, None):
-                    code, _ = _device_decode("trpx_decode", signed, dst, d_wide, stream_w.size, given, n, frames, want_pixels=False)
-                    assert code == CORRUPT, ("one wide block", route, kind, n, (f, b), given is not None, code)
-                got = _host_decode(stream_w, offs_w, n, frames, dst, signed)
-                keep = want[f, i]
-                want[f, i] = info.max if v > 0 else info.min                     # truth of the one changed pixel
-                try:
-                    assert want[f, i] == ce.truth(np.array([v]), dst)[0]
-                    assert _same(got, want), ("one wide block", route, kind, n, (f, b), "host")
-                finally:
-                    want[f, i] = keep
-        assert saw_parts                                                          # the large-frame geometry is cut into parts
+        with selected("trpx_set_decode_path", ROUTES[route]):
+            saw_parts = False
+            for (kind, n, frames), (px, streams, want) in zip(GEOMETRIES, cases):
+                nblk = (n + 11) // 12
+                sizes = np.array([s.size for s in streams], np.uint64)
+                offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+                stream = np.concatenate(streams)
+                d_stream = _stream_dev(stream)
+                # fits: the tuned decoders take the stream of the wider type into the narrow container
+                for given in (offs, None):
+                    code, got = _device_decode("trpx_decode", signed, dst, d_stream, stream.size, given, n, frames)
+                    assert code == 0, ("fits", route, kind, n, given is not None, code)
+                    assert _same(got, want), ("fits", route, kind, n, given is not None)
+                where, P = _placements(oracle, L, route, px, streams, codec.dtype_code(dst))
+                saw_parts = saw_parts or P > 1
+                for k, (f, b) in enumerate(where):
+                    # one value of the block needs one bit more than the container has: it clamps to the container's end
+                    v = 1 << (bits - 1) if signed else 1 << bits
+                    if signed and k % 2:
+                        v = -v - 1
+                    i = b * 12 + (k * 5) % (min(12, n - b * 12))
+                    frame_px = px[f].copy()
+                    frame_px[i] = v
+                    w = oracle.widths(frame_px)
+                    assert (w > bits).sum() == 1 and w[b] == bits + 1                 # exactly one block, one bit wider
+                    wide = oracle.encode(frame_px)[0]
+                    parts = streams[:f] + [wide] + streams[f + 1:]
+                    stream_w = np.concatenate(parts)
+                    offs_w = np.concatenate([[0], np.cumsum([s.size for s in parts])]).astype(np.uint64)
+                    d_wide = _stream_dev(stream_w)
+                    for given in (offs_w, None):
+                        code, _ = _device_decode("trpx_decode", signed, dst, d_wide, stream_w.size, given, n, frames, want_pixels=False)
+                        assert code == CORRUPT, ("one wide block", route, kind, n, (f, b), given is not None, code)
+                    got = _host_decode(stream_w, offs_w, n, frames, dst, signed)
+                    keep = want[f, i]
+                    want[f, i] = info.max if v > 0 else info.min                     # truth of the one changed pixel
+                    try:
+                        assert want[f, i] == ce.truth(np.array([v]), dst)[0]
+                        assert _same(got, want), ("one wide block", route, kind, n, (f, b), "host")
+                    finally:
+                        want[f, i] = keep
+            assert saw_parts                                                          # the large-frame geometry is cut into parts
     finally:
-        L.trpx_set_decode_path(0)
         L.trpx_host_release()
 
 

@@ -10,12 +10,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import ALL_DTYPES as DTYPES
 from gpu_support import CORRUPT, OK, Guarded, encode, input_forms, ladder, ladder_holds_every_width, mixed, status_block, torch_dt
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 SENTINEL = 0x5A5A5A5A5A5A5A5A
 I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
 WIDTH = 37                                                  # the row length the 2-D maps use: no multiple or divisor of 12

@@ -7,12 +7,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import ALL_DTYPES as DTYPES
 from gpu_support import Guarded, encode, events_median, input_forms, mixed, to_np, torch_dt
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 
 
 def truth(px, boxes, bh, bw):

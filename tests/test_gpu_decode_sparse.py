@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import ALL_DTYPES as DTYPES
 from gpu_support import CAPACITY, CORRUPT, OK, Guarded, encode, events_median, input_forms, ladder, ladder_holds_every_width, mixed
 from gpu_support import sparse_truth as truth
 from gpu_support import status_block, to_np
@@ -15,7 +16,6 @@ from gpu_support import status_block, to_np
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 ROW_SENTINEL, POS_SENTINEL, VAL_SENTINEL = 0x5A5A5A5A5A5A5A5A, 0x5A5A5A5A, 0x5A
 
 

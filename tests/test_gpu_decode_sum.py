@@ -6,6 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import ALL_DTYPES as DTYPES
 from gpu_support import encode, events_median, input_forms, mixed, to_np, torch_dt
 from gpu_support import sum_truth as truth
 from tiff_layout import parse_tiff
@@ -13,7 +14,6 @@ from tiff_layout import parse_tiff
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 OUTS = [np.int32, np.uint32, np.int64, np.uint64, np.float32, np.float64]
 
 

@@ -8,12 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import ALL_DTYPES as DTYPES
 from gpu_support import CAPACITY, INVALID_ARG, OK, Guarded, events_median, ladder, mixed, status_block, to_dev, torch_dt
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 OUT_SENTINEL, OFF_SENTINEL = 0xA5, 0x5A5A5A5A5A5A5A5A
 TILE = 3072
 IDS = dict(ids=lambda d: np.dtype(d).name)

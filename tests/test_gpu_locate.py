@@ -8,11 +8,10 @@ import io
 import numpy as np
 import pytest
 
+from gpu_support import ALL_DTYPES as DTYPES
 from gpu_support import encode
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 
 
 def _locate(stack, n, frames, dtype):

@@ -6,11 +6,10 @@ the two 2000-frame stacks, 5.9 s for the decode without offsets)."""
 import numpy as np
 import pytest
 
-from gpu_support import encode
+from gpu_support import ALL_DTYPES as DTYPES
+from gpu_support import encode, selected
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32]
 
 
 def _lib():
@@ -25,15 +24,11 @@ def _locate(stack, n, frames, dtype, serial=False, first_bad=None):
     from trpx_amd import codec
     if isinstance(stack, np.ndarray):
         stack = torch.from_numpy(np.ascontiguousarray(stack, dtype=np.uint8)).to("cuda:0")
-    L = _lib()
-    assert L.trpx_set_locate_path(1 if serial else 0) == 0
     ws = codec.Workspace(stack.device)
-    try:
+    with selected("trpx_set_locate_path", 1 if serial else 0):
         ws.get(256)[:4].fill_(0xEE)
         offs, st = codec.locate_frames(stack, n, frames, dtype, workspace=ws)
         torch.cuda.synchronize()
-    finally:
-        L.trpx_set_locate_path(0)
     if first_bad is not None:
         first_bad.append(int(ws.get(256)[:4].view(torch.int32).item()))
     return offs.cpu().numpy(), int(st[0].item())

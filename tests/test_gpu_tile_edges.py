@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from alignment import carve_stream
-from gpu_support import encode, mixed, to_np
+from gpu_support import encode, mixed, selected, to_np
 from gpu_support import sum_truth as truth
 
 pytestmark = pytest.mark.gpu
@@ -48,15 +48,12 @@ CASES = ["base4", "base8", "base12", "exact_end"]
 
 @pytest.mark.parametrize("case", CASES)
 def test_decode_indexed_tiled(stack, case):
-    from trpx_amd import _lib, codec
+    from trpx_amd import codec
     import torch
     px, enc, streams = stack
-    assert _lib.lib().trpx_set_decode_path(ROUTE_TILED) == 0
-    try:
+    with selected("trpx_set_decode_path", ROUTE_TILED):
         back, st = codec.decode(streams[case], enc.frame_offsets, VALUES, FRAMES, px.dtype, index=enc.index)
         torch.cuda.synchronize()
-    finally:
-        _lib.lib().trpx_set_decode_path(0)
     assert int(st[0].item()) == 0
     assert np.array_equal(to_np(back), px)
 

@@ -452,7 +452,7 @@ __global__ __launch_bounds__(kWave) void k_chain_walk(const uint8_t* __restrict_
     s.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.w);
     uint64_t* const sw = reinterpret_cast<uint64_t*>(states);
 #ifdef TRPX_CHAIN_FORCE_TIMEOUT
-    // test build (make chain_timeout, tests/test_gpu_parity.py): frame 0's part 3 never publishes its start state, frame 1's part 5
+    // test build (make chain_timeout, tests/test_gpu_large_frames.py): frame 0's part 3 never publishes its start state, frame 1's part 5
     // never its record -- the wavefronts that wait for them give up after kChainWaitTicks, the frames take the other route
     const bool mute_start = frame == 0u && p == 3u, mute_record = frame == 1u && p == 5u;
 #else
