@@ -301,6 +301,29 @@ public:
         return out;
     }
 
+    /// Per frame the sums of its pixels over the bins of a label map, in one device call, without expanding the frames
+    /// (trpx_decode_bins_host): labels = size() values, one per pixel; out[f * n_bins + b] = the sum of px[f][p] over the pixels
+    /// with labels[p] == b, in int64, exact.  A label >= n_bins belongs to no bin (mask with 0xFFFF).  The radial profile of
+    /// every frame.  1 <= n_bins <= 4096.
+    void prolix_bins(std::uint16_t const* labels, std::size_t n_bins, std::int64_t* out) {
+        if (n_bins == 0 || n_bins > 4096) throw std::invalid_argument("prolix_bins: 1 to 4096 bins");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_bins: values of more than 32 bits are not supported");
+        if (d_frame_sizes.empty()) return;
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_bins_host(bits + (d_signed ? 1 : 0), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                            d_frame_sizes.size(), d_block, labels, (unsigned)n_bins, out, -1), "Terse::prolix_bins");
+    }
+    std::vector<std::int64_t> prolix_bins(std::vector<std::uint16_t> const& labels, std::size_t n_bins) {
+        if (labels.size() != d_size) throw std::invalid_argument("prolix_bins: labels must hold size() values");
+        if (n_bins == 0 || n_bins > 4096) throw std::invalid_argument("prolix_bins: 1 to 4096 bins");
+        std::vector<std::int64_t> out(d_frame_sizes.size() * n_bins);
+        prolix_bins(labels.data(), n_bins, out.data());
+        return out;
+    }
+
     /// A new object holding the frames `frames` of this one -- any order, repeats allowed, possibly more than the stack has --
     /// in one device call, without decoding them (trpx_select_frames_host): the frames' bytes are copied, so the result is
     /// what push_back of those frames' pixels makes.  dim(), signedness and block are copied; bits_per_val() is kept from the

@@ -53,7 +53,8 @@ typedef enum trpx_status {
  * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
  *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
- *     trpx_decode_sparse and trpx_decode_dot where they build the index themselves (no index given) -- and their _host forms;
+ *     trpx_decode_sparse, trpx_decode_dot and trpx_decode_bins where they build the index themselves (no index given) -- and
+ *     their _host forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -424,6 +425,63 @@ int trpx_decode_dot(int dtype, const uint8_t* terse, size_t terse_bytes, const u
 int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                          size_t n_values, size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps,
                          int64_t* dots_out, int device);
+
+/*
+ * Per-frame sums over labelled pixel bins: bins_out[f][b] = sum over the pixels p of frame f with labels[p] == b of px[f][p],
+ * straight from the stream and its decode index, without expanding the frames -- the radial profile (azimuthal integration) of
+ * every frame, ring detectors, any partition of the detector into up to 4096 regions.  One label per pixel whatever the number
+ * of bins: the stream is walked once.  A width-0 block adds nothing and has no payload; the payload of a block none of whose
+ * labels is a bin is never read.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_dot: index given -- validated against the frame sizes as in
+ *                  trpx_decode_indexed; offsets only -- the index is built in the workspace by trpx_build_index's walk; offsets
+ *                  NULL -- the frames are located in the workspace first.  workspace: DEVICE, 8-byte aligned, ALWAYS needed (one
+ *                  support bit per block of a frame lives there): trpx_decode_bins_workspace_bytes() is the need with offsets
+ *                  and index both NULL; with offsets or index given less is used, and the call checks against what its own form
+ *                  needs.  The size is arithmetic: beyond what the index needs (trpx_decode_roi_workspace_bytes()), the support
+ *                  words, 4 * ceil(ceil(n_values / 12) / 32) bytes rounded up to 8, and, where spans =
+ *                  trpx_decode_bins_spans_per_frame(n_values, n_frames) is more than 1, 8 * n_bins * n_frames * spans bytes of
+ *                  partial sums -- nothing otherwise
+ *   labels         DEVICE const uint16_t[n_values], 2-byte aligned; 8-byte aligned is the fast case (a block's 12 labels are
+ *                  three 8-byte loads).  A label >= n_bins belongs to NO bin: this is how a beam stop, dead pixels and detector
+ *                  gaps are masked (0xFFFF); it is legal, not an error.  A device array on purpose: a captured graph is replayed
+ *                  with a new map in the same buffer, and nothing derived from its contents is decided on the host.
+ *                  1 <= n_bins <= 4096
+ *   bins_out       DEVICE int64_t[n_frames][n_bins], 8-byte aligned.  EVERY element is written by every successful call (a bin
+ *                  without pixels is 0): the caller clears nothing.  The sums are exact: a frame has fewer than 2^29 values of
+ *                  magnitude at most 2^32, so no sum leaves int64.  Integer arithmetic throughout: bit-identical across runs,
+ *                  input forms and launch shapes
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT in exactly the cases of trpx_decode_dot: a
+ *                  256-block group does not end where the next group's offset (the last group: the frame's size) says, a block is
+ *                  wider than dtype allows, a frame lies outside the stream or the index does not fit the offsets, with index ==
+ *                  NULL also for a valid stream with restated widths (trpx_build_index's verdict).  EVERY group of EVERY frame is
+ *                  walked and validated, also where every label of it is masked or every block has width 0.  The outputs are
+ *                  then unspecified
+ * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)) and labels[0 .. n_values) is read
+ * (the labels behind n_values are never read for a frame's partial last block), nothing outside bins_out, status and the
+ * workspace is written, whatever the status.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits;
+ * TRPX_ERR_INVALID_ARG for an unknown or float dtype, zero sizes, n_bins 0 or above 4096, null or misaligned pointers, an index
+ * without offsets, a NULL workspace; TRPX_ERR_CAPACITY for a workspace that is too small for the call's own form.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the
+ * host from n_frames, n_values and n_bins alone, never from the data or the map.
+ * trpx_decode_bins_spans_per_frame: the workgroups a frame is cut into, min(ceil(runs / 4), max(1, ceil(1536 / n_frames))) with
+ * runs = ceil(groups / 8) -- pure arithmetic, for tests and diagnostics (0 for sizes no call takes); above 1 the partial sums of
+ * the spans pass through the workspace.
+ * trpx_decode_bins_host: host terse / frame_offsets (or NULL) / labels / bins_out; checks its arguments before a device is looked
+ * for, stages, calls trpx_decode_bins and synchronises.
+ */
+size_t trpx_decode_bins_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                        unsigned n_bins);
+unsigned trpx_decode_bins_spans_per_frame(size_t n_values, size_t n_frames);
+int trpx_decode_bins(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                     size_t n_values, size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins,
+                     int64_t* bins_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                          size_t n_values, size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins,
+                          int64_t* bins_out, int device);
 
 /*
  * Encode from events: the stream of a stack given in CSR form -- what trpx_decode_sparse writes, what a counting detector or a

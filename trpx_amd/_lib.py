@@ -67,6 +67,10 @@ SYMBOLS = {
     "trpx_decode_dot_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _U]),
     "trpx_decode_dot": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _P, _U, _P, _P, _P, _SZ, _P]),
     "trpx_decode_dot_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _P, _U, _P, _I]),
+    "trpx_decode_bins_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _U]),
+    "trpx_decode_bins_spans_per_frame": (_U, [_SZ, _SZ]),
+    "trpx_decode_bins": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _P, _U, _P, _P, _P, _SZ, _P]),
+    "trpx_decode_bins_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _P, _U, _P, _I]),
     "trpx_encode_sparse_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _U]),
     "trpx_encode_sparse_bound_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
     "trpx_encode_sparse": (_I, [_I, _P, _P, _P, _SZ, _SZ, _SZ, _U, _P, _SZ, _P, _P, _P, _SZ, _P]),

@@ -444,6 +444,44 @@ def decode_dot(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
     return out, status
 
 
+def decode_bins_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, n_bins: int, block: int = BLOCK) -> int:
+    return lib().trpx_decode_bins_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block, n_bins)
+
+
+def decode_bins(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, labels: torch.Tensor,
+                n_bins: int, index: torch.Tensor | None = None, out: torch.Tensor | None = None, workspace: Workspace | None = None,
+                status: torch.Tensor | None = None, block: int = BLOCK):
+    """Per frame the sums of its pixels over the bins of a label map (trpx_decode_bins), for a stack resident on the GPU,
+    without decoding its frames to memory: the radial profile (azimuthal integration) of every frame, ring detectors.
+
+    ``dtype`` is the stream's pixel type; ``labels`` a contiguous uint16 (or int16, read as uint16) tensor ``[n_values]`` (or
+    ``[H, W]`` with ``H * W == n_values``) on the stack's device; 1 <= n_bins <= 4096.  A label >= n_bins belongs to no bin
+    (mask with 0xFFFF).  Returns (bins int64 [n_frames, n_bins], status): ``bins[f, b] = sum of px[f][p] over labels[p] == b``,
+    exact, every element written; asynchronous on the current stream, like ``decode``.  status[0] is 5 for a corrupt stream or
+    index -- the whole stack is validated, whatever the map.  ``frame_offsets = None``: the frames are located first; ``index =
+    None``: the decode index is built on the way (both in ``workspace``)."""
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    if labels.dtype not in (torch.uint16, torch.int16):
+        raise TypeError("decode_bins: labels must be a uint16 (or int16-viewed) tensor")
+    if labels.dim() < 1 or not labels.is_contiguous() or labels.numel() != n_values:
+        raise ValueError(f"decode_bins: labels must be a contiguous tensor of {n_values} elements ([n_values] or [H, W])")
+    if labels.device != dev:
+        raise ValueError("decode_bins: labels must live on the stack's device")
+    if not 1 <= n_bins <= 4096:
+        raise ValueError("decode_bins: 1 to 4096 bins")
+    if out is None:
+        out = torch.empty((n_frames, n_bins), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.numel() != n_frames * n_bins or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_bins: out must be a contiguous int64 tensor of {n_frames} x {n_bins} elements on {dev}")
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_bins_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_bins))
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_bins(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                     n_values, n_frames, block, labels.data_ptr(), n_bins, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+    return out, status
+
+
 def select_frames_workspace_bytes(n_frames: int, n_select: int) -> int:
     return lib().trpx_select_frames_workspace_bytes(n_frames, n_select)
 

@@ -17,6 +17,7 @@
 #include "decode_roi.hpp"
 #include "decode_sparse.hpp"
 #include "decode_dot.hpp"
+#include "decode_bins.hpp"
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -656,7 +657,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 }
 
 }  // extern "C"
-// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot -------------------
+// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins -------------------
 // Each reads: its own checks, the shared checks (stack_limits, consumer_ws), the front (consumer_front), its own few fields, launch.
 namespace {
 // The consumers take three input forms: index given; offsets only -- the index is built by trpx_build_index's walk; neither --
@@ -793,6 +794,19 @@ DotWs dot_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_maps) {
     return w;
 }
 bool dot_maps_ok(unsigned n_maps) { return n_maps >= 1 && n_maps <= trpx::kDotMaxMaps; }
+
+// ---- sums over labelled bins (decode_bins.hip): its scratch is [support: one bit per block of a frame] and, with more than one
+// span per frame, per (frame, span, bin) [partial sum i64] ---------------------------------------------------------------------------
+struct BinsWs { size_t support, partials, total; };
+BinsWs bins_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_bins) {
+    BinsWs w;
+    const size_t spans = trpx::bins_spans_per_frame(g, n_frames);
+    w.support = 0;
+    w.partials = trpx::align_up(w.support + 4 * trpx::bins_support_words(g), 8);
+    w.total = w.partials + (spans > 1 ? 8 * (size_t)n_bins * n_frames * spans : 0);
+    return w;
+}
+bool bins_count_ok(unsigned n_bins) { return n_bins >= 1 && n_bins <= trpx::kBinsMax; }
 }  // namespace
 
 extern "C" {
@@ -965,6 +979,48 @@ int trpx_decode_dot(int dtype, const uint8_t* terse, size_t terse_bytes, const u
     a.dots_out = dots_out;
     a.status = status;
     HIP_TRY(trpx::launch_decode_dot(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+size_t trpx_decode_bins_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, unsigned n_bins) {
+    trpx::FrameGeom g;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && bins_count_ok(n_bins) ? front + bins_ws(g, n_frames, n_bins).total : 0;
+}
+
+unsigned trpx_decode_bins_spans_per_frame(size_t n_values, size_t n_frames) {
+    trpx::FrameGeom g;
+    return geom_of(n_values, kBlock, &g) && sizes_ok(g, n_frames) ? trpx::bins_spans_per_frame(g, n_frames) : 0;
+}
+
+int trpx_decode_bins(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                     size_t n_values, size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins, int64_t* bins_out,
+                     uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_bins", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {labels, 2}, {bins_out, 8}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
+                                   {workspace, 8, false}}, &g))
+        return rc;
+    const Consumer c{"trpx_decode_bins", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
+    if (!bins_count_ok(n_bins)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_bins: n_bins=%u (1..%u)", n_bins, trpx::kBinsMax);
+    const BinsWs own = bins_ws(g, n_frames, n_bins);
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, own.total, "the support bits live there", &w)) return rc;
+    if (const int rc = consumer_front(c, w, true, &f)) return rc;
+    trpx::BinsArgs a{};
+    static_cast<trpx::IndexedStack&>(a) = f.stack;
+    a.labels = labels;
+    a.n_bins = n_bins;
+    a.spans = trpx::bins_spans_per_frame(g, n_frames);
+    a.support = reinterpret_cast<uint32_t*>(f.own + own.support);
+    a.partials = reinterpret_cast<int64_t*>(f.own + own.partials);
+    a.bins_out = bins_out;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_bins(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -1464,6 +1520,33 @@ int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, co
                          reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
     if (rc || (rc = finish("trpx_decode_dot_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, dots_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                          size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins, int64_t* bins_out, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (const int rc = consumer_host_refusals("trpx_decode_bins_host", terse && labels && bins_out && bins_count_ok(n_bins), dtype, terse_bytes, n_values,
+                                              n_frames, block, &g))
+        return rc;
+    const size_t ws_bytes = trpx_decode_bins_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_bins);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_bins_host: bad dtype/sizes");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_bins_host: frames of >= 2^32 bits");
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_bins_host", device, &hs)) return rc;
+    // the map and the sums in one device block: [labels] [bins]
+    const size_t l_bytes = 2 * n_values, out_at = trpx::align_up(l_bytes, 16), out_bytes = 8 * n_frames * (size_t)n_bins;
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_at + out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    char* o = static_cast<char*>(d.out);
+    HIP_TRY(copy_sync(hs, o, labels, l_bytes, hipMemcpyHostToDevice));
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_bins(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const uint16_t*>(o), n_bins,
+                          reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_bins_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, bins_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

@@ -23,16 +23,6 @@ namespace trpx {
 
 namespace {
 
-// the support words of group grp's rows: the lane's block's bit is bit lane % 32 of s[r]
-__device__ __forceinline__ void dot_load_support(uint32_t (&s)[kGroupRows], const uint32_t* __restrict__ support, uint32_t n_words,
-                                                 uint32_t grp, uint32_t lane) {
-#pragma unroll
-    for (int r = 0; r < kGroupRows; ++r) {
-        const uint32_t word = grp * (kTileBlocks / 32) + r * (kWave / 32) + (lane >> 5);
-        s[r] = word < n_words ? support[word] : 0u;
-    }
-}
-
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {  // every lane gets the sum of the 64 lanes' values (mod 2^64)
 #pragma unroll
     for (int m = 1; m < kWave; m <<= 1) {
@@ -100,7 +90,7 @@ __device__ __forceinline__ void dot_run(const DotArgs& a, uint64_t run, uint32_t
     run_load(R, a, lane);
     uint32_t wn[kGroupRows], nbn[kGroupRows], wp0n[kGroupRows], sn[kGroupRows];
     group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0, lane);
-    dot_load_support(sn, a.support, n_words, R.g0, lane);
+    group_load_support(sn, a.support, n_words, R.g0, lane);
     uint64_t acc[KM];
 #pragma unroll
     for (int k = 0; k < KM; ++k) acc[k] = 0ull;
@@ -112,7 +102,7 @@ __device__ __forceinline__ void dot_run(const DotArgs& a, uint64_t run, uint32_t
         for (int r = 0; r < kGroupRows; ++r) { w[r] = wn[r]; nb[r] = nbn[r]; wp0[r] = wp0n[r]; sup[r] = sn[r]; }
         if (j + 1 < R.n) {                                  // in flight during this group
             group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + j + 1, lane);
-            dot_load_support(sn, a.support, n_words, R.g0 + j + 1, lane);
+            group_load_support(sn, a.support, n_words, R.g0 + j + 1, lane);
         }
         const uint64_t t_off = lane_value64(R.my_off, j), t_next = lane_value64(R.my_off, j + 1);
         if (!group_offsets<T>(off, w, nb, wp0, R.fo, R.fe, t_off, t_next, R.g0 + j + 1 == g.n_tiles, a.terse_bytes, lane)) {

@@ -1,5 +1,5 @@
 // A RUN of consecutive 256-block groups of one frame on one wavefront, as the kernels that walk a whole stack through its decode
-// index see it (decode_sparse.hip: trpx_decode_sparse, decode_dot.hip: trpx_decode_dot): what belongs to the run is loaded once
+// index see it (decode_sparse.hip: trpx_decode_sparse, decode_dot.hip: trpx_decode_dot, decode_bins.hip: trpx_decode_bins): what belongs to the run is loaded once
 // (the frame's bytes, the groups' offsets: one per lane), and the blocks a group chooses are compacted into consecutive lanes
 // through a per-wavefront list in LDS, 64 at a time.  The group itself: group_front.hpp.
 #pragma once
@@ -27,6 +27,17 @@ __device__ __forceinline__ void list_sync() {               // the wavefront's L
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The support words of group grp's rows (one bit per block of a frame: trpx_decode_dot's and trpx_decode_bins' "some map / some
+// label wants this block"): the lane's block's bit is bit lane % 32 of s[r]
+__device__ __forceinline__ void group_load_support(uint32_t (&s)[kGroupRows], const uint32_t* __restrict__ support, uint32_t n_words,
+                                                   uint32_t grp, uint32_t lane) {
+#pragma unroll
+    for (int r = 0; r < kGroupRows; ++r) {
+        const uint32_t word = grp * (kTileBlocks / 32) + r * (kWave / 32) + (lane >> 5);
+        s[r] = word < n_words ? support[word] : 0u;
+    }
 }
 
 // what a wavefront holds for its run: lane j the offset of group g0 + j (lane n: the group behind the run)

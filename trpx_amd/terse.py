@@ -342,6 +342,28 @@ class Terse:
                                              w.ctypes.data, w.shape[0], out.ctypes.data, self._device))
         return out
 
+    def prolix_bins(self, labels, n_bins: int) -> np.ndarray:
+        """Per frame the sums of its pixels over the bins of a label map in ONE GPU call (trpx_decode_bins_host), without
+        decoding the frames to memory.  ``labels``: integers ``[size]`` (or ``[H, W]`` with ``H * W == size``) that fit uint16;
+        a label >= n_bins belongs to no bin (mask with 0xFFFF); 1 <= n_bins <= 4096.  Returns int64 ``[number_of_frames,
+        n_bins]``: ``[f, b] = sum of px[f][p] over labels[p] == b``, exact -- the radial profile of every frame."""
+        lab = np.asarray(labels)
+        if lab.dtype.kind not in "iu" or (lab.size and (lab.min() < 0 or lab.max() > 0xFFFF)):
+            raise TypeError("prolix_bins: labels must be integers that fit uint16")
+        if lab.size != self._size:
+            raise ValueError("prolix_bins: labels must be [size] or [H, W]")
+        if not 1 <= int(n_bins) <= 4096:
+            raise ValueError("prolix_bins: 1 to 4096 bins")
+        lab = np.ascontiguousarray(lab.reshape(self._size), dtype=np.uint16)
+        code, _ = self._stream_type("prolix_bins")
+        f = self.number_of_frames()
+        out = np.zeros((f, int(n_bins)), np.int64)
+        if f:
+            buf, offs = self._stream_and_offsets()
+            check(lib().trpx_decode_bins_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f, self._block,
+                                              lab.ctypes.data, int(n_bins), out.ctypes.data, self._device))
+        return out
+
     def select(self, frames) -> "Terse":
         """A new object holding the frames ``frames`` of this one, in ONE GPU call (trpx_select_frames_host), without decoding
         them: the frames' bytes are copied, so the result is what ``push_back_stack(pixels[frames])`` would make.  ``frames``: a
