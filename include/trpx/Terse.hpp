@@ -212,6 +212,40 @@ public:
                                            (unsigned)group, out, -1), "Terse::prolix_sum");
     }
 
+    /// Every frame summed over bins of bin_y x bin_x neighbouring pixels into `out` (number_of_frames() x ceil(height / bin_y) x
+    /// ceil(width / bin_x) values, frame by frame, row by row) in one device call, without expanding the frames
+    /// (trpx_decode_binned_host).  dim() = {width, height} must be set; a bin side is 1 .. 64 and no larger than the frame's; the
+    /// edge bins sum the pixels that exist.  V: int32 / uint32 (clamped), int64 / uint64 (exact), float / double (the exact sum
+    /// rounded once).
+    template <typename V>
+    void prolix_binned(V* out, std::size_t bin_y, std::size_t bin_x) {
+        static_assert(std::is_same_v<V, std::int32_t> || std::is_same_v<V, std::uint32_t> || std::is_same_v<V, std::int64_t> ||
+                          std::is_same_v<V, std::uint64_t> || std::is_same_v<V, float> || std::is_same_v<V, double>,
+                      "prolix_binned: int32, uint32, int64, uint64, float or double sums");
+        if (d_signed && std::is_unsigned_v<V>)
+            throw std::invalid_argument("signed data cannot be decompressed into unsigned data");
+        if (d_dim.size() != 2 || d_dim[0] * d_dim[1] != d_size) throw std::invalid_argument("prolix_binned: dim() must be {width, height} of the frames");
+        const std::size_t width = d_dim[0], height = d_dim[1];
+        if (bin_y == 0 || bin_x == 0 || bin_y > 64 || bin_x > 64 || bin_y > height || bin_x > width)
+            throw std::invalid_argument("prolix_binned: a bin side is 1 to 64 and no larger than the frame's");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_binned: values of more than 32 bits are not supported");
+        if (d_frame_sizes.empty()) return;
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_binned_host(bits + (d_signed ? 1 : 0), detail::out_dtype_of<V>(), d_terse_data.data(),
+                                              d_terse_data.size(), offs.data(), d_size, d_frame_sizes.size(), d_block, width,
+                                              (unsigned)bin_y, (unsigned)bin_x, out, -1), "Terse::prolix_binned");
+    }
+    template <typename V = std::int32_t>
+    std::vector<V> prolix_binned(std::size_t bin_y, std::size_t bin_x) {
+        if (d_dim.size() != 2 || bin_y == 0 || bin_x == 0) throw std::invalid_argument("prolix_binned: dim() must be set, a bin side is at least 1");
+        std::vector<V> out(d_frame_sizes.size() * ((d_dim[1] + bin_y - 1) / bin_y) * ((d_dim[0] + bin_x - 1) / bin_x));
+        prolix_binned(out.data(), bin_y, bin_x);
+        return out;
+    }
+
     /// The rectangle [y0, y0 + h) x [x0, x0 + w) of frames [first_frame, first_frame + n_frames) to `out` (n_frames x h x w
     /// values, frame by frame, row by row) in one device call, without expanding whole frames (trpx_decode_roi_host).
     /// dim() = {width, height} must be set.  The value type of `out` is the narrowest integer type that holds the object's

@@ -53,8 +53,8 @@ typedef enum trpx_status {
  * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
  *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
- *     trpx_decode_sparse, trpx_decode_dot and trpx_decode_bins where they build the index themselves (no index given) -- and
- *     their _host forms;
+ *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins and trpx_decode_binned where they build the index themselves (no
+ *     index given) -- and their _host forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -482,6 +482,62 @@ int trpx_decode_bins(int dtype, const uint8_t* terse, size_t terse_bytes, const 
 int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                           size_t n_values, size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins,
                           int64_t* bins_out, int device);
+
+/*
+ * Binned decode: every frame summed over bins of bin_y x bin_x neighbouring pixels, straight from the stream and its decode
+ * index, without expanding the frames -- previews, binned diffraction patterns for indexing, down-sampled movies.  A frame is
+ * height = n_values / width rows of `width` pixels (as trpx_decode_roi); out_h = ceil(height / bin_y), out_w = ceil(width / bin_x),
+ *     binned_out[f][Y][X] = sum of px[f][y][x] over Y * bin_y <= y < min((Y + 1) * bin_y, height),
+ *                                                   X * bin_x <= x < min((X + 1) * bin_x, width):
+ * the edge bins of a frame whose sides are no multiples of the bin sum the pixels that exist (a 1030 x 1065 frame bins by 2).
+ * A width-0 block adds nothing and has no payload: it is never fetched.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32
+ *   out_dtype      TRPX_I32, TRPX_U32, TRPX_I64, TRPX_U64, TRPX_F32 or TRPX_F64, converted exactly as trpx_decode_sum does: the sum
+ *                  is exact in integers and converted once -- 32-bit integers clamp, 64-bit integers keep the value, floats round
+ *                  once to nearest even.  A signed stream into U32 / U64 is TRPX_ERR_UNSUPPORTED
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_roi: index given -- validated against the frame sizes as in
+ *                  trpx_decode_indexed, the kernel alone, no workspace (NULL allowed); offsets only -- the index is built in the
+ *                  workspace by trpx_build_index's walk; offsets NULL -- the frames are located in the workspace first.  The call
+ *                  has no scratch of its own: trpx_decode_binned_workspace_bytes() = trpx_decode_roi_workspace_bytes(), the need
+ *                  with offsets and index both NULL; the call checks against what its own form needs
+ *   width          pixels per row; n_values % width == 0
+ *   bin_y, bin_x   1 <= bin_y <= min(height, 64), 1 <= bin_x <= min(width, 64).  (1, 1) is legal: a widening decode.  The cap
+ *                  bounds a band of one output row to 64 rows of pixels, and lets the pixel types of up to 16 bits accumulate in
+ *                  32 bits (64 * 64 * 65535 < 2^32).  out_w > 8192 is TRPX_ERR_UNSUPPORTED: one output row of 64-bit sums has
+ *                  to fit 64 KB of LDS
+ *   binned_out     DEVICE out_dtype[n_frames][out_h][out_w], compact, aligned to its type.  EVERY element is written by every
+ *                  successful call: the caller clears nothing.  Integer accumulation only: bit-identical across runs, input
+ *                  forms and launch shapes
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT in exactly the cases of trpx_decode_bins: a
+ *                  256-block group does not end where the next group's offset (the last group: the frame's size) says, a block is
+ *                  wider than dtype allows, a frame lies outside the stream or the index does not fit the offsets, with index ==
+ *                  NULL also for a valid stream with restated widths (trpx_build_index's verdict).  EVERY group of EVERY frame is
+ *                  walked and validated, also where every block of it has width 0.  The outputs are then unspecified
+ * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)) is read, nothing outside
+ * binned_out, status and the workspace is written, whatever the status.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits, a
+ * signed stream into an unsigned output, out_w > 8192; TRPX_ERR_INVALID_ARG for an unknown or float dtype, an out_dtype that is
+ * none of the six, zero sizes, a width that does not divide n_values, a bin side of 0, above 64 or above the frame's, null or
+ * misaligned pointers, an index without offsets; TRPX_ERR_CAPACITY for a workspace that is too small for the call's own form.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the
+ * host from n_frames, n_values, width, bin_y and bin_x alone, never from the data.
+ * trpx_decode_binned_bands_per_frame: the workgroups a frame is cut into, each a band of whole output rows whose sums live in
+ * LDS: rows = ceil(out_h / want), bands = ceil(out_h / rows), with want = min(out_h, max(ceil(out_h / max(1, 8192 / out_w)),
+ * min(ceil(1536 / n_frames), ceil(groups / 8)))) and groups = ceil(ceil(n_values / 12) / 256) -- pure arithmetic, for tests and
+ * diagnostics (0 for sizes no call takes).
+ * trpx_decode_binned_host: host terse / frame_offsets (or NULL) / binned_out; checks its arguments before a device is looked
+ * for, stages, calls trpx_decode_binned and synchronises.
+ */
+size_t trpx_decode_binned_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block);
+unsigned trpx_decode_binned_bands_per_frame(size_t n_values, size_t width, unsigned bin_y, unsigned bin_x, size_t n_frames);
+int trpx_decode_binned(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                       const void* index, size_t n_values, size_t n_frames, unsigned block, size_t width, unsigned bin_y,
+                       unsigned bin_x, void* binned_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_binned_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                            size_t n_values, size_t n_frames, unsigned block, size_t width, unsigned bin_y, unsigned bin_x,
+                            void* binned_out, int device);
 
 /*
  * Encode from events: the stream of a stack given in CSR form -- what trpx_decode_sparse writes, what a counting detector or a

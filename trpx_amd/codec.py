@@ -482,6 +482,56 @@ def decode_bins(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_value
     return out, status
 
 
+def decode_binned_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, block: int = BLOCK) -> int:
+    return lib().trpx_decode_binned_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block)
+
+
+def _bin_sides(bin):
+    """bin: an int (square bins) or (bin_y, bin_x)"""
+    by, bx = (bin, bin) if isinstance(bin, int) else bin
+    return int(by), int(bx)
+
+
+def decode_binned(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, width: int, bin,
+                  out_dtype=torch.int32, index: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                  workspace: Workspace | None = None, status: torch.Tensor | None = None, block: int = BLOCK):
+    """Every frame of a stack resident on the GPU summed over bins of ``bin_y x bin_x`` neighbouring pixels (trpx_decode_binned),
+    without decoding its frames to memory: previews, binned diffraction patterns, down-sampled movies.
+
+    ``dtype`` is the stream's pixel type; ``width`` the row length of a frame (``height = n_values // width``); ``bin`` an int
+    or ``(bin_y, bin_x)``, each side 1 .. 64 and no larger than the frame's; ``out_dtype`` one of int32, uint32, int64, uint64,
+    float32, float64, converted as ``decode_sum`` does.  Returns (binned [n_frames, ceil(height / bin_y), ceil(width / bin_x)],
+    status): edge bins sum the pixels that exist, every element is written; asynchronous on the current stream, like ``decode``.
+    status[0] is 5 for a corrupt stream or index -- the whole stack is validated.  ``frame_offsets = None``: the frames are
+    located first; ``index = None``: the decode index is built on the way (both in ``workspace``)."""
+    odt = torch_dtype(out_dtype)
+    if odt not in _SUM_OUT:
+        raise TypeError(f"decode_binned: out_dtype {odt} (int32, uint32, int64, uint64, float32, float64)")
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    bin_y, bin_x = _bin_sides(bin)
+    if width <= 0 or n_values % width:
+        raise ValueError(f"decode_binned: width {width} does not divide n_values {n_values}")
+    height = n_values // width
+    if not (1 <= bin_y <= min(height, 64) and 1 <= bin_x <= min(width, 64)):
+        raise ValueError(f"decode_binned: bin {bin_y} x {bin_x} in frames of {height} x {width} (1 .. 64, within the frame)")
+    out_h, out_w = -(-height // bin_y), -(-width // bin_x)
+    if out is None:
+        out = torch.empty((n_frames, out_h, out_w), dtype=odt, device=dev)
+    elif out.dtype != odt or out.numel() != n_frames * out_h * out_w or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_binned: out must be a contiguous {odt} tensor of {n_frames} x {out_h} x {out_w} elements on {dev}")
+    status = _status(status, dev)
+    ws_ptr, ws_bytes = None, 0
+    if index is None or frame_offsets is None:
+        ws = _scratch(workspace, dev, lib().trpx_decode_binned_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_binned(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                       n_values, n_frames, block, width, bin_y, bin_x, out.data_ptr(), status.data_ptr(), ws_ptr, ws_bytes,
+                                       _stream_ptr(terse)))
+    return out.view(n_frames, out_h, out_w), status
+
+
 def select_frames_workspace_bytes(n_frames: int, n_select: int) -> int:
     return lib().trpx_select_frames_workspace_bytes(n_frames, n_select)
 

@@ -18,6 +18,7 @@
 #include "decode_sparse.hpp"
 #include "decode_dot.hpp"
 #include "decode_bins.hpp"
+#include "decode_binned.hpp"
 #include "decode_sum.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -657,7 +658,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 }
 
 }  // extern "C"
-// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins -------------------
+// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned -------------------
 // Each reads: its own checks, the shared checks (stack_limits, consumer_ws), the front (consumer_front), its own few fields, launch.
 namespace {
 // The consumers take three input forms: index given; offsets only -- the index is built by trpx_build_index's walk; neither --
@@ -807,6 +808,23 @@ BinsWs bins_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_bins) {
     return w;
 }
 bool bins_count_ok(unsigned n_bins) { return n_bins >= 1 && n_bins <= trpx::kBinsMax; }
+
+// ---- binned decode (decode_binned.hip): no scratch of its own ------------------------------------------------------------------------
+// the checks the device-pointer and the host-pointer entry point share, behind the stack's own (a frame has < 2^29 values, see
+// frame_bits_fit_32); 0 = fine
+int binned_geometry(const char* fn, int dtype, int out_dtype, size_t n_values, size_t width, unsigned bin_y, unsigned bin_x) {
+    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "%s: out_dtype %d (I32, U32, I64, U64, F32, F64)", fn, out_dtype);
+    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
+        return fail(TRPX_ERR_UNSUPPORTED, "%s: signed stream into an unsigned output (Terse.hpp:356-357)", fn);
+    if (width == 0 || n_values % width) return fail(TRPX_ERR_INVALID_ARG, "%s: width %zu does not divide n_values %zu", fn, width, n_values);
+    const size_t height = n_values / width;
+    if (bin_y == 0 || bin_x == 0 || bin_y > trpx::kBinnedMaxBin || bin_x > trpx::kBinnedMaxBin || bin_y > height || bin_x > width)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bin %u x %u in frames of %zu x %zu (1..%u, within the frame)", fn, bin_y, bin_x, height, width,
+                    trpx::kBinnedMaxBin);
+    if ((width + bin_x - 1) / bin_x > trpx::kBinnedAccs)
+        return fail(TRPX_ERR_UNSUPPORTED, "%s: %zu bins in a row (at most %u)", fn, (width + bin_x - 1) / bin_x, trpx::kBinnedAccs);
+    return TRPX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1021,6 +1039,47 @@ int trpx_decode_bins(int dtype, const uint8_t* terse, size_t terse_bytes, const 
     a.bins_out = bins_out;
     a.status = status;
     HIP_TRY(trpx::launch_decode_bins(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+size_t trpx_decode_binned_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    return consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+}
+
+unsigned trpx_decode_binned_bands_per_frame(size_t n_values, size_t width, unsigned bin_y, unsigned bin_x, size_t n_frames) {
+    trpx::FrameGeom g;
+    if (!geom_of(n_values, kBlock, &g) || !sizes_ok(g, n_frames) || n_values >= ((size_t)1 << 29) || width == 0 || n_values % width) return 0;
+    if (bin_y == 0 || bin_x == 0 || bin_y > trpx::kBinnedMaxBin || bin_x > trpx::kBinnedMaxBin || bin_y > n_values / width || bin_x > width) return 0;
+    const trpx::BinnedGeom geo = trpx::binned_geom((uint32_t)n_values, (uint32_t)width, bin_y, bin_x);
+    return geo.out_w > trpx::kBinnedAccs ? 0 : trpx::binned_plan(geo, n_frames).bands;
+}
+
+int trpx_decode_binned(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                       const void* index, size_t n_values, size_t n_frames, unsigned block, size_t width, unsigned bin_y,
+                       unsigned bin_x, void* binned_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_binned", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {binned_out, sum_out_ok(out_dtype) ? sum_out_size(out_dtype) : 1}, {status, 8},
+                                   {frame_offsets, 8, false}, {index, 16, false}, {workspace, 8, false}}, &g))
+        return rc;
+    const Consumer c{"trpx_decode_binned", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
+    if (const int rc = binned_geometry("trpx_decode_binned", dtype, out_dtype, n_values, width, bin_y, bin_x)) return rc;
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, 0, nullptr, &w)) return rc;             // (offsets and index given: no workspace at all)
+    if (const int rc = consumer_front(c, w, true, &f)) return rc;
+    trpx::BinnedArgs a{};
+    static_cast<trpx::IndexedStack&>(a) = f.stack;
+    a.geo = trpx::binned_geom((uint32_t)n_values, (uint32_t)width, bin_y, bin_x);
+    a.plan = trpx::binned_plan(a.geo, n_frames);
+    a.out = binned_out;
+    a.out_code = out_dtype;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_binned(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -1547,6 +1606,32 @@ int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, c
                           reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
     if (rc || (rc = finish("trpx_decode_bins_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, bins_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_binned_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                            size_t n_values, size_t n_frames, unsigned block, size_t width, unsigned bin_y, unsigned bin_x,
+                            void* binned_out, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (const int rc = consumer_host_refusals("trpx_decode_binned_host", terse && binned_out, dtype, terse_bytes, n_values, n_frames, block, &g))
+        return rc;
+    const size_t ws_bytes = trpx_decode_binned_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_binned_host: bad dtype/sizes");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_binned_host: frames of >= 2^32 bits");
+    if (const int rc = binned_geometry("trpx_decode_binned_host", dtype, out_dtype, n_values, width, bin_y, bin_x)) return rc;
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_binned_host", device, &hs)) return rc;
+    const trpx::BinnedGeom geo = trpx::binned_geom((uint32_t)n_values, (uint32_t)width, bin_y, bin_x);
+    const size_t out_bytes = n_frames * (size_t)geo.out_h * geo.out_w * sum_out_size(out_dtype);
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_binned(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, width, bin_y, bin_x, d.out,
+                            d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_binned_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, binned_out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

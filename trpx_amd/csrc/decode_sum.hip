@@ -15,9 +15,9 @@
 // HBM traffic: stream + widths (+ group offsets) read once, n_out * n_values sums written (+ 2 x the partial slab when split).
 #include "codec_common.hpp"
 #include "decode_sum.hpp"
+#include "put_sum.hpp"
 #include "unpack_common.hpp"
 #include "unpack_tile.hpp"
-#include <limits.h>
 #include <type_traits>
 
 namespace trpx {
@@ -33,21 +33,6 @@ template <typename T> constexpr int sum_stage_dwords() {   // LDS: the tile's st
 }
 // stream dwords held in registers per lane while the previous frame is extracted (4 per load, all 256 lanes)
 template <typename T> constexpr int sum_prefetch_loads() { return (sum_image_dwords<T>() + 4 * kThreads - 1) / (4 * kThreads); }
-
-// The exact sum s -> one element of the output type: 32-bit integers clamp (Bit_pointer.hpp:747-763), 64-bit integers keep
-// it, float / double round it once to nearest even.  kPart32 / kPart64: a chunk's raw accumulator (partial slab).
-__device__ __forceinline__ void put_sum(void* __restrict__ out, uint64_t i, int code, int64_t s) {
-    switch (code) {
-    case kSumI32: static_cast<int32_t*>(out)[i] = (int32_t)(s > INT_MAX ? (int64_t)INT_MAX : s < INT_MIN ? (int64_t)INT_MIN : s); break;
-    case kSumU32: static_cast<uint32_t*>(out)[i] = (uint32_t)(s > (int64_t)UINT_MAX ? (int64_t)UINT_MAX : s < 0 ? 0 : s); break;
-    case kSumI64: static_cast<int64_t*>(out)[i] = s; break;
-    case kSumU64: static_cast<uint64_t*>(out)[i] = (uint64_t)s; break;
-    case kSumF32: static_cast<float*>(out)[i] = (float)s; break;
-    case kSumF64: static_cast<double*>(out)[i] = (double)s; break;
-    case kSumPart32: static_cast<uint32_t*>(out)[i] = (uint32_t)s; break;
-    case kSumPart64: static_cast<uint64_t*>(out)[i] = (uint64_t)s; break;
-    }
-}
 
 template <typename T>
 __device__ __forceinline__ int64_t acc_value(SumAcc<T> a) {

@@ -5,11 +5,11 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "codec_common.hpp"
+#include "put_sum.hpp"
 
 namespace trpx {
 
-// output element codes (the trpx_dtype values of include/trpx_hip.h) and the partial slabs' raw accumulators
-enum : int { kSumU32 = 4, kSumI32 = 5, kSumF32 = 6, kSumF64 = 7, kSumU64 = 8, kSumI64 = 9, kSumPart32 = 100, kSumPart64 = 101 };
+// (the output element codes kSumU32 .. kSumPart64 and the conversion: put_sum.hpp)
 // Few outputs: each group's frames are split into chunks until about this many workgroups run (about four per CU).
 constexpr uint64_t kSumTargetUnits = 1024;
 constexpr uint32_t kSumSubTiles = 2;                 // 256-block groups per tile

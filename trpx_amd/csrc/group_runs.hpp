@@ -1,5 +1,6 @@
 // A RUN of consecutive 256-block groups of one frame on one wavefront, as the kernels that walk a whole stack through its decode
-// index see it (decode_sparse.hip: trpx_decode_sparse, decode_dot.hip: trpx_decode_dot, decode_bins.hip: trpx_decode_bins): what belongs to the run is loaded once
+// index see it (decode_sparse.hip: trpx_decode_sparse, decode_dot.hip: trpx_decode_dot, decode_bins.hip: trpx_decode_bins,
+// decode_binned.hip: trpx_decode_binned): what belongs to the run is loaded once
 // (the frame's bytes, the groups' offsets: one per lane), and the blocks a group chooses are compacted into consecutive lanes
 // through a per-wavefront list in LDS, 64 at a time.  The group itself: group_front.hpp.
 #pragma once

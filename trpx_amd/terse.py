@@ -285,6 +285,29 @@ class Terse:
         frames = range(self.number_of_frames()) if frames is None else frames
         return self.prolix_boxes([(int(f), y0, x0) for f in frames], (h, w))
 
+    def prolix_binned(self, bin, out_dtype=np.int32) -> np.ndarray:
+        """Every frame summed over bins of ``bin_y x bin_x`` neighbouring pixels in ONE GPU call (trpx_decode_binned_host),
+        without decoding the frames to memory.  ``bin``: an int or ``(bin_y, bin_x)``, each side 1 .. 64 and no larger than the
+        frame's; ``dim()`` = {width, height} must be set.  Returns ``[number_of_frames, ceil(height / bin_y), ceil(width /
+        bin_x)]`` of ``out_dtype`` (int32 / uint32 clamp, int64 / uint64 exact, float32 / float64 rounded once); edge bins sum
+        the pixels that exist."""
+        if len(self._dim) != 2 or self._dim[0] * self._dim[1] != self._size:
+            raise ValueError("prolix_binned: dim() must be set to {width, height} of the frames")
+        width, height = self._dim
+        bin_y, bin_x = (int(bin), int(bin)) if np.isscalar(bin) else (int(x) for x in bin)
+        if not (1 <= bin_y <= min(height, 64) and 1 <= bin_x <= min(width, 64)):
+            raise ValueError("prolix_binned: a bin side is 1 .. 64 and no larger than the frame's")
+        if self._signed and np.dtype(out_dtype).kind == "u":
+            raise ValueError("signed data cannot be decompressed into unsigned data")            # Terse.hpp:356-357
+        code, _ = self._stream_type("prolix_binned")
+        f = self.number_of_frames()
+        out = np.empty((f, -(-height // bin_y), -(-width // bin_x)), np.dtype(out_dtype))
+        if f:
+            buf, offs = self._stream_and_offsets()
+            check(lib().trpx_decode_binned_host(code, _code(out_dtype, True), buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f,
+                                                self._block, width, bin_y, bin_x, out.ctypes.data, self._device))
+        return out
+
     def prolix_sparse(self, threshold: int, frames=None):
         """The pixels with value >= ``threshold`` (trpx_decode_sparse_host: two GPU calls, sizes then events), without decoding
         the frames to memory.  Returns numpy ``(row_offsets int64 [n + 1], positions uint32, values)``: event i of the k-th frame
