@@ -20,6 +20,7 @@
 #include "decode_bins.hpp"
 #include "decode_binned.hpp"
 #include "decode_sum.hpp"
+#include "group_runs.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
 #include "select_map.hpp"
@@ -790,8 +791,8 @@ struct DotWs { size_t support, partials, total; };
 DotWs dot_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_maps) {
     DotWs w;
     w.support = 0;
-    w.partials = trpx::align_up(w.support + 4 * trpx::dot_support_words(g), 8);
-    w.total = w.partials + 8 * n_frames * (size_t)trpx::dot_runs_per_frame(g) * n_maps;
+    w.partials = trpx::align_up(w.support + 4 * trpx::support_words(g), 8);
+    w.total = w.partials + 8 * n_frames * (size_t)trpx::runs_per_frame(g) * n_maps;
     return w;
 }
 bool dot_maps_ok(unsigned n_maps) { return n_maps >= 1 && n_maps <= trpx::kDotMaxMaps; }
@@ -803,7 +804,7 @@ BinsWs bins_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_bins) {
     BinsWs w;
     const size_t spans = trpx::bins_spans_per_frame(g, n_frames);
     w.support = 0;
-    w.partials = trpx::align_up(w.support + 4 * trpx::bins_support_words(g), 8);
+    w.partials = trpx::align_up(w.support + 4 * trpx::support_words(g), 8);
     w.total = w.partials + (spans > 1 ? 8 * (size_t)n_bins * n_frames * spans : 0);
     return w;
 }

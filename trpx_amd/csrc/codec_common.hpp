@@ -264,6 +264,11 @@ inline void zero_status(uint32_t* status, hipStream_t st) {           // 8 x u32
     hipLaunchKernelGGL(k_zero_words<0>, dim3(1), dim3(kThreads), 0, st, static_cast<uint64_t*>(nullptr), (uint64_t)0,
                        reinterpret_cast<uint64_t*>(status), (uint64_t)4);
 }
+// workgroups for `units` pieces of work at per_wg a workgroup, at most cap: a kernel launched with it strides over what is left
+inline uint32_t grid_capped(uint64_t units, uint32_t per_wg, uint32_t cap = 4096) {
+    const uint64_t wgs = (units + per_wg - 1) / per_wg;
+    return (uint32_t)(wgs < cap ? wgs : cap);
+}
 
 // ---- workspace layouts (device memory, carved by the host API) -------------------------------
 // encode: [status-shadow 64 B][frame_size u64 x F][tile_off u64 x F*T][tile_bits u32 x F*T]

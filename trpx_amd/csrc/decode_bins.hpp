@@ -17,16 +17,14 @@ struct BinsArgs : IndexedStack {
     const uint16_t* labels;         // [n_values]
     uint32_t        n_bins;
     uint32_t        spans;          // bins_spans_per_frame(): workgroups per frame
-    uint32_t*       support;        // workspace, bins_support_words(): bit b = some label of block b of a frame is a bin
+    uint32_t*       support;        // workspace, support_words() (group_runs.hpp): bit b = some label of block b of a frame is a bin
     int64_t*        partials;       // workspace, [n_frames][spans][n_bins] (spans > 1 only)
     int64_t*        bins_out;       // [n_frames][n_bins]
     uint32_t*       status;
 };
-uint32_t bins_runs_per_frame(const FrameGeom& g);
 // min(ceil(runs per frame / 4), max(1, ceil(kBinsTargetWgs / n_frames))): arithmetic on the geometry
 uint32_t bins_spans_per_frame(const FrameGeom& g, uint64_t n_frames);
-__host__ __device__ inline size_t bins_support_words(const FrameGeom& g) { return ((size_t)g.n_blocks + 31) / 32; }
-// k_bins_support, k_bins_spans, k_bins_reduce (spans > 1); clear_status: zero the status block first
+// k_bins_support, k_bins_spans, k_reduce_parts (spans > 1); clear_status: zero the status block first
 hipError_t launch_decode_bins(int dtype, const BinsArgs& a, bool clear_status, hipStream_t st);
 
 }  // namespace trpx

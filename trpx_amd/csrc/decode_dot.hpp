@@ -13,14 +13,12 @@ constexpr uint32_t kDotMaxMaps = 16;
 struct DotArgs : IndexedStack {
     const int32_t*  weights;        // [n_maps][n_values]
     uint32_t        n_maps;
-    uint32_t*       support;        // workspace, dot_support_words(): bit b = some map is non-zero on block b of a frame
-    int64_t*        partials;       // workspace, [n_frames][dot_runs_per_frame()][n_maps]
+    uint32_t*       support;        // workspace, support_words() (group_runs.hpp): bit b = some map is non-zero on block b of a frame
+    int64_t*        partials;       // workspace, [n_frames][runs_per_frame()][n_maps]
     int64_t*        dots_out;       // [n_frames][n_maps]
     uint32_t*       status;
 };
-uint32_t dot_runs_per_frame(const FrameGeom& g);
-__host__ __device__ inline size_t dot_support_words(const FrameGeom& g) { return ((size_t)g.n_blocks + 31) / 32; }
-// k_dot_support, k_dot_runs, k_dot_reduce; clear_status: zero the status block first
+// k_dot_support, k_dot_runs, k_reduce_parts; clear_status: zero the status block first
 hipError_t launch_decode_dot(int dtype, const DotArgs& a, bool clear_status, hipStream_t st);
 
 }  // namespace trpx

@@ -1,21 +1,16 @@
 // Threshold decode (trpx_decode_sparse): a stack with its decode index -> the pixels at or above a threshold as (row offsets,
 // positions, values), without expanding the frames.  The order of the output is fixed (by frame, then by pixel), so the
 // shape is count -> scan -> write.  The two kernels that read the stream give a wavefront a RUN of kRun consecutive 256-block
-// groups of one frame (group_front.hpp: four blocks per lane; group_runs.hpp: the run and the candidate list): what belongs to
-// the run is loaded once and coalesced (the frame's bytes, the groups' offsets, counts, bases and flag words, one per lane), the
-// next group's widths are in flight while a group is scanned and extracted, and the run's counts and flag words leave in one
-// store each.
+// groups of one frame and walk it with the pieces of group_runs.hpp (run_groups, list_compact, list_rounds): the run's counts,
+// bases and flag words are loaded and stored coalesced, one per lane, in one access each.
 //
-//   k_sparse_count       every group of every frame: widths -> header_len + 12 * w -> wave scans from the group's offset -> the
-//                        group validated (so the whole stack is) -> the CANDIDATE blocks, those wide enough to hold an event (a
-//                        block's width bounds its values), compacted into consecutive lanes through a list in LDS -> per 64
-//                        candidates one round: the payload dwords straight from the stream into registers, the register
-//                        extraction, the compare on the extracted values -> per group the number of events and a 256-bit set,
-//                        bit i = "candidate i (in block order) has events".  A group that fails validation sets CORRUPT and
-//                        counts nothing.
+//   k_sparse_count       every group of every frame.  The CANDIDATE blocks are those wide enough to hold an event (a block's
+//                        width bounds its values); per round the compare on the extracted values -> per group the number of
+//                        events and a 256-bit set, bit i = "candidate i (in block order) has events".  A group that fails
+//                        validation sets CORRUPT and counts nothing.
 //   k_sparse_frame_scan  per frame (one wavefront): exclusive scan of its groups' counts, the frame's total
 //   k_sparse_stack_scan  one workgroup: exclusive scan of the frames' totals -> row_offsets; CAPACITY when the total exceeds it
-//   k_sparse_write       groups with events only: the front end again, the candidates that have events compacted and extracted
+//   k_sparse_write       groups with events only (run_groups over a mask): the candidates that have events compacted and extracted
 //                        again, each event stored at row_offsets[frame] + base[group] + its rank in the group (block order,
 //                        then k), under index < capacity.
 // HBM traffic: the widths (and 16 bytes per group) twice at most, the payload of the candidate blocks, 40 bytes per group of
@@ -39,158 +34,99 @@ __device__ __forceinline__ uint32_t event_mask(const uint32_t (&o)[PackedDwords<
     return mask;
 }
 
-// entry 64 * c + lane of a list of n: the lane's block, extracted; returns its event mask (0 behind the list's end)
-template <typename T>
-__device__ __forceinline__ uint32_t list_round(uint32_t (&o)[PackedDwords<T>::n], uint32_t& block, const uint32_t* __restrict__ list,
-                                               uint32_t n, uint32_t c, uint32_t grp, const FrameGeom& g, const GroupStream& gs,
-                                               int64_t threshold, uint32_t lane) {
-    const bool have = c * kWave + lane < n;
-    const uint32_t e = have ? list[c * kWave + lane] : 0u;
-    block = grp * kTileBlocks + (e >> 23);
-    const uint32_t left = (uint32_t)g.n_values - block * kBlock;   // (listed blocks lie inside the frame: < 2^29 values)
-    const uint32_t nr = have ? (left < (uint32_t)kBlock ? left : (uint32_t)kBlock) : 0u;
-    group_extract<T>(o, gs, have, (e >> 17) & 63u, nr, e & 0x1FFFFu);
-    return have ? event_mask<T>(o, nr, threshold) : 0u;
+__device__ __forceinline__ uint64_t pick64(uint32_t k, uint64_t v0, uint64_t v1, uint64_t v2, uint64_t v3) {   // (values, not references: the choice stays in registers)
+    return k == 0u ? v0 : k == 1u ? v1 : k == 2u ? v2 : v3;
 }
 
 template <typename T>
 __device__ __forceinline__ void sparse_count_run(const SparseArgs& a, uint64_t run, uint32_t runs_per_frame, uint32_t* __restrict__ list) {
-    const FrameGeom& g = a.geom;
     const uint32_t lane = (uint32_t)lane_id();
     Run R = run_place(a, run, runs_per_frame);
     run_load(R, a, lane);
-    uint32_t wn[kGroupRows], nbn[kGroupRows], wp0n[kGroupRows];
-    group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0, lane);
     uint32_t my_count = 0;                                  // lane j: group g0 + j's events
     uint64_t my_flags = 0;                                  // lane 4 * j + c: "has events" of its candidates 64 c .. 64 c + 63
-    bool bad = false;
-#pragma unroll 1
-    for (uint32_t j = 0; j < R.n; ++j) {
-        uint32_t w[kGroupRows], nb[kGroupRows], wp0[kGroupRows], off[kGroupRows];
-#pragma unroll
-        for (int r = 0; r < kGroupRows; ++r) { w[r] = wn[r]; nb[r] = nbn[r]; wp0[r] = wp0n[r]; }
-        if (j + 1 < R.n) group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + j + 1, lane);   // in flight during this group
-        const uint64_t t_off = lane_value64(R.my_off, j), t_next = lane_value64(R.my_off, j + 1);
-        if (!group_offsets<T>(off, w, nb, wp0, R.fo, R.fe, t_off, t_next, R.g0 + j + 1 == g.n_tiles, a.terse_bytes, lane)) {
-            bad = true;                                     // (count 0, no flags: the later passes never touch the group)
-            continue;
-        }
-        const GroupStream gs = group_stream(a.terse, a.terse_bytes, R.fo, t_off);
-        // ---- the candidates, in block order, into consecutive entries
-        uint32_t n_cand = 0;
-#pragma unroll
-        for (int r = 0; r < kGroupRows; ++r) {
-            const bool want = nb[r] != 0u && w[r] >= a.min_width;   // an optimisation only: the verdict is the compare below
-            const uint64_t ballot = __ballot(want);
-            if (want) list[n_cand + lanes_below(ballot)] = list_entry(off[r], w[r], r * kWave + lane);
-            n_cand += (uint32_t)__builtin_popcountll(ballot);
-        }
-        list_sync();
-        uint32_t count = 0;
-#pragma unroll 1
-        for (uint32_t c = 0; c * kWave < n_cand; ++c) {
-            uint32_t o[PackedDwords<T>::n], block;
-            const uint32_t mask = list_round<T>(o, block, list, n_cand, c, R.g0 + j, g, gs, a.threshold, lane);
-            count += (uint32_t)__builtin_popcount(mask);
-            const uint64_t has = __ballot(mask != 0u);
-            if (lane == (uint32_t)kGroupRows * j + c) my_flags = has;
-        }
-        list_sync();                                        // (the next group rewrites the list)
-        const uint32_t inc = wave_inclusive_scan(count);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        if (lane == j) my_count = total;
-    }
-    if (bad && lane == 0) atomicMax(&a.status[0], kStatusCorrupt);
+    const bool bad = run_groups<T>(a, R, AllGroups{R.n}, NoSupport{}, lane,   // (not valid: count 0, no flags: the later passes never touch the group)
+        [&](uint32_t j, const uint32_t (&w)[kGroupRows], const uint32_t (&nb)[kGroupRows], const uint32_t (&)[kGroupRows],
+            const uint32_t (&off)[kGroupRows], const GroupStream& gs) {
+            // (the width: an optimisation only, the verdict is the compare on the values)
+            const uint32_t n_cand = list_compact(list, off, w, lane, [&](int r) { return nb[r] != 0u && w[r] >= a.min_width; });
+            uint32_t count = 0;
+            list_rounds<T>(list, n_cand, R.g0 + j, a.geom, gs, lane,
+                [&](uint32_t c, uint32_t, uint32_t nr, const uint32_t (&o)[PackedDwords<T>::n], bool have) {
+                    const uint32_t mask = have ? event_mask<T>(o, nr, a.threshold) : 0u;
+                    count += (uint32_t)__builtin_popcount(mask);
+                    const uint64_t has = __ballot(mask != 0u);
+                    if (lane == (uint32_t)kGroupRows * j + c) my_flags = has;
+                });
+            const uint32_t inc = wave_inclusive_scan(count);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+            if (lane == j) my_count = total;
+        });
+    run_verdict(bad, a.status, lane);
     if (lane < R.n) a.counts[R.u0 + lane] = my_count;
     if (lane < (uint32_t)kGroupRows * R.n) a.flags[kGroupRows * R.u0 + lane] = my_flags;
 }
 
 template <typename T>
 __device__ __forceinline__ void sparse_write_run(const SparseArgs& a, uint64_t run, uint32_t runs_per_frame, uint32_t* __restrict__ list) {
-    const FrameGeom& g = a.geom;
     const uint32_t lane = (uint32_t)lane_id();
     Run R = run_place(a, run, runs_per_frame);
     const uint32_t my_count = lane < R.n ? a.counts[R.u0 + lane] : 0u;
-    uint64_t todo = __ballot(my_count != 0u);               // the run's groups with events
+    const uint64_t todo = __ballot(my_count != 0u);         // the run's groups with events
     if (todo == 0ull) return;                               // (after one load)
     run_load(R, a, lane);
     const uint32_t my_base = lane < R.n ? a.base[R.u0 + lane] : 0u;
     const uint64_t my_flags = lane < (uint32_t)kGroupRows * R.n ? a.flags[kGroupRows * R.u0 + lane] : 0ull;
     const uint64_t row = a.row_offsets[R.frame];
     T* __restrict__ values = static_cast<T*>(a.values);
-    uint32_t wn[kGroupRows], nbn[kGroupRows], wp0n[kGroupRows];
-    group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + (uint32_t)__builtin_ctzll(todo), lane);
-#pragma unroll 1
-    while (todo) {
-        const uint32_t j = (uint32_t)__builtin_ctzll(todo);
-        todo &= todo - 1;
-        uint32_t w[kGroupRows], nb[kGroupRows], wp0[kGroupRows], off[kGroupRows];
+    run_groups<T>(a, R, MaskGroups{todo}, NoSupport{}, lane,           // (no verdict: a group with a count was valid)
+        [&](uint32_t j, const uint32_t (&w)[kGroupRows], const uint32_t (&nb)[kGroupRows], const uint32_t (&)[kGroupRows],
+            const uint32_t (&off)[kGroupRows], const GroupStream& gs) {
+            // ---- the candidates again, in the count pass's order; those it found events in go into the list: the predicate
+            // ranks the row's candidates first (list_compact calls it row by row)
+            const uint32_t l0 = (uint32_t)kGroupRows * j;
+            const uint64_t has0 = uniform64(lane_value64(my_flags, l0)), has1 = uniform64(lane_value64(my_flags, l0 + 1)),
+                           has2 = uniform64(lane_value64(my_flags, l0 + 2)), has3 = uniform64(lane_value64(my_flags, l0 + 3));
+            uint32_t n_cand = 0;
+            const uint32_t n_list = list_compact(list, off, w, lane, [&](int r) {
+                const bool cand = nb[r] != 0u && w[r] >= a.min_width;
+                const uint64_t ballot = __ballot(cand);
+                const uint32_t i = n_cand + lanes_below(ballot);              // the block's place among the candidates
+                n_cand += (uint32_t)__builtin_popcountll(ballot);
+                return cand && ((pick64(i >> 6, has0, has1, has2, has3) >> (i & 63u)) & 1ull);
+            });
+            uint64_t at = row + (uint32_t)__shfl((int)my_base, (int)j, kWave);   // where the group's next event goes
+            list_rounds<T>(list, n_list, R.g0 + j, a.geom, gs, lane,
+                [&](uint32_t, uint32_t block, uint32_t nr, const uint32_t (&o)[PackedDwords<T>::n], bool have) {
+                    const uint32_t mask = have ? event_mask<T>(o, nr, a.threshold) : 0u;
+                    const uint32_t m = (uint32_t)__builtin_popcount(mask);
+                    const uint32_t inc = wave_inclusive_scan(m);
+                    uint64_t i = at + (inc - m);            // rank: the blocks in front (block order), then k ascending
 #pragma unroll
-        for (int r = 0; r < kGroupRows; ++r) { w[r] = wn[r]; nb[r] = nbn[r]; wp0[r] = wp0n[r]; }
-        if (todo) group_load_widths(wn, nbn, wp0n, R.wf, g, R.g0 + (uint32_t)__builtin_ctzll(todo), lane);   // in flight during this group
-        const uint64_t t_off = lane_value64(R.my_off, j), t_next = lane_value64(R.my_off, j + 1);
-        if (!group_offsets<T>(off, w, nb, wp0, R.fo, R.fe, t_off, t_next, R.g0 + j + 1 == g.n_tiles, a.terse_bytes, lane)) continue;   // (counted: it was valid)
-        const GroupStream gs = group_stream(a.terse, a.terse_bytes, R.fo, t_off);
-        // ---- the candidates again, in the count pass's order; those it found events in go into the list
-        uint64_t has[kGroupRows];
-#pragma unroll
-        for (int c = 0; c < kGroupRows; ++c) has[c] = uniform64(lane_value64(my_flags, (uint32_t)kGroupRows * j + c));
-        uint32_t n_cand = 0, n_list = 0;
-#pragma unroll
-        for (int r = 0; r < kGroupRows; ++r) {
-            const bool want = nb[r] != 0u && w[r] >= a.min_width;
-            const uint64_t ballot = __ballot(want);
-            const uint32_t i = n_cand + lanes_below(ballot);                  // the block's place among the candidates
-            const uint64_t word = (i >> 6) == 0u ? has[0] : (i >> 6) == 1u ? has[1] : (i >> 6) == 2u ? has[2] : has[3];
-            const bool listed = want && ((word >> (i & 63u)) & 1ull);
-            const uint64_t lballot = __ballot(listed);
-            if (listed) list[n_list + lanes_below(lballot)] = list_entry(off[r], w[r], r * kWave + lane);
-            n_cand += (uint32_t)__builtin_popcountll(ballot);
-            n_list += (uint32_t)__builtin_popcountll(lballot);
-        }
-        list_sync();
-        uint64_t at = row + (uint32_t)__shfl((int)my_base, (int)j, kWave);   // where the group's next event goes
-#pragma unroll 1
-        for (uint32_t c = 0; c * kWave < n_list; ++c) {
-            uint32_t o[PackedDwords<T>::n], block;
-            const uint32_t mask = list_round<T>(o, block, list, n_list, c, R.g0 + j, g, gs, a.threshold, lane);
-            const uint32_t m = (uint32_t)__builtin_popcount(mask);
-            const uint32_t inc = wave_inclusive_scan(m);
-            uint64_t i = at + (inc - m);                    // rank: the blocks in front (block order), then k ascending
-#pragma unroll
-            for (int k = 0; k < kBlock; ++k) {
-                if (mask & (1u << k)) {
-                    if (i < a.capacity) {
-                        a.positions[i] = block * kBlock + k;
-                        values[i] = packed_value<T>(o, k);
+                    for (int k = 0; k < kBlock; ++k) {
+                        if (mask & (1u << k)) {
+                            if (i < a.capacity) {
+                                a.positions[i] = block * kBlock + k;
+                                values[i] = packed_value<T>(o, k);
+                            }
+                            ++i;
+                        }
                     }
-                    ++i;
-                }
-            }
-            at += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-        }
-        list_sync();                                        // (the next group rewrites the list)
-    }
+                    at += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+                });
+        });
 }
 
 }  // namespace
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void k_sparse_count(SparseArgs a, uint32_t runs_per_frame) {
-    __shared__ uint32_t s_list[kWavesPerWg * kTileBlocks];
-    const uint64_t runs = a.n_frames * runs_per_frame;
-    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerWg;
-    for (uint64_t run = (uint64_t)blockIdx.x * kWavesPerWg + (uint32_t)wave_id(); run < runs; run += stride)
-        sparse_count_run<T>(a, run, runs_per_frame, s_list + wave_id() * kTileBlocks);
+    for_each_run(a.n_frames * runs_per_frame, [&](uint64_t run, uint32_t* __restrict__ list) { sparse_count_run<T>(a, run, runs_per_frame, list); });
 }
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void k_sparse_write(SparseArgs a, uint32_t runs_per_frame) {
-    __shared__ uint32_t s_list[kWavesPerWg * kTileBlocks];
-    const uint64_t runs = a.n_frames * runs_per_frame;
-    const uint64_t stride = (uint64_t)gridDim.x * kWavesPerWg;
-    for (uint64_t run = (uint64_t)blockIdx.x * kWavesPerWg + (uint32_t)wave_id(); run < runs; run += stride)
-        sparse_write_run<T>(a, run, runs_per_frame, s_list + wave_id() * kTileBlocks);
+    for_each_run(a.n_frames * runs_per_frame, [&](uint64_t run, uint32_t* __restrict__ list) { sparse_write_run<T>(a, run, runs_per_frame, list); });
 }
 
 // per frame, one wavefront: exclusive scan of the groups' counts (a frame has < 2^29 pixels: 32 bits), the frame's total
@@ -244,11 +180,9 @@ uint32_t sparse_min_width(int64_t threshold, bool stream_signed) {
 hipError_t launch_decode_sparse(int dtype, const SparseArgs& a, bool clear_status, hipStream_t st) {
     if (clear_status) zero_status(a.status, st);
     // launch shapes from the geometry alone: a wavefront per run of kRun groups up to 4096 workgroups, strided runs beyond
-    const uint32_t rpf = (a.geom.n_tiles + kRun - 1) / kRun;
-    const uint64_t wgs = (a.n_frames * rpf + kWavesPerWg - 1) / kWavesPerWg;
-    const uint32_t grid = (uint32_t)(wgs < 4096 ? wgs : 4096);
-    const uint64_t fwgs = (a.n_frames + kWavesPerWg - 1) / kWavesPerWg;
-    const uint32_t fgrid = (uint32_t)(fwgs < 4096 ? fwgs : 4096);
+    const uint32_t rpf = runs_per_frame(a.geom);
+    const uint32_t grid = grid_capped(a.n_frames * rpf, kWavesPerWg);
+    const uint32_t fgrid = grid_capped(a.n_frames, kWavesPerWg);
     return for_pixel_type(dtype, [&]<class T>() {
         hipLaunchKernelGGL((k_sparse_count<T>), dim3(grid), dim3(kThreads), 0, st, a, rpf);
         hipLaunchKernelGGL(k_sparse_frame_scan, dim3(fgrid), dim3(kThreads), 0, st, a.counts, a.n_frames, a.geom.n_tiles, a.base, a.frame_total);
