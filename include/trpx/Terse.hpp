@@ -212,6 +212,33 @@ public:
                                            (unsigned)group, out, -1), "Terse::prolix_sum");
     }
 
+    /// Per pixel, one statistic over `group` consecutive frames into `out` (ceil(number_of_frames() / group) x size() values) in
+    /// one device call, without expanding the frames (trpx_decode_reduce_host).  op: TRPX_REDUCE_MAX / TRPX_REDUCE_MIN -- V is the
+    /// narrowest integer type that holds the object's values ((u)int8_t for bits_per_val() <= 8, (u)int16_t for <= 16, (u)int32_t
+    /// for <= 32, signed as is_signed()); TRPX_REDUCE_SUMSQ -- V is uint64_t, the sum of squares modulo 2^64;
+    /// TRPX_REDUCE_COUNT_GE -- V is uint32_t, the frames with pixel >= threshold.  A V that is not what the op writes throws.
+    template <typename V>
+    void prolix_reduce(V* out, int op, std::size_t group, std::int64_t threshold = 0) {
+        static_assert(std::is_integral_v<V> && !std::is_same_v<V, bool> && (sizeof(V) <= 4 || std::is_same_v<V, std::uint64_t>),
+                      "prolix_reduce: the pixel type (max, min), uint64_t (sum of squares) or uint32_t (count)");
+        if (op < TRPX_REDUCE_MAX || op > TRPX_REDUCE_COUNT_GE) throw std::invalid_argument("prolix_reduce: unknown op");
+        if (group == 0) throw std::invalid_argument("prolix_reduce: group must be at least 1");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_reduce: values of more than 32 bits are not supported");
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        const int dtype = bits + (d_signed ? 1 : 0);
+        const bool fits = op == TRPX_REDUCE_SUMSQ      ? std::is_same_v<V, std::uint64_t>
+                          : op == TRPX_REDUCE_COUNT_GE ? std::is_same_v<V, std::uint32_t>
+                                                       : sizeof(V) == trpx_dtype_size(dtype) && std::is_signed_v<V> == (d_signed != 0);
+        if (!fits) throw std::invalid_argument("prolix_reduce: the output type is not what the op writes for this object");
+        if (d_frame_sizes.empty()) return;
+        detail::require_abi();
+        group = std::min(group, d_frame_sizes.size());
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        detail::check(trpx_decode_reduce_host(dtype, op, d_terse_data.data(), d_terse_data.size(), offs.data(), d_size,
+                                              d_frame_sizes.size(), d_block, (unsigned)group, threshold, out, -1), "Terse::prolix_reduce");
+    }
+
     /// Every frame summed over bins of bin_y x bin_x neighbouring pixels into `out` (number_of_frames() x ceil(height / bin_y) x
     /// ceil(width / bin_x) values, frame by frame, row by row) in one device call, without expanding the frames
     /// (trpx_decode_binned_host).  dim() = {width, height} must be set; a bin side is 1 .. 64 and no larger than the frame's; the

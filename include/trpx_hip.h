@@ -53,8 +53,8 @@ typedef enum trpx_status {
  * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
  *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
- *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins and trpx_decode_binned where they build the index themselves (no
- *     index given) -- and their _host forms;
+ *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned and trpx_decode_reduce where they build the
+ *     index themselves (no index given) -- and their _host forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -538,6 +538,53 @@ int trpx_decode_binned(int dtype, int out_dtype, const uint8_t* terse, size_t te
 int trpx_decode_binned_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                             size_t n_values, size_t n_frames, unsigned block, size_t width, unsigned bin_y, unsigned bin_x,
                             void* binned_out, int device);
+
+/*
+ * Reducing decode: per pixel, one statistic over groups of consecutive frames, straight from the stream and its decode index,
+ * without writing the decoded frames -- the companion of trpx_decode_sum for the statistics that are no sum of pixels: the
+ * maximum pattern of a scan, the sum of squares behind a variance (noise) map, the hit-rate map of a counting detector.
+ *   dtype          the stream's pixel type T, TRPX_U8 .. TRPX_I32
+ *   op             TRPX_REDUCE_MAX / TRPX_REDUCE_MIN: out is T[n_out][n_values], exactly px[g0:g1].max(0) / .min(0).  The zeros of a
+ *                  width-0 block take part: the max of negative frames and one blank frame is 0.
+ *                  TRPX_REDUCE_SUMSQ: out is uint64_t, the sum of (int64)v * (int64)v modulo 2^64, accumulated in unsigned
+ *                  arithmetic: always exact for 8- and 16-bit pixel types, for 32-bit types while the true sum is below 2^64 (the
+ *                  precedent of trpx_decode_dot).
+ *                  TRPX_REDUCE_COUNT_GE: out is uint32_t, the number of frames of the group with (int64)v >= threshold, the
+ *                  comparison of trpx_decode_sparse: a threshold at or below the type's minimum counts every frame, one above its
+ *                  maximum counts none.  count == frames of the group: a hot pixel.
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_sum: index given -- no workspace unless the launch plan splits the groups
+ *                  into frame chunks; offsets only -- the index is built in the workspace by trpx_build_index's walk; offsets NULL
+ *                  -- the frames are located in the workspace first.  workspace: DEVICE, 8-byte aligned, >=
+ *                  trpx_decode_reduce_workspace_bytes() (the need with offsets and index both NULL; the call checks against what
+ *                  its own form needs)
+ *   group          frames per output, >= 1; n_out = ceil(n_frames / group); output j reduces frames [j * group, min((j + 1) * group,
+ *                  n_frames)): a short last group reduces the frames that exist
+ *   threshold      TRPX_REDUCE_COUNT_GE only; ignored by the other ops
+ *   out            DEVICE, compact, aligned to its element type only.  EVERY element is written by every successful call: the
+ *                  caller clears nothing.  Integer arithmetic, no atomics on the output: bit-identical across runs, input forms
+ *                  and launch splits
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT in the cases of trpx_decode_sum, with index == NULL
+ *                  also for a valid stream with restated widths; the outputs are then unspecified
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits;
+ * TRPX_ERR_INVALID_ARG for an unknown or float dtype, an unknown op, group 0, bad sizes, null or misaligned pointers, an index
+ * without offsets; TRPX_ERR_CAPACITY for a workspace that is too small for the call's own form.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape and split is decided
+ * on the host from the geometry alone: trpx_decode_sum's plan.  trpx_decode_reduce_chunks: the frame chunks a group is split
+ * into -- pure arithmetic, for tests and diagnostics (0 for sizes no call takes).
+ * trpx_decode_reduce_host: host terse / frame_offsets (or NULL) / out; checks its arguments before a device is looked for,
+ * stages, calls trpx_decode_reduce and synchronises.
+ */
+typedef enum trpx_reduce_op { TRPX_REDUCE_MAX = 0, TRPX_REDUCE_MIN = 1, TRPX_REDUCE_SUMSQ = 2, TRPX_REDUCE_COUNT_GE = 3 } trpx_reduce_op;
+size_t trpx_decode_reduce_workspace_bytes(int dtype, int op, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                          unsigned group);
+unsigned trpx_decode_reduce_chunks(int dtype, size_t n_values, size_t n_frames, unsigned group);
+int trpx_decode_reduce(int dtype, int op, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                       size_t n_values, size_t n_frames, unsigned block, unsigned group, int64_t threshold, void* out,
+                       uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_reduce_host(int dtype, int op, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                            size_t n_frames, unsigned block, unsigned group, int64_t threshold, void* out, int device);
 
 /*
  * Encode from events: the stream of a stack given in CSR form -- what trpx_decode_sparse writes, what a counting detector or a

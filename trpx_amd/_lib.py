@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("TRPX_LIB") or os.path.join(_HERE, "libtrpx_hip.so")  
 
 OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_CAPACITY, ERR_HIP, ERR_CORRUPT, ERR_NO_DEVICE, ERR_TIMEOUT = range(8)
 U8, I8, U16, I16, U32, I32, F32, F64, U64, I64 = range(10)
+REDUCE_MAX, REDUCE_MIN, REDUCE_SUMSQ, REDUCE_COUNT_GE = range(4)     # trpx_reduce_op
 STATUS_WORDS = 8
 ABI_VERSION = 3          # TRPX_ABI_VERSION of include/trpx_hip.h (tests/test_abi.py compares them)
 
@@ -75,6 +76,10 @@ SYMBOLS = {
     "trpx_decode_binned_bands_per_frame": (_U, [_SZ, _SZ, _U, _U, _SZ]),
     "trpx_decode_binned": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _SZ, _U, _U, _P, _P, _P, _SZ, _P]),
     "trpx_decode_binned_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _SZ, _U, _U, _P, _I]),
+    "trpx_decode_reduce_workspace_bytes": (_SZ, [_I, _I, _SZ, _SZ, _SZ, _U, _U]),
+    "trpx_decode_reduce_chunks": (_U, [_I, _SZ, _SZ, _U]),
+    "trpx_decode_reduce": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _U, _I64, _P, _P, _P, _SZ, _P]),
+    "trpx_decode_reduce_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _U, _I64, _P, _I]),
     "trpx_encode_sparse_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _U]),
     "trpx_encode_sparse_bound_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
     "trpx_encode_sparse": (_I, [_I, _P, _P, _P, _SZ, _SZ, _SZ, _U, _P, _SZ, _P, _P, _P, _SZ, _P]),

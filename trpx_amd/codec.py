@@ -532,6 +532,57 @@ def decode_binned(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
     return out.view(n_frames, out_h, out_w), status
 
 
+REDUCE_OPS = {"max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN, "sumsq": _lib.REDUCE_SUMSQ, "count": _lib.REDUCE_COUNT_GE}
+
+
+def _reduce_op(op) -> int:
+    """op: one of "max", "min", "sumsq", "count", or the trpx_reduce_op value"""
+    if isinstance(op, str):
+        if op not in REDUCE_OPS:
+            raise ValueError(f"decode_reduce: op {op!r} (one of {', '.join(REDUCE_OPS)})")
+        return REDUCE_OPS[op]
+    if int(op) not in REDUCE_OPS.values():
+        raise ValueError(f"decode_reduce: op {op!r}")
+    return int(op)
+
+
+def reduce_out_dtype(dtype, op) -> torch.dtype:
+    """The element the op writes: the pixel type for max / min, uint64 for sumsq, uint32 for count."""
+    code = _reduce_op(op)
+    return torch.uint64 if code == _lib.REDUCE_SUMSQ else torch.uint32 if code == _lib.REDUCE_COUNT_GE else torch_dtype(dtype)
+
+
+def decode_reduce_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, group: int, op, block: int = BLOCK) -> int:
+    return lib().trpx_decode_reduce_workspace_bytes(dtype_code(torch_dtype(dtype)), _reduce_op(op), terse_bytes, n_values, n_frames, block, group)
+
+
+def decode_reduce(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, group: int, op,
+                  threshold: int = 0, out: torch.Tensor | None = None, index: torch.Tensor | None = None,
+                  workspace: Workspace | None = None, status: torch.Tensor | None = None, block: int = BLOCK):
+    """Per pixel, one statistic over ``group`` consecutive frames of a stack resident on the GPU (trpx_decode_reduce), without
+    decoding it to memory.  ``op``: "max" / "min" (elements of the pixel type), "sumsq" (uint64: the sum of squares modulo 2^64)
+    or "count" (uint32: the frames with pixel >= ``threshold``).
+
+    ``dtype`` is the stream's pixel type.  Returns (out [ceil(n_frames / group), n_values], status); every element is written;
+    asynchronous on the current stream, like ``decode_sum``.  ``frame_offsets = None``: the frames are located first;
+    ``index = None``: the decode index is built on the way."""
+    code, opc = dtype_code(torch_dtype(dtype)), _reduce_op(op)
+    odt = reduce_out_dtype(dtype, opc)
+    dev = terse.device
+    n_out = -(-n_frames // group) if group > 0 else 0
+    if out is None:
+        out = torch.empty((n_out, n_values), dtype=odt, device=dev)
+    elif out.dtype != odt or out.numel() != n_out * n_values or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_reduce: out must be a contiguous {odt} tensor of {n_out} x {n_values} elements on {dev}")
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_reduce_workspace_bytes(code, opc, terse.numel(), n_values, n_frames, block, group))
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_reduce(code, opc, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index), n_values, n_frames,
+                                       block, group, int(threshold), out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream_ptr(terse)))
+    return out, status
+
+
 def select_frames_workspace_bytes(n_frames: int, n_select: int) -> int:
     return lib().trpx_select_frames_workspace_bytes(n_frames, n_select)
 

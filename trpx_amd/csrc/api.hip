@@ -20,6 +20,7 @@
 #include "decode_bins.hpp"
 #include "decode_binned.hpp"
 #include "decode_sum.hpp"
+#include "decode_reduce.hpp"
 #include "group_runs.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -659,7 +660,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 }
 
 }  // extern "C"
-// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned -------------------
+// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce ----
 // Each reads: its own checks, the shared checks (stack_limits, consumer_ws), the front (consumer_front), its own few fields, launch.
 namespace {
 // The consumers take three input forms: index given; offsets only -- the index is built by trpx_build_index's walk; neither --
@@ -826,6 +827,12 @@ int binned_geometry(const char* fn, int dtype, int out_dtype, size_t n_values, s
         return fail(TRPX_ERR_UNSUPPORTED, "%s: %zu bins in a row (at most %u)", fn, (width + bin_x - 1) / bin_x, trpx::kBinnedAccs);
     return TRPX_OK;
 }
+
+// ---- reducing decode (decode_reduce.hip): the ops of trpx_reduce_op ---------------------------------------------------------------
+static_assert((int)TRPX_REDUCE_MAX == (int)trpx::kReduceMax && (int)TRPX_REDUCE_MIN == (int)trpx::kReduceMin &&
+              (int)TRPX_REDUCE_SUMSQ == (int)trpx::kReduceSumSq && (int)TRPX_REDUCE_COUNT_GE == (int)trpx::kReduceCountGe,
+              "reduce_ops.hpp names the values of trpx_reduce_op");
+bool reduce_op_ok(int op) { return op >= 0 && op < trpx::kReduceOps; }
 }  // namespace
 
 extern "C" {
@@ -1081,6 +1088,59 @@ int trpx_decode_binned(int dtype, int out_dtype, const uint8_t* terse, size_t te
     a.out_code = out_dtype;
     a.status = status;
     HIP_TRY(trpx::launch_decode_binned(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+// ---- reducing decode (decode_reduce.hip): trpx_decode_sum's launch plan; its scratch is [partial slab of the op's accumulators] ----
+
+size_t trpx_decode_reduce_workspace_bytes(int dtype, int op, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                          unsigned group) {
+    trpx::FrameGeom g;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && group && reduce_op_ok(op) ? front + trpx::reduce_partial_bytes(trpx::sum_plan(dtype, g, n_frames, group), op, g) : 0;
+}
+
+unsigned trpx_decode_reduce_chunks(int dtype, size_t n_values, size_t n_frames, unsigned group) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || !group || !geom_of(n_values, kBlock, &g) || !sizes_ok(g, n_frames) ||
+        !frame_bits_fit_32(dtype, n_values, kBlock))
+        return 0;
+    return trpx::sum_plan(dtype, g, n_frames, group).chunks;
+}
+
+int trpx_decode_reduce(int dtype, int op, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                       size_t n_values, size_t n_frames, unsigned block, unsigned group, int64_t threshold, void* out,
+                       uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_reduce", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {out, reduce_op_ok(op) ? trpx::reduce_out_size(op, es) : 1}, {status, 8},
+                                   {frame_offsets, 8, false}, {index, 16, false}, {workspace, 8, false}}, &g))
+        return rc;
+    if (!reduce_op_ok(op)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_reduce: unknown op %d (MAX, MIN, SUMSQ, COUNT_GE)", op);
+    if (group == 0) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_reduce: group = 0");
+    const Consumer c{"trpx_decode_reduce", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
+    const trpx::SumPlan p = trpx::sum_plan(dtype, g, n_frames, group);
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, trpx::reduce_partial_bytes(p, op, g), nullptr, &w)) return rc;   // (index given, one chunk: no workspace at all)
+    if (p.n_out * p.chunks * (uint64_t)p.tpf >= (1ull << 40)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_reduce: bad sizes");
+    // (no k_check_index behind the walk: k_reduce_tiles compares every block's header bit with its widths on the way)
+    if (const int rc = consumer_front(c, w, false, &f)) return rc;
+    trpx::ReduceArgs a{};
+    trpx::set_stack(a, f.stack);
+    a.group = group;
+    a.n_out = p.n_out;
+    a.tpf = p.tpf;
+    a.chunks = p.chunks;
+    a.fpc = p.fpc;
+    a.out = out;
+    a.threshold = threshold;
+    a.partial = p.chunks > 1 ? f.own : nullptr;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_reduce(dtype, op, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -1633,6 +1693,30 @@ int trpx_decode_binned_host(int dtype, int out_dtype, const uint8_t* terse, size
                             d.status, d.ws, ws_bytes, hs);
     if (rc || (rc = finish("trpx_decode_binned_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, binned_out, d.out, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_reduce_host(int dtype, int op, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                            size_t n_frames, unsigned block, unsigned group, int64_t threshold, void* out, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (const int rc = consumer_host_refusals("trpx_decode_reduce_host", terse && out && reduce_op_ok(op) && group, dtype, terse_bytes, n_values,
+                                              n_frames, block, &g))
+        return rc;
+    const size_t ws_bytes = trpx_decode_reduce_workspace_bytes(dtype, op, terse_bytes, n_values, n_frames, block, group);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_reduce_host: bad dtype/sizes");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_reduce_host: frames of >= 2^32 bits");
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_reduce_host", device, &hs)) return rc;
+    const size_t out_bytes = (n_frames + group - 1) / group * n_values * trpx::reduce_out_size(op, trpx_dtype_size(dtype));
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_reduce(dtype, op, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, group, threshold, d.out, d.status, d.ws,
+                            ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_reduce_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

@@ -16,23 +16,14 @@
 #include "codec_common.hpp"
 #include "decode_sum.hpp"
 #include "put_sum.hpp"
-#include "unpack_common.hpp"
-#include "unpack_tile.hpp"
+#include "sum_tile.hpp"
 #include <type_traits>
 
 namespace trpx {
 
 namespace {
 
-// 512 blocks per tile for every pixel type (k_unpack_tiles: 1024 for 8/16-bit pixels): the accumulators stay at 24 per lane
-template <typename T> constexpr int sum_sub_tiles() { return kSumSubTiles; }
-template <typename T> constexpr int sum_image_dwords() { return kSumSubTiles * ((kThreads * max_block_bits<T>() + 31) / 32) + 12; }
 template <typename T> using SumAcc = std::conditional_t<PixelTraits<T>::bits == 32, uint64_t, uint32_t>;
-template <typename T> constexpr int sum_stage_dwords() {   // LDS: the tile's stream image, reused for the sums (4 waves x 768 x 8 B)
-    return sum_image_dwords<T>() > 2 * kThreads * kBlock ? sum_image_dwords<T>() : 2 * kThreads * kBlock;
-}
-// stream dwords held in registers per lane while the previous frame is extracted (4 per load, all 256 lanes)
-template <typename T> constexpr int sum_prefetch_loads() { return (sum_image_dwords<T>() + 4 * kThreads - 1) / (4 * kThreads); }
 
 template <typename T>
 __device__ __forceinline__ int64_t acc_value(SumAcc<T> a) {
@@ -41,69 +32,10 @@ __device__ __forceinline__ int64_t acc_value(SumAcc<T> a) {
     else return (int64_t)a;
 }
 
-// The tile rule is unpack_tile.hpp's pieces; here: its steps spread over three frames.
-// what a frame's tile needs before its scan: the lanes' widths and the frame / tile positions
-template <typename T> struct SumPre {
-    uint32_t w[sum_sub_tiles<T>()], wp[sum_sub_tiles<T>()];
-    uint64_t fo, fe, t_off;
-};
-// ... and after it
-template <typename T> struct SumCur {
-    uint32_t w[sum_sub_tiles<T>()], hl[sum_sub_tiles<T>()], off[sum_sub_tiles<T>()];
-    int nb[sum_sub_tiles<T>()];
-    uint32_t tile_bits, n_dw, img_bit0;
-    uint64_t d_lo;
-};
-
-template <typename T>
-__device__ __forceinline__ void sum_load_pre(SumPre<T>& p, const uint64_t* __restrict__ frame_offsets, const FrameGeom& g,
-                                             uint64_t frame, uint32_t t, const uint8_t* __restrict__ widths,
-                                             const uint64_t* __restrict__ tile_off) {
-    constexpr int kSub = sum_sub_tiles<T>();
-    tile_load_widths<kSub>(p.w, p.wp, widths + frame * g.n_blocks, g, t);
-    // vector loads (the index in a VGPR): a scalar load in flight shares lgkmcnt with LDS, and every LDS access of the frame
-    // being extracted would wait for it
-    uint64_t fi = frame, ti = frame * g.n_tiles + (uint64_t)t * kSub;   // (walk records every 256 blocks)
-    asm volatile("" : "+v"(fi));
-    asm volatile("" : "+v"(ti));
-    p.fo = frame_offsets[fi];
-    p.fe = frame_offsets[fi + 1];
-    p.t_off = tile_off[ti];
-}
-
-// widths -> bit offsets inside the tile -> the window.  Returns false when the index does not fit the frame or the LDS image
-// (uniform over the workgroup: every lane sees the same positions and totals).
-template <typename T>
-__device__ __forceinline__ bool sum_scan(SumCur<T>& c, const SumPre<T>& p, const FrameGeom& g, uint32_t t, uint64_t terse_bytes,
-                                         uint32_t* __restrict__ s_wtot) {
-    tile_scan<sum_sub_tiles<T>()>(c.w, c.hl, c.off, c.nb, c.tile_bits,
-                                  [&](int r, uint32_t, uint32_t& w, uint32_t& w_prev) { w = p.w[r]; w_prev = p.wp[r]; }, g, t, s_wtot, lane_id(), wave_id());
-    uint64_t a0;
-    if (!tile_window(uniform64(p.fo), uniform64(p.fe), uniform64(p.t_off), c.tile_bits, terse_bytes, a0, c.d_lo, c.n_dw)) return false;
-    c.img_bit0 = tile_img_bit0(a0, c.d_lo);
-    return c.n_dw <= (uint32_t)(sum_image_dwords<T>() - 8);   // (widths above the type's: more bits than the image holds)
-}
-
-template <typename T>
-__device__ __forceinline__ void sum_fetch(uint4 (&R)[sum_prefetch_loads<T>()], const SumCur<T>& c, const uint8_t* __restrict__ terse,
-                                          uint64_t terse_bytes) {
-#pragma unroll
-    for (int k = 0; k < sum_prefetch_loads<T>(); ++k) {
-        const uint32_t i = threadIdx.x * 4 + k * kThreads * 4;
-        if (i < c.n_dw) R[k] = tile_fetch16(c.d_lo, i, terse, terse_bytes);
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void sum_stage(uint32_t* __restrict__ s_image, const uint4 (&R)[sum_prefetch_loads<T>()], uint32_t n_dw) {
-#pragma unroll
-    for (int k = 0; k < sum_prefetch_loads<T>(); ++k) {
-        const uint32_t i = threadIdx.x * 4 + k * kThreads * 4;
-        if (i < n_dw) *reinterpret_cast<uint4*>(&s_image[i]) = R[k];
-    }
-}
-
+// (the walk's pieces -- load, scan, fetch, stage: sum_tile.hpp, shared with decode_reduce.hip)
 // The frame's fields from the LDS image, added to the lane's accumulators.  Returns false for a width above the type's.
+// (sum_tile.hpp's sum_fields is this text as a function; called here it changes how k_sum_tiles' checks are scheduled, so the
+// kernel keeps the text it was measured with)
 template <typename T>
 __device__ __forceinline__ bool sum_extract(SumAcc<T> (&acc)[sum_sub_tiles<T>()][kBlock], const SumCur<T>& c,
                                             const uint32_t* __restrict__ s_image) {

@@ -245,6 +245,29 @@ class Terse:
                                          f, self._block, group, out.ctypes.data, self._device))
         return out
 
+    def prolix_reduce(self, op: str, group: int | None = None, threshold: int = 0) -> np.ndarray:
+        """Per pixel, one statistic over ``group`` consecutive frames (``None``: all frames) in ONE GPU call
+        (trpx_decode_reduce_host), without decoding the stack to memory.  ``op``: ``"max"`` / ``"min"`` (elements of the
+        narrowest integer type that holds the object's values), ``"sumsq"`` (uint64: the sum of squares modulo 2^64; with
+        ``prolix_sum`` the per-pixel variance) or ``"count"`` (uint32: the frames with pixel >= ``threshold``).  Returns
+        [ceil(number_of_frames / group), size]."""
+        ops = {"max": _lib.REDUCE_MAX, "min": _lib.REDUCE_MIN, "sumsq": _lib.REDUCE_SUMSQ, "count": _lib.REDUCE_COUNT_GE}
+        if op not in ops:
+            raise ValueError(f"prolix_reduce: op {op!r} (one of {', '.join(ops)})")
+        f = self.number_of_frames()
+        if group is None:
+            group = f
+        if f and group < 1:
+            raise ValueError("group must be >= 1")
+        code, dt = self._stream_type("prolix_reduce")
+        out = np.empty((-(-f // group) if f else 0, self._size), {"sumsq": np.dtype(np.uint64), "count": np.dtype(np.uint32)}.get(op, dt))
+        if f == 0:
+            return out
+        buf, offs = self._stream_and_offsets()
+        check(lib().trpx_decode_reduce_host(code, ops[op], buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f, self._block,
+                                            group, int(threshold), out.ctypes.data, self._device))
+        return out
+
     def _stream_and_offsets(self):
         """The stream and its frame offsets as the host entry points take them: (uint8 array, uint64 [frames + 1])."""
         return np.frombuffer(self._data, np.uint8), np.concatenate([[0], np.cumsum(self._frame_sizes)]).astype(np.uint64)
