@@ -212,6 +212,30 @@ public:
                                            (unsigned)group, out, -1), "Terse::prolix_sum");
     }
 
+    /// Sums of the frames that carry the same label into `out` (n_out x size() values) in one device call, without expanding the
+    /// frames (trpx_decode_sum_labelled_host).  labels: number_of_frames() of them; frame f is added into output labels[f], a label
+    /// >= n_out (by convention 0xFFFFFFFF) takes the frame out of every sum.  An output without frames is 0.  counts: n_out values,
+    /// the frames of every output, or nullptr.  V and the refusals: prolix_sum's.  An object without frames writes nothing.
+    template <typename V>
+    void prolix_sum_labelled(V* out, const std::uint32_t* labels, std::size_t n_out, std::uint32_t* counts = nullptr) {
+        static_assert(std::is_same_v<V, std::int32_t> || std::is_same_v<V, std::uint32_t> || std::is_same_v<V, std::int64_t> ||
+                          std::is_same_v<V, std::uint64_t> || std::is_same_v<V, float> || std::is_same_v<V, double>,
+                      "prolix_sum_labelled: int32, uint32, int64, uint64, float or double sums");
+        if (d_signed && std::is_unsigned_v<V>)
+            throw std::invalid_argument("signed data cannot be decompressed into unsigned data");
+        if (n_out == 0) throw std::invalid_argument("prolix_sum_labelled: n_out must be at least 1");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_sum_labelled: values of more than 32 bits are not supported");
+        if (d_frame_sizes.empty()) return;
+        if (!labels) throw std::invalid_argument("prolix_sum_labelled: no labels");
+        detail::require_abi();
+        std::vector<std::uint64_t> offs(d_frame_sizes.size() + 1, 0);
+        for (std::size_t f = 0; f < d_frame_sizes.size(); ++f) offs[f + 1] = offs[f] + d_frame_sizes[f];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_sum_labelled_host(bits + (d_signed ? 1 : 0), detail::out_dtype_of<V>(), d_terse_data.data(),
+                                                    d_terse_data.size(), offs.data(), d_size, d_frame_sizes.size(), d_block, labels,
+                                                    n_out, out, counts, -1), "Terse::prolix_sum_labelled");
+    }
+
     /// Per pixel, one statistic over `group` consecutive frames into `out` (ceil(number_of_frames() / group) x size() values) in
     /// one device call, without expanding the frames (trpx_decode_reduce_host).  op: TRPX_REDUCE_MAX / TRPX_REDUCE_MIN -- V is the
     /// narrowest integer type that holds the object's values ((u)int8_t for bits_per_val() <= 8, (u)int16_t for <= 16, (u)int32_t

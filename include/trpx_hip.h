@@ -53,8 +53,8 @@ typedef enum trpx_status {
  * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
  *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
- *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned and trpx_decode_reduce where they build the
- *     index themselves (no index given) -- and their _host forms;
+ *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce and
+ *     trpx_decode_sum_labelled where they build the index themselves (no index given) -- and their _host forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -585,6 +585,58 @@ int trpx_decode_reduce(int dtype, int op, const uint8_t* terse, size_t terse_byt
                        uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 int trpx_decode_reduce_host(int dtype, int op, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                             size_t n_frames, unsigned block, unsigned group, int64_t threshold, void* out, int device);
+
+/*
+ * Labelled summing decode: the sum of the frames that carry the same label, one label per frame, straight from the stream and its
+ * decode index, without writing the decoded frames -- trpx_decode_sum for frames that do not lie next to each other: the
+ * real-space binning of a scan, the mean pattern of every cluster of scan positions, the sum of the hits alone.  The transpose of
+ * trpx_decode_bins (one label per pixel).
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32
+ *   out_dtype      as trpx_decode_sum: TRPX_I32 / TRPX_U32 (clamped), TRPX_I64 / TRPX_U64 (exact), TRPX_F32 / TRPX_F64 (the exact
+ *                  integer sum rounded once to nearest even); a signed stream into U32 / U64 is TRPX_ERR_UNSUPPORTED
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_sum: index given -- validated against the frame sizes as in
+ *                  trpx_decode_indexed; offsets only -- the index is built in the workspace by trpx_build_index's walk; offsets NULL
+ *                  -- the frames are located in the workspace first.  workspace: DEVICE, 8-byte aligned, NEVER NULL (the order
+ *                  of the frames lives there), >= trpx_decode_sum_labelled_workspace_bytes() (the need with offsets and index both
+ *                  NULL; the call checks against what its own form needs).  Own scratch: 16 bytes per output, 8 per frame, and two
+ *                  frames' worth of raw accumulators for each of at most about 1024 chunks of the ordered frames
+ *   labels         DEVICE const uint32_t[n_frames], 4-byte aligned.  labels[f] < n_out: frame f is added into output labels[f];
+ *                  labels[f] >= n_out: frame f takes part in nothing (0xFFFFFFFF is the conventional mask) -- legal, not an error.
+ *                  A device array on purpose: a captured graph is replayed with new labels in the same buffer, and nothing that
+ *                  depends on the labels' contents is decided on the host
+ *   n_out          1 .. 2^20 outputs (above: TRPX_ERR_UNSUPPORTED); may exceed n_frames
+ *   sums_out       DEVICE [n_out][n_values] of out_dtype, compact, aligned to its element type only.  EVERY element is written by
+ *                  every successful call, an output without frames is 0: the caller clears nothing
+ *   counts_out     DEVICE uint32_t[n_out] or NULL: the frames of every output (for means)
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS]; word 0 = TRPX_ERR_CORRUPT in the cases of trpx_decode_sum, for the frames that
+ *                  have an output.  A MASKED FRAME IS NEVER READ AND NEVER VALIDATED: status 0 says nothing about it.  With index ==
+ *                  NULL trpx_build_index's verdict on the whole stack is reported (masked frames and valid streams with restated
+ *                  widths included).  After a non-zero status the outputs are unspecified
+ * Integer accumulation, no float atomics: bit-identical across runs, input forms, label orders and launch shapes.  Nothing outside
+ * terse[0 .. align4(terse_bytes)), labels[0 .. n_frames), the offsets and the index is read; nothing outside sums_out, counts_out,
+ * status and the workspace is written, whatever the labels hold.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL; labels[0] is frame a's.
+ * Errors returned before any device call, in trpx_decode_sum's order: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers,
+ * frames of >= 2^32 bits, a signed stream into an unsigned output, n_out > 2^20; TRPX_ERR_INVALID_ARG for an unknown or float
+ * dtype, an out_dtype that is none of the six, n_out 0, bad sizes, null or misaligned pointers (labels included), an index without
+ * offsets, a NULL workspace; TRPX_ERR_CAPACITY for a workspace that is too small for the call's own form.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape and split is decided
+ * on the host from n_frames, n_values, n_out and dtype alone.  trpx_decode_sum_labelled_frames_per_chunk: the length of the
+ * chunks the ordered frames are cut into -- pure arithmetic, for tests and diagnostics (0 for sizes no call takes).
+ * trpx_decode_sum_labelled_host: host terse / frame_offsets (or NULL) / labels / sums_out / counts_out (or NULL); checks its
+ * arguments before a device is looked for, stages, calls trpx_decode_sum_labelled and synchronises.
+ */
+size_t trpx_decode_sum_labelled_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                                size_t n_out);
+unsigned trpx_decode_sum_labelled_frames_per_chunk(int dtype, size_t n_values, size_t n_frames);
+int trpx_decode_sum_labelled(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                             const void* index, size_t n_values, size_t n_frames, unsigned block, const uint32_t* labels, size_t n_out,
+                             void* sums_out, uint32_t* counts_out, uint32_t* status, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int trpx_decode_sum_labelled_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                                  size_t n_values, size_t n_frames, unsigned block, const uint32_t* labels, size_t n_out,
+                                  void* sums_out, uint32_t* counts_out, int device);
 
 /*
  * Encode from events: the stream of a stack given in CSR form -- what trpx_decode_sparse writes, what a counting detector or a

@@ -80,6 +80,10 @@ SYMBOLS = {
     "trpx_decode_reduce_chunks": (_U, [_I, _SZ, _SZ, _U]),
     "trpx_decode_reduce": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _U, _I64, _P, _P, _P, _SZ, _P]),
     "trpx_decode_reduce_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _U, _I64, _P, _I]),
+    "trpx_decode_sum_labelled_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U, _SZ]),
+    "trpx_decode_sum_labelled_frames_per_chunk": (_U, [_I, _SZ, _SZ]),
+    "trpx_decode_sum_labelled": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _P, _SZ, _P, _P, _P, _P, _SZ, _P]),
+    "trpx_decode_sum_labelled_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _P, _SZ, _P, _P, _I]),
     "trpx_encode_sparse_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _U]),
     "trpx_encode_sparse_bound_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
     "trpx_encode_sparse": (_I, [_I, _P, _P, _P, _SZ, _SZ, _SZ, _U, _P, _SZ, _P, _P, _P, _SZ, _P]),

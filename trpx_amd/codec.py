@@ -583,6 +583,45 @@ def decode_reduce(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
     return out, status
 
 
+def decode_sum_labelled_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, n_out: int, block: int = BLOCK) -> int:
+    return lib().trpx_decode_sum_labelled_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block, n_out)
+
+
+def decode_sum_labelled(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype,
+                        labels: torch.Tensor, n_out: int, out_dtype=torch.int32, out: torch.Tensor | None = None,
+                        counts: torch.Tensor | None = None, index: torch.Tensor | None = None,
+                        workspace: Workspace | None = None, status: torch.Tensor | None = None, block: int = BLOCK):
+    """Sums of the frames that carry the same label, of a stack resident on the GPU (trpx_decode_sum_labelled), without decoding
+    it to memory.  ``labels``: one uint32 (or int32, read as uint32: -1 is the mask) per frame, on the device; frame f is added
+    into output ``labels[f]``, a label >= ``n_out`` takes the frame out of every sum and it is not read.
+
+    ``dtype`` is the stream's pixel type; ``out_dtype`` one of int32, uint32, int64, uint64, float32, float64.  Returns
+    (sums [n_out, n_values], status); every element is written, an output without frames is 0.  ``counts``: a uint32 (or
+    int32) tensor of n_out elements that receives the frames per output.  Asynchronous on the current stream, like
+    ``decode_sum``.  ``frame_offsets = None``: the frames are located first; ``index = None``: the decode index is built on the way."""
+    odt = torch_dtype(out_dtype)
+    if odt not in _SUM_OUT:
+        raise TypeError(f"decode_sum_labelled: out_dtype {odt} (int32, uint32, int64, uint64, float32, float64)")
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    words = (torch.uint32, torch.int32)
+    if labels.dtype not in words or labels.numel() != n_frames or not labels.is_contiguous() or labels.device != dev:
+        raise ValueError(f"decode_sum_labelled: labels must be a contiguous uint32 / int32 tensor of {n_frames} elements on {dev}")
+    if counts is not None and (counts.dtype not in words or counts.numel() != n_out or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"decode_sum_labelled: counts must be a contiguous uint32 / int32 tensor of {n_out} elements on {dev}")
+    if out is None:
+        out = torch.empty((max(n_out, 0), n_values), dtype=odt, device=dev)
+    elif out.dtype != odt or out.numel() != n_out * n_values or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_sum_labelled: out must be a contiguous {odt} tensor of {n_out} x {n_values} elements on {dev}")
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_sum_labelled_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_out))
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_sum_labelled(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
+                                             n_values, n_frames, block, labels.data_ptr(), n_out, out.data_ptr(), _ptr(counts),
+                                             status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+    return out, status
+
+
 def select_frames_workspace_bytes(n_frames: int, n_select: int) -> int:
     return lib().trpx_select_frames_workspace_bytes(n_frames, n_select)
 

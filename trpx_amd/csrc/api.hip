@@ -21,6 +21,7 @@
 #include "decode_binned.hpp"
 #include "decode_sum.hpp"
 #include "decode_reduce.hpp"
+#include "decode_sum_labelled.hpp"
 #include "group_runs.hpp"
 #include "launchers.hpp"
 #include "profile.hpp"
@@ -660,7 +661,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 }
 
 }  // extern "C"
-// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce ----
+// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce, trpx_decode_sum_labelled ----
 // Each reads: its own checks, the shared checks (stack_limits, consumer_ws), the front (consumer_front), its own few fields, launch.
 namespace {
 // The consumers take three input forms: index given; offsets only -- the index is built by trpx_build_index's walk; neither --
@@ -833,6 +834,9 @@ static_assert((int)TRPX_REDUCE_MAX == (int)trpx::kReduceMax && (int)TRPX_REDUCE_
               (int)TRPX_REDUCE_SUMSQ == (int)trpx::kReduceSumSq && (int)TRPX_REDUCE_COUNT_GE == (int)trpx::kReduceCountGe,
               "reduce_ops.hpp names the values of trpx_reduce_op");
 bool reduce_op_ok(int op) { return op >= 0 && op < trpx::kReduceOps; }
+
+// ---- labelled summing decode (decode_sum_labelled.hip) -----------------------------------------------------------------------------
+bool labelled_out_ok(size_t n_out) { return n_out >= 1 && n_out <= trpx::kLabelledMaxOut; }
 }  // namespace
 
 extern "C" {
@@ -1141,6 +1145,74 @@ int trpx_decode_reduce(int dtype, int op, const uint8_t* terse, size_t terse_byt
     a.partial = p.chunks > 1 ? f.own : nullptr;
     a.status = status;
     HIP_TRY(trpx::launch_decode_reduce(dtype, op, a, f.clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+// ---- labelled summing decode (decode_sum_labelled.hip): its scratch is LabelledPlan's -- the frames' order and the partial slab ----
+
+size_t trpx_decode_sum_labelled_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                                size_t n_out) {
+    trpx::FrameGeom g;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && labelled_out_ok(n_out) ? front + trpx::labelled_plan(dtype, g, n_frames, n_out).total : 0;
+}
+
+unsigned trpx_decode_sum_labelled_frames_per_chunk(int dtype, size_t n_values, size_t n_frames) {
+    trpx::FrameGeom g;
+    if (dtype < TRPX_U8 || dtype > TRPX_I32 || !geom_of(n_values, kBlock, &g) || !sizes_ok(g, n_frames) ||
+        !frame_bits_fit_32(dtype, n_values, kBlock))
+        return 0;
+    return trpx::labelled_plan(dtype, g, n_frames, 1).fpc;
+}
+
+// (trpx_decode_sum's order of checks, the outputs' count where its group stands)
+int trpx_decode_sum_labelled(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                             const void* index, size_t n_values, size_t n_frames, unsigned block, const uint32_t* labels, size_t n_out,
+                             void* sums_out, uint32_t* counts_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* const fn = "trpx_decode_sum_labelled";
+    trpx::FrameGeom g;
+    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "%s: no decode index for 64-bit containers", fn);
+    if (dtype < TRPX_U8 || dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "%s: unknown stream dtype %d", fn, dtype);
+    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "%s: out_dtype %d (I32, U32, I64, U64, F32, F64)", fn, out_dtype);
+    if (block != kBlock) return fail(TRPX_ERR_UNSUPPORTED, "%s: block=%u (the decode index needs 12)", fn, block);
+    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
+        return fail(TRPX_ERR_UNSUPPORTED, "%s: signed stream into an unsigned output (Terse.hpp:356-357)", fn);
+    if (n_out == 0) return fail(TRPX_ERR_INVALID_ARG, "%s: n_out = 0", fn);
+    if (!labelled_out_ok(n_out)) return fail(TRPX_ERR_UNSUPPORTED, "%s: n_out=%zu (at most 2^20)", fn, n_out);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0 || n_frames > terse_bytes)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", fn, n_values, n_frames);
+    if (!terse || !labels || !sums_out || !status) return fail(TRPX_ERR_INVALID_ARG, "%s: null pointer", fn);
+    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "%s: an index needs its frame offsets", fn);
+    if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 || (uintptr_t)workspace % 8 ||
+        (uintptr_t)labels % 4 || (uintptr_t)counts_out % 4 || (uintptr_t)sums_out % sum_out_size(out_dtype))
+        return fail(TRPX_ERR_INVALID_ARG, "%s: misaligned pointer (terse / labels / counts 4 B, offsets / workspace 8 B, index 16 B, sums their type)", fn);
+    const Consumer c{fn, dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace, workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
+    const trpx::LabelledPlan p = trpx::labelled_plan(dtype, g, n_frames, n_out);
+    IndexWs w;
+    if (const int rc = consumer_ws(c, p.total, "the order of the frames lives there", &w)) return rc;
+    Front f;
+    // (no k_check_index behind the walk: k_sum_labelled compares every block's header bit with its widths on the way)
+    if (const int rc = consumer_front(c, w, false, &f)) return rc;
+    trpx::LabelledArgs a{};
+    trpx::set_stack(a, f.stack);
+    a.n_out = (uint32_t)n_out;
+    a.tpf = p.tpf;
+    a.n_chunks = p.n_chunks;
+    a.fpc = p.fpc;
+    a.labels = labels;
+    a.out = sums_out;
+    a.out_code = out_dtype;
+    a.counts_out = counts_out;
+    a.counts = reinterpret_cast<uint32_t*>(f.own + p.counts);
+    a.cursor = reinterpret_cast<uint32_t*>(f.own + p.cursor);
+    a.starts = reinterpret_cast<uint32_t*>(f.own + p.starts);
+    a.todo = reinterpret_cast<uint32_t*>(f.own + p.todo);
+    a.order = reinterpret_cast<uint2*>(f.own + p.order);
+    a.partial = f.own + p.slab;
+    a.stride = p.stride;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_sum_labelled(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -1717,6 +1789,40 @@ int trpx_decode_reduce_host(int dtype, int op, const uint8_t* terse, size_t ters
                             ws_bytes, hs);
     if (rc || (rc = finish("trpx_decode_reduce_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, out, d.out, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_sum_labelled_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                                  size_t n_values, size_t n_frames, unsigned block, const uint32_t* labels, size_t n_out, void* sums_out,
+                                  uint32_t* counts_out, int device) {
+    // (the argument checks need no device: they come first)
+    const char* const fn = "trpx_decode_sum_labelled_host";
+    trpx::FrameGeom g;
+    if (const int rc = consumer_host_refusals(fn, terse && labels && sums_out && sum_out_ok(out_dtype) && n_out, dtype, terse_bytes, n_values, n_frames,
+                                              block, &g))
+        return rc;
+    if (!labelled_out_ok(n_out)) return fail(TRPX_ERR_UNSUPPORTED, "%s: n_out=%zu (at most 2^20)", fn, n_out);
+    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
+        return fail(TRPX_ERR_UNSUPPORTED, "%s: signed stream into an unsigned output (Terse.hpp:356-357)", fn);
+    const size_t ws_bytes = trpx_decode_sum_labelled_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_out);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "%s: bad dtype/sizes", fn);
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "%s: frames of >= 2^32 bits", fn);
+    hipStream_t hs = nullptr;
+    if (const int rc = enter(fn, device, &hs)) return rc;
+    // the labels, the sums and the counts in one device block: [labels] [sums] [counts]
+    const size_t l_bytes = 4 * n_frames, out_at = trpx::align_up(l_bytes, 16), out_bytes = n_out * n_values * sum_out_size(out_dtype);
+    const size_t counts_at = out_at + trpx::align_up(out_bytes, 8), counts_bytes = 4 * n_out;
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, counts_at + counts_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    char* o = static_cast<char*>(d.out);
+    HIP_TRY(copy_sync(hs, o, labels, l_bytes, hipMemcpyHostToDevice));
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_sum_labelled(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const uint32_t*>(o),
+                                  n_out, o + out_at, reinterpret_cast<uint32_t*>(o + counts_at), d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish(fn, hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, sums_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
+    if (counts_out) HIP_TRY(copy_sync(hs, counts_out, o + counts_at, counts_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

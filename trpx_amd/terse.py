@@ -245,6 +245,34 @@ class Terse:
                                          f, self._block, group, out.ctypes.data, self._device))
         return out
 
+    def prolix_sum_labelled(self, labels, n_out: int | None = None, dtype=np.int64, return_counts: bool = False):
+        """Sums of the frames that carry the same label in ONE GPU call (trpx_decode_sum_labelled_host), without decoding the
+        stack to memory.  ``labels``: one unsigned 32-bit label per frame; frame f is added into output ``labels[f]``, a label
+        >= ``n_out`` (by convention 2^32 - 1) takes the frame out of every sum.  ``n_out`` defaults to the largest label below
+        2^32 - 1, plus one.  Returns [n_out, size] of ``dtype`` (int32 / uint32 clamp, int64 / uint64 exact, float32 / float64
+        rounded once), an output without frames is 0; with ``return_counts`` also the frames per output (uint32 [n_out])."""
+        f = self.number_of_frames()
+        lab = np.asarray(labels)
+        if lab.shape != (f,) or lab.dtype.kind not in "iu" or (lab.size and (lab.min() < 0 or lab.max() > 0xFFFFFFFF)):
+            raise ValueError(f"prolix_sum_labelled: labels must be {f} integers in [0, 2^32)")
+        lab = np.ascontiguousarray(lab, np.uint32)
+        if n_out is None:
+            kept = lab[lab != 0xFFFFFFFF]
+            n_out = int(kept.max()) + 1 if kept.size else 1
+        if n_out < 1:
+            raise ValueError("n_out must be >= 1")
+        if self._signed and np.dtype(dtype).kind == "u":
+            raise ValueError("signed data cannot be decompressed into unsigned data")            # Terse.hpp:356-357
+        stream, _ = self._stream_type("prolix_sum_labelled")
+        out = np.zeros((n_out, self._size), np.dtype(dtype))
+        counts = np.zeros(n_out, np.uint32)
+        if f:
+            buf, offs = self._stream_and_offsets()
+            check(lib().trpx_decode_sum_labelled_host(stream, _code(dtype, True), buf.ctypes.data, buf.size, offs.ctypes.data, self._size,
+                                                      f, self._block, lab.ctypes.data, n_out, out.ctypes.data, counts.ctypes.data,
+                                                      self._device))
+        return (out, counts) if return_counts else out
+
     def prolix_reduce(self, op: str, group: int | None = None, threshold: int = 0) -> np.ndarray:
         """Per pixel, one statistic over ``group`` consecutive frames (``None``: all frames) in ONE GPU call
         (trpx_decode_reduce_host), without decoding the stack to memory.  ``op``: ``"max"`` / ``"min"`` (elements of the
