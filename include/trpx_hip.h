@@ -78,6 +78,20 @@ enum { TRPX_STATUS_WORDS = 8 };
 /*   word 0: 0 = ok, else a trpx_status (CAPACITY / CORRUPT) detected on the device
  *   word 1: prolix_bits of this call (max significant bits over all blocks, Terse.hpp:516)   */
 
+/* Size limits of one call.  A frame is cut into tiles of 256 blocks (3072 values at block 12): tiles = ceil(ceil(n_values /
+ * block) / 256).  Every device entry point takes
+ *   - n_frames * tiles <= TRPX_MAX_TILES_PER_CALL = 2^24 - 1: the hot kernels start one workgroup of 256 threads per tile, or one
+ *     wavefront per frame, and the device launches no grid of 2^32 threads or more.  That is 195 083 frames of 512 x 512
+ *     (51 G values), but only 16 777 215 frames of a single tile.  A larger stack is TRPX_ERR_UNSUPPORTED, decided before the
+ *     first device call, never a TRPX_ERR_HIP of a launch: split the stack (frames are independent; trpx_select_frames moves
+ *     bytes only and is under the same limit for its source);
+ *   - n_values * n_frames * 8 < 2^62 bytes and at most 2^32 - 1 blocks a frame (otherwise TRPX_ERR_INVALID_ARG);
+ *   - a frame whose worst case is 0xF0000000 bits or more (about 122 M values of 32 bits) decodes and encodes, on the routes
+ *     that need no 32-bit position inside the frame; trpx_build_index and the consumers of a decode index (trpx_decode_sum ..
+ *     trpx_decode_sum_labelled) answer TRPX_ERR_UNSUPPORTED.
+ * The host entry points (_host) pass a stack to the device entry points and answer what those answer. */
+#define TRPX_MAX_TILES_PER_CALL 0xFFFFFFu
+
 int         trpx_abi_version(void);
 const char* trpx_last_error_string(void);
 size_t      trpx_dtype_size(int dtype);          /* 0 for an unknown dtype */

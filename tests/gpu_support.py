@@ -16,7 +16,11 @@ consumer's data.
   * assert_round_trip: status 0 and the pixels back, byte for byte;
   * host_encode / host_decode: trpx_encode_host / trpx_decode_host on numpy arrays, into poisoned buffers;
   * fuzz_stack, ALL_DTYPES, ROUTES: the width patterns, pixel types and forced decode routes of the route tests;
-  * run_case / run_variant: a program of tests/variant_cases/ in a child python, on the product or on a test build of the library.
+  * run_case / run_variant: a program of tests/variant_cases/ in a child python, on the product or on a test build of the library;
+  * large stacks (tests/test_gpu_large_stacks.py): crossing_frames picks the frames around a boundary of a running total,
+    assert_stream_is_chunks compares a stack with the concatenation of encodes of its chunks, DeviceGuarded is Guarded for outputs
+    too large for the host, wide / frame_chunks / ConsumerSpec / consumer_truths are every consumer written with plain torch in
+    int64, chunk by chunk, from the pixels; need_device_memory fails (never skips) where the device has too little free.
 
 No fixtures, no library at import; everything but encode(), the host_ calls and the child programs works on CPU tensors:
 tests/test_gpu_support_model.py and tests/test_support_checks_model.py run it there and show that each check can fail."""
@@ -352,3 +356,167 @@ def fuzz_stack(rng, dt, kind, n, frames):
     if dt.kind == "i":
         mag = mag * rng.choice([-1, 1], size=mag.shape)
     return mag.astype(dt)
+
+
+# ---- large stacks: the frames around a boundary, chunk-wise encodes, guarded outputs on the device, torch truths ---------------------
+def need_device_memory(need: int, what: str):
+    """Fails -- never skips -- where the device has less than `need` bytes free (after handing torch's cache back)."""
+    import torch
+    torch.cuda.empty_cache()
+    free = torch.cuda.mem_get_info()[0]
+    assert free >= need, f"{what} needs {need / 2 ** 30:.1f} GiB of device memory, {free / 2 ** 30:.1f} GiB are free"
+
+
+def crossing_frames(offs, boundaries):
+    """offs [n + 1]: what lies in front of every frame (bytes, bits, values), tensor or array.  Returns ({boundary: the frame k
+    that holds it, offs[k] <= boundary < offs[k + 1]}, the frames to sample: the first, the last and k - 1, k, k + 1 of every
+    boundary).  A boundary the stack does not reach is an error: a test of a crossing must not pass without one."""
+    o = (offs if isinstance(offs, np.ndarray) else to_np(offs)).astype(np.int64)
+    n = o.size - 1
+    at, picks = {}, {0, n - 1}
+    for b in boundaries:
+        assert o[0] <= b < o[-1], f"boundary {b} is not crossed: the stack ends at {int(o[-1])}"
+        k = int(np.searchsorted(o, b, side="right")) - 1
+        at[b] = k
+        picks.update(f for f in (k - 1, k, k + 1) if 0 <= f < n)
+    return at, sorted(picks)
+
+
+def _i64(x):
+    if isinstance(x, np.ndarray):
+        return x.astype(np.int64)
+    import torch
+    return x.view(torch.int64) if str(x.dtype) == "torch.uint64" else x.to(torch.int64)
+
+
+def assert_stream_is_chunks(stream, offs, n_frames, encode_chunk, chunk=256, ctx=""):
+    """Frames are independent and start on a byte: `stream` with offsets `offs` [n_frames + 1] must be, byte for byte, what
+    encode_chunk(f0, f1) -> (bytes, offsets [f1 - f0 + 1]) gives for the frames [f0, f1) of every chunk of `chunk` frames, one
+    behind the other, and `offs` the running sums.  Tensors (compared where they are) or arrays."""
+    assert int(offs[0]) == 0 and offs.shape[0] == n_frames + 1, (ctx, "offsets")
+    at = 0
+    for f0 in range(0, n_frames, chunk):
+        f1 = min(f0 + chunk, n_frames)
+        cs, co = encode_chunk(f0, f1)
+        co = _i64(co)
+        assert int(co[0]) == 0 and co.shape[0] == f1 - f0 + 1, (ctx, "chunk offsets", f0)
+        assert _same(_i64(offs[f0:f1 + 1]), co + at), (ctx, f"offsets of frames {f0}..{f1} are not the running sums", at)
+        size = int(co[-1])
+        assert at + size <= stream.shape[0], (ctx, f"the stream ends inside frames {f0}..{f1}")
+        assert _same(stream[at:at + size], cs[:size]), (ctx, f"bytes of frames {f0}..{f1} (from byte {at}) differ")
+        at += size
+    assert at == int(offs[n_frames]) == stream.shape[0], (ctx, "total", at, int(offs[n_frames]), stream.shape[0])
+
+
+class DeviceGuarded:
+    """Guarded for an output too large to build or to check on the host: `view` has `shape` and type `tdt` (a torch dtype), with
+    GUARD elements on either side, every byte of the allocation 0xA5 until something writes it; checked where it lies."""
+    BYTE = 0xA5
+
+    def __init__(self, shape, tdt, device="cuda"):
+        import torch
+        self.n = int(np.prod(shape))
+        self.whole = torch.empty(self.n + 2 * GUARD, dtype=tdt, device=device)
+        self.view = self.whole[GUARD:GUARD + self.n].view(shape)
+        self.poison()
+
+    def poison(self):
+        import torch
+        self.whole.view(torch.uint8).fill_(self.BYTE)
+
+    def check(self, what: str):
+        import torch
+        lo, hi = self.whole[:GUARD].view(torch.uint8), self.whole[GUARD + self.n:].view(torch.uint8)
+        assert bool((lo == self.BYTE).all()) and bool((hi == self.BYTE).all()), f"written outside {what}"
+        return self.view
+
+
+def wide(x):
+    """An integer tensor as int64 with the same values (torch has few operators for the unsigned wide types)."""
+    import torch
+    name = str(x.dtype)
+    if name == "torch.uint16":
+        return x.view(torch.int16).to(torch.int64) & 0xFFFF
+    if name == "torch.uint32":
+        return x.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    if name == "torch.uint64":
+        return x.view(torch.int64)                          # (the same bits: equal where the values are)
+    return x.to(torch.int64)
+
+
+def signed_view(x):
+    """The same bits as the signed type of the same size (for torch.where and friends on the unsigned wide types)"""
+    import torch
+    return x.view({"torch.uint16": torch.int16, "torch.uint32": torch.int32, "torch.uint64": torch.int64}.get(str(x.dtype), x.dtype))
+
+
+def keep_from(x, threshold):
+    """x with every value below `threshold` set to 0: the frames whose events trpx_decode_sparse returns at that threshold"""
+    import torch
+    s = signed_view(x)
+    return torch.where(wide(x) >= threshold, s, torch.zeros_like(s)).view(x.dtype)
+
+
+same_bytes = _same
+
+
+def frame_chunks(f0, f1, n_values, elems=1 << 25):
+    """[f0, f1) in runs of frames of at most `elems` values (one int64 copy of a run: 8 * elems bytes)"""
+    step = max(1, elems // n_values)
+    for a in range(f0, f1, step):
+        yield a, min(a + step, f1)
+
+
+class ConsumerSpec:
+    """What the consumers of one large-stack test are asked: group (trpx_decode_sum / _reduce), frame_labels int64 [frames] with
+    n_out (a label outside 0 .. n_out - 1 masks the frame; _sum_labelled), weights int64 [K, n_values] (_dot), pixel_labels int64
+    [n_values] with n_bins (_bins), width and bin = (bin_y, bin_x) (_binned), threshold (_sparse)."""
+
+    def __init__(self, group, frame_labels, n_out, weights, pixel_labels, n_bins, width, bin, threshold):
+        self.group, self.frame_labels, self.n_out, self.weights = group, frame_labels, n_out, weights
+        self.pixel_labels, self.n_bins, self.width, self.bin, self.threshold = pixel_labels, n_bins, width, bin, threshold
+
+
+def consumer_truths(px, spec, elems=1 << 25):
+    """Every consumer from the pixels px [frames, n_values], in int64 on px's device, a run of frames at a time: a dict of
+      sum, max, sumsq [ceil(frames / group), n_values] (sumsq modulo 2^64, as int64 bits);
+      labelled [n_out, n_values], counts [n_out];  dot [frames, K];  bins [frames, n_bins];  binned [frames, oh, ow];
+      rows [frames + 1], positions, values: the events with value >= threshold, by frame and ascending position."""
+    import torch
+    F, n = px.shape
+    dev, i64 = px.device, torch.int64
+    g, by, bx = spec.group, spec.bin[0], spec.bin[1]
+    W = spec.width
+    H = n // W
+    oh, ow = -(-H // by), -(-W // bx)
+    n_g = -(-F // g)
+    t = dict(sum=torch.zeros((n_g, n), dtype=i64, device=dev), max=torch.full((n_g, n), -2 ** 63, dtype=i64, device=dev),
+             sumsq=torch.zeros((n_g, n), dtype=i64, device=dev), labelled=torch.zeros((spec.n_out, n), dtype=i64, device=dev),
+             counts=torch.zeros(spec.n_out, dtype=i64, device=dev), dot=torch.zeros((F, spec.weights.shape[0]), dtype=i64, device=dev),
+             bins=torch.zeros((F, spec.n_bins), dtype=i64, device=dev), binned=torch.zeros((F, oh, ow), dtype=i64, device=dev))
+    rows, pos, val = [torch.zeros(1, dtype=i64, device=dev)], [], []
+    for j in range(n_g):
+        for a, b in frame_chunks(j * g, min((j + 1) * g, F), n, elems):
+            x = wide(px[a:b])
+            t["sum"][j] += x.sum(0)
+            t["max"][j] = torch.maximum(t["max"][j], x.amax(0))
+            t["sumsq"][j] += (x * x).sum(0)
+            lab = spec.frame_labels[a:b]
+            ok = (lab >= 0) & (lab < spec.n_out)
+            t["labelled"].index_add_(0, lab[ok], x[ok])
+            t["counts"] += torch.bincount(lab[ok], minlength=spec.n_out)
+            for k in range(spec.weights.shape[0]):
+                t["dot"][a:b, k] = (x * spec.weights[k]).sum(1)
+            for k in range(spec.n_bins):
+                t["bins"][a:b, k] = (x * (spec.pixel_labels == k)).sum(1)
+            img = torch.zeros((b - a, oh * by, ow * bx), dtype=i64, device=dev)
+            img[:, :H, :W] = x.view(b - a, H, W)
+            t["binned"][a:b] = img.view(b - a, oh, by, ow, bx).sum((2, 4))
+            m = x >= spec.threshold
+            rows.append(m.sum(1))
+            pos.append(m.nonzero()[:, 1])
+            val.append(x[m])
+            del x, img, m
+    t["rows"] = torch.cumsum(torch.cat(rows), 0)
+    t["positions"], t["values"] = torch.cat(pos), torch.cat(val)
+    return t

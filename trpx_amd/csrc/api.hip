@@ -84,6 +84,16 @@ bool sizes_ok(const trpx::FrameGeom& g, size_t n_frames) {
     const unsigned __int128 bytes = (unsigned __int128)g.n_values * n_frames * 8;
     return bytes < ((unsigned __int128)1 << 62);
 }
+// What the device can be asked to launch: HIP refuses a grid of 2^32 threads or more (gridDim.x * blockDim.x), and the hot
+// kernels start one workgroup of 256 threads per tile (encode.hip, decode.hip, decode_fast.hip) or one wavefront per frame
+// (decode.hip, decode_seg.hip, decode_locate.hip) with no cap.  So a call takes at most 2^24 - 1 tiles in all
+// (TRPX_MAX_TILES_PER_CALL, include/trpx_hip.h) -- 51 G values of frames of 512 x 512, but only 16.7 M frames of one tile
+// each; beyond it every device entry point answers UNSUPPORTED before its first device call.  (n_frames <= the tiles.)
+bool grid_ok(const trpx::FrameGeom& g, size_t n_frames) { return n_frames <= (size_t)TRPX_MAX_TILES_PER_CALL / g.n_tiles; }
+int grid_refused(const char* fn, const trpx::FrameGeom& g, size_t n_frames) {
+    return fail(TRPX_ERR_UNSUPPORTED, "%s: %zu frames of %u tiles: more than %u tiles in one call (split the stack)", fn, n_frames, g.n_tiles,
+                (unsigned)TRPX_MAX_TILES_PER_CALL);
+}
 // the locator and the host wrappers: a geometry that cannot be had is laid to the block size unless that is the tuned one
 int bad_geom(const char* fn, unsigned block) {
     return fail(block != kBlock ? TRPX_ERR_UNSUPPORTED : TRPX_ERR_INVALID_ARG, "%s: unsupported sizes/block (block=%u)", fn, block);
@@ -91,7 +101,9 @@ int bad_geom(const char* fn, unsigned block) {
 
 // ---- the argument prologue of the device-pointer entry points ---------------------------------------------------------------
 // Every error is decided here, before the first device call, in one order: [unknown dtype] -> block size -> 64-bit container ->
-// signedness (all UNSUPPORTED) -> dtype / sizes -> null -> misaligned pointers (all INVALID_ARG).  tests/test_abi_args.py pins
+// signedness (all UNSUPPORTED) -> dtype / sizes (INVALID_ARG) -> more tiles than one call takes (grid_ok, UNSUPPORTED; a stream of
+// fewer bytes than frames stays INVALID_ARG) -> null ->
+// misaligned pointers (both INVALID_ARG).  tests/test_abi_args.py pins
 // the code and the prefix of each; trpx_locate_frames and trpx_decode_sum keep their own, different orders.
 struct PtrReq { const void* p; size_t align; bool required = true; };
 enum : unsigned {
@@ -113,6 +125,11 @@ int check_args(const char* fn, unsigned rules, int dtype, size_t elem, int strea
     if (!elem) return fail(TRPX_ERR_INVALID_ARG, "%s: unknown dtype %d", fn, dtype);
     if (!geom_of(n_values, block, g) || !sizes_ok(*g, n_frames) || ((rules & kHasStream) && !terse_bytes))
         return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", fn, n_values, n_frames);
+    if (!grid_ok(*g, n_frames)) {
+        if ((rules & kHasStream) && n_frames > terse_bytes)                     // no such stack: every frame is at least one byte (Terse.hpp:547)
+            return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", fn, n_values, n_frames);
+        return grid_refused(fn, *g, n_frames);
+    }
     for (const PtrReq& q : ptrs)
         if (q.required && !q.p) return fail(TRPX_ERR_INVALID_ARG, "%s: null pointer", fn);
     for (const PtrReq& q : ptrs)
@@ -650,6 +667,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
     if (!geom_of(n_values, block, &g)) return bad_geom("trpx_locate_frames", block);
     if (!sizes_ok(g, n_frames) || n_frames > terse_bytes)                      // every frame is at least one byte (Terse.hpp:547)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
+    if (!grid_ok(g, n_frames)) return grid_refused("trpx_locate_frames", g, n_frames);
     if ((uintptr_t)terse % 4 || (uintptr_t)workspace % 8 || (uintptr_t)frame_offsets % 8 || (uintptr_t)status % 8)
         return fail(TRPX_ERR_INVALID_ARG, "trpx_locate_frames: misaligned pointer (terse needs 4 B, workspace 8 B)");
     const size_t need = trpx::locate_workspace_bytes(g, terse_bytes, n_frames);
@@ -704,6 +722,7 @@ int stack_limits(const Consumer& c) {
     if (!frame_bits_fit_32(c.dtype, c.n_values, c.block)) return fail(TRPX_ERR_UNSUPPORTED, "%s: frames of >= 2^32 bits", c.fn);
     if (c.n_frames > c.terse_bytes)                                             // every frame is at least one byte (Terse.hpp:547)
         return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", c.fn, c.n_values, c.n_frames);
+    if (!grid_ok(c.g, c.n_frames)) return grid_refused(c.fn, c.g, c.n_frames);    // (trpx_decode_sum / _sum_labelled: not through check_args)
     return TRPX_OK;
 }
 // The workspace against what this form of the call needs: *w, then own_bytes of the consumer's.  always: why the consumer needs

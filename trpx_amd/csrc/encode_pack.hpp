@@ -2,15 +2,24 @@
 // block's width, the scans over tiles and frames, a tile's output span, and the serialisation of one block into the
 // workgroup's LDS staging image.  Where a block's twelve values come from is each encoder's own.
 #pragma once
+#include <type_traits>
+
 #include "codec_common.hpp"
 
 namespace trpx {
 
+// A block's twelve values in registers.  8-bit pixels are held in 32-bit registers, zero- or sign-extended: with `T v[12]` the
+// compiler keeps twelve bytes in three VGPRs and merges every value into them (v_and_b32_sdwa ... dst_sel:BYTE_n, v_bitop3_b16),
+// and k_pack<uint8_t> built that way wrote bytes that differed from run to run on stacks of a few hundred tiles and more
+// (tests/test_gpu_large_stacks.py) -- the sequence that once made the basic 8-bit unpack kernel do the same (LABNOTES.md).
 template <typename T>
-__device__ __forceinline__ uint32_t block_width(const T (&v)[kBlock]) {
+using BlockReg = std::conditional_t<sizeof(T) == 1, std::conditional_t<PixelTraits<T>::is_signed, int32_t, uint32_t>, T>;
+
+template <typename T>
+__device__ __forceinline__ uint32_t block_width(const BlockReg<T> (&v)[kBlock]) {
     uint32_t m = 0;
 #pragma unroll
-    for (int k = 0; k < kBlock; ++k) m |= magnitude<T>(v[k]);   // OR-scan (Terse.hpp:508-514)
+    for (int k = 0; k < kBlock; ++k) m |= magnitude<T>((T)v[k]);   // OR-scan (Terse.hpp:508-514)
     return width_from_or<T>(m);
 }
 
@@ -143,7 +152,7 @@ constexpr int stage_dwords() { return (31 + kTileBlocks * max_block_bits<T>() + 
 
 // One block -- header of hl bits, nb values of w bits -- into the staging image at bit o.
 template <typename T>
-__device__ __forceinline__ void pack_block(uint32_t* stage, uint32_t o, const T (&v)[kBlock], int nb, uint32_t w,
+__device__ __forceinline__ void pack_block(uint32_t* stage, uint32_t o, const BlockReg<T> (&v)[kBlock], int nb, uint32_t w,
                                            uint32_t w_prev, uint32_t hl) {
     BitSink sink{stage, 0ull, o & 31u, o >> 5, true};
     sink.put(header_val(w, w_prev), hl);

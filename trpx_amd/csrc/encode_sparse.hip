@@ -85,7 +85,7 @@ __device__ __forceinline__ uint32_t halo_width(const uint32_t* __restrict__ posi
 template <typename T>
 __device__ __forceinline__ void blocks_from_events(const uint32_t* __restrict__ positions, const T* __restrict__ values,
                                                    uint64_t e0, uint64_t e1, uint64_t p0, const FrameGeom& g, uint32_t t,
-                                                   uint32_t w_halo, uint32_t* s_px, uint32_t* s_w, T (&v)[kBlock], int& nb, uint32_t& w,
+                                                   uint32_t w_halo, uint32_t* s_px, uint32_t* s_w, BlockReg<T> (&v)[kBlock], int& nb, uint32_t& w,
                                                    uint32_t& w_prev, bool& valid) {
     const uint32_t tid = threadIdx.x;
     uint4* z = reinterpret_cast<uint4*>(s_px);            // (dwords through a vector of dwords: 3 stores per thread)
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kThreads) void k_se_pack(const uint64_t* __restrict
         continue;
     }
 
-    T v[kBlock];
+    BlockReg<T> v[kBlock];
     int nb; uint32_t w, w_prev; bool valid;
     blocks_from_events<T>(positions, values, e0, e1, p0, g, t, w_halo, s_px, s_w, v, nb, w, w_prev, valid);
     const uint32_t hl = header_len(w, w_prev);

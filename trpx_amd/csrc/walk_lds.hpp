@@ -47,9 +47,11 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
         // LDS window; every lane decodes "its" explicit header in parallel, the step itself is branch-free ----------------
         {
             uint32_t stride = 1u + kBlock * w_prev;
-            int32_t pos_max = 32 * (c_hi - 1) - (int32_t)frame_sh - 63 * (int32_t)stride;
+            // (64-bit: frames of 2^31 bits and more have c_hi > 2^26 and pos > INT32_MAX -- in 32 bits the product wrapped and the
+            // comparison was signed, so the fast steps read outside the window and a valid frame came out as corrupt)
+            int64_t pos_max = 32 * (int64_t)(c_hi - 1) - (int64_t)frame_sh - 63 * (int64_t)stride;
             uint32_t wide = 0;
-            while (b + 64u < n_blocks && (int32_t)pos < pos_max) {
+            while (b + 64u < n_blocks && (int64_t)pos < pos_max) {
 #ifdef TRPX_WALK_STATS
                 ++st_steps;
 #endif
@@ -75,7 +77,7 @@ __device__ __forceinline__ void walk_lds_frame(const uint8_t* __restrict__ terse
                 b += n_done;
                 w_prev = e_w;
                 stride = 1u + kBlock * e_w;
-                pos_max = 32 * (c_hi - 1) - (int32_t)frame_sh - 63 * (int32_t)stride;
+                pos_max = 32 * (int64_t)(c_hi - 1) - (int64_t)frame_sh - 63 * (int64_t)stride;
             }
             if (wide > max_w) { bad = true; break; }
         }
