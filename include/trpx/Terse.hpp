@@ -409,6 +409,29 @@ public:
         return out;
     }
 
+    /// Per group of `group` consecutive frames the histogram of its pixel values, in one device call, without expanding the
+    /// frames (trpx_decode_hist_host): out[g * n_bins + b] = the number of pixels of group g with bin(v) == b,
+    /// bin(v) = clamp(floor((v - lo) / 2^shift), 0, n_bins - 1) -- the first and the last bin take everything below and above,
+    /// so every row sums to size() x the group's frames.  The last group holds what is left.  group >= 1, 1 <= n_bins <= 4096,
+    /// shift <= 32, |lo| <= 2^32.
+    std::vector<std::uint64_t> prolix_hist(std::size_t group, std::int64_t lo, unsigned shift, std::size_t n_bins) {
+        if (n_bins == 0 || n_bins > 4096) throw std::invalid_argument("prolix_hist: 1 to 4096 bins");
+        if (group == 0) throw std::invalid_argument("prolix_hist: group >= 1");
+        if (shift > 32 || lo > (std::int64_t(1) << 32) || lo < -(std::int64_t(1) << 32))
+            throw std::invalid_argument("prolix_hist: shift <= 32 and |lo| <= 2^32");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_hist: values of more than 32 bits are not supported");
+        const std::size_t f = d_frame_sizes.size();
+        if (f == 0) return {};
+        detail::require_abi();
+        std::vector<std::uint64_t> out((f + std::min(group, f) - 1) / std::min(group, f) * n_bins);
+        std::vector<std::uint64_t> offs(f + 1, 0);
+        for (std::size_t i = 0; i < f; ++i) offs[i + 1] = offs[i] + d_frame_sizes[i];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_hist_host(bits + (d_signed ? 1 : 0), d_terse_data.data(), d_terse_data.size(), offs.data(), d_size, f,
+                                            d_block, group, lo, shift, (unsigned)n_bins, out.data(), -1), "Terse::prolix_hist");
+        return out;
+    }
+
     /// A new object holding the frames `frames` of this one -- any order, repeats allowed, possibly more than the stack has --
     /// in one device call, without decoding them (trpx_select_frames_host): the frames' bytes are copied, so the result is
     /// what push_back of those frames' pixels makes.  dim(), signedness and block are copied; bits_per_val() is kept from the

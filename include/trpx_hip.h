@@ -53,8 +53,9 @@ typedef enum trpx_status {
  * stream by its widths alone (one header bit where a width repeats), so it cannot describe a restated width:
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
  *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
- *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce and
- *     trpx_decode_sum_labelled where they build the index themselves (no index given) -- and their _host forms;
+ *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce,
+ *     trpx_decode_sum_labelled and trpx_decode_hist where they build the index themselves (no index given) -- and their _host
+ *     forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -496,6 +497,67 @@ int trpx_decode_bins(int dtype, const uint8_t* terse, size_t terse_bytes, const 
 int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                           size_t n_values, size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins,
                           int64_t* bins_out, int device);
+
+/*
+ * Value histograms: hist_out[g][b] = the number of pixels of the frames of group g whose bin is b, straight from the stream and
+ * its decode index, without expanding the frames -- the threshold of trpx_decode_sparse, the percentiles a preview is scaled by,
+ * detector QC (saturation pile-up in the last bin, a negative tail after dark subtraction), "how many pixels >= t" for many t at
+ * once.  It stands in for the loop of src/prolix.cpp:69-92 (one `trpx_data.prolix(image, i)` per frame, Terse.hpp:387-388) with a
+ * histogram of every expanded image behind it.
+ *     bin(v) = clamp(floor((v - lo) / 2^shift), 0, n_bins - 1), computed in int64
+ * -- in numpy np.bincount(np.clip((px.astype(np.int64) - lo) >> shift, 0, n_bins - 1).ravel(), minlength=n_bins) per group (>> is
+ * arithmetic: values below lo floor).  The first and the last bin take everything below and above: every pixel is counted
+ * exactly once, and each row sums to n_values * (frames in the group).  The twelve zeros of a width-0 block are pixels and are
+ * counted, in bin(0).  A block's width bounds its values: a block whose whole value range lies inside one bin is counted from
+ * its width alone, and its payload is never fetched.
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_bins: index given -- validated against the frame sizes as in
+ *                  trpx_decode_indexed; offsets only -- the index is built in the workspace by trpx_build_index's walk; offsets
+ *                  NULL -- the frames are located in the workspace first.  workspace: DEVICE, 8-byte aligned;
+ *                  trpx_decode_hist_workspace_bytes() is the need with offsets and index both NULL; with offsets or index given
+ *                  less is used, and the call checks against what its own form needs (index given and one span per group:
+ *                  nothing, NULL is legal).  The size is arithmetic: beyond what the index needs
+ *                  (trpx_decode_roi_workspace_bytes()), where spans = trpx_decode_hist_spans_per_group(n_values, n_frames, group)
+ *                  is more than 1, 8 * n_bins * ceil(n_frames / group) * spans bytes of partial counts -- nothing otherwise
+ *   group          frames per histogram, trpx_decode_sum's rule: >= 1; groups are `group` consecutive frames, the last one holds
+ *                  what is left (a group larger than the stack: one group).  group = 1: per frame; group = n_frames: the stack's
+ *   lo, shift, n_bins
+ *                  the bin rule above.  -2^32 <= lo <= 2^32, 0 <= shift <= 32, 1 <= n_bins <= 4096: with these v - lo cannot
+ *                  leave int64 for any pixel type
+ *   hist_out       DEVICE uint64_t[ceil(n_frames / group)][n_bins], 8-byte aligned.  EVERY element is written by every successful
+ *                  call (a bin without pixels is 0): the caller clears nothing.  Integer counting throughout: bit-identical
+ *                  across runs, input forms, sub-stacks and launch shapes
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT in exactly the cases of trpx_decode_bins: a
+ *                  256-block group does not end where the next group's offset (the last group: the frame's size) says, a block is
+ *                  wider than dtype allows, a frame lies outside the stream or the index does not fit the offsets, with index ==
+ *                  NULL also for a valid stream with restated widths (trpx_build_index's verdict).  EVERY group of EVERY frame is
+ *                  walked and validated, also where no block of it is fetched.  The outputs are then unspecified
+ * The stream is read in aligned 32-bit words: nothing outside terse[0 .. align4(terse_bytes)) is read, nothing outside hist_out,
+ * status and the workspace is written, whatever the status.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, frames of >= 2^32 bits, more
+ * groups of 256 blocks than one call takes; TRPX_ERR_INVALID_ARG for an unknown or float dtype, zero sizes, group 0, n_bins 0 or
+ * above 4096, shift above 32, |lo| above 2^32, null or misaligned pointers, an index without offsets, a NULL workspace where the
+ * call's form needs one; TRPX_ERR_CAPACITY for a workspace that is too small for the call's own form.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); every launch shape is decided on the
+ * host from n_frames, n_values, group and n_bins alone, never from the data.
+ * trpx_decode_hist_spans_per_group: the workgroups a group is cut into, with R = min(group, n_frames) * ceil(groups of 256 blocks
+ * / 8) runs a group and G = ceil(n_frames / group) groups: max(ceil(R / 2^17), min(ceil(R / 4), max(1, ceil(1536 / G)))) -- pure
+ * arithmetic, for tests and diagnostics (0 for sizes no call takes, the stacks beyond TRPX_MAX_TILES_PER_CALL included, as is
+ * trpx_decode_hist_workspace_bytes()); above 1 the partial counts of the spans pass through the workspace.  The ragged last group is cut into the same number of (shorter, possibly empty) spans.
+ * trpx_decode_hist_host: host terse / frame_offsets (or NULL) / hist_out; checks its arguments before a device is looked for,
+ * stages, calls trpx_decode_hist and synchronises.
+ */
+size_t trpx_decode_hist_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
+                                        size_t group, unsigned n_bins);
+unsigned trpx_decode_hist_spans_per_group(size_t n_values, size_t n_frames, size_t group);
+int trpx_decode_hist(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                     size_t n_values, size_t n_frames, unsigned block, size_t group, int64_t lo, unsigned shift,
+                     unsigned n_bins, uint64_t* hist_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_hist_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                          size_t n_values, size_t n_frames, unsigned block, size_t group, int64_t lo, unsigned shift,
+                          unsigned n_bins, uint64_t* hist_out, int device);
 
 /*
  * Binned decode: every frame summed over bins of bin_y x bin_x neighbouring pixels, straight from the stream and its decode

@@ -482,6 +482,44 @@ def decode_bins(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_value
     return out, status
 
 
+def decode_hist_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, n_bins: int, group: int = 1, block: int = BLOCK) -> int:
+    return lib().trpx_decode_hist_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block, group, n_bins)
+
+
+def decode_hist(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype, n_bins: int,
+                group: int = 1, lo: int = 0, shift: int = 0, index: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                workspace: Workspace | None = None, status: torch.Tensor | None = None, block: int = BLOCK):
+    """Per group of ``group`` consecutive frames the histogram of its pixel values (trpx_decode_hist), for a stack resident on
+    the GPU, without decoding its frames to memory: ``bin(v) = clamp((v - lo) >> shift, 0, n_bins - 1)``, the first and the last
+    bin taking everything below and above.
+
+    ``dtype`` is the stream's pixel type; 1 <= n_bins <= 4096, 0 <= shift <= 32, |lo| <= 2^32, group >= 1 (the last group holds
+    what is left; ``group = n_frames``: the stack's histogram).  Returns (hist int64 [ceil(n_frames / group), n_bins], status):
+    exact counts, every element written, each row summing to n_values x the group's frames; asynchronous on the current stream,
+    like ``decode``.  status[0] is 5 for a corrupt stream or index -- the whole stack is validated, whatever is fetched.
+    ``frame_offsets = None``: the frames are located first; ``index = None``: the decode index is built on the way (both in
+    ``workspace``)."""
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    if not 1 <= n_bins <= 4096:
+        raise ValueError("decode_hist: 1 to 4096 bins")
+    if not 0 <= shift <= 32 or abs(lo) > 2**32:
+        raise ValueError("decode_hist: 0 <= shift <= 32 and |lo| <= 2^32")
+    if group < 1:
+        raise ValueError("decode_hist: group >= 1")
+    n_groups = -(-n_frames // min(group, n_frames)) if n_frames else 0
+    if out is None:
+        out = torch.empty((n_groups, n_bins), dtype=torch.int64, device=dev)     # (counts < 2^63: the uint64 of the C ABI, as int64)
+    elif out.dtype not in (torch.int64, torch.uint64) or out.numel() != n_groups * n_bins or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_hist: out must be a contiguous int64 tensor of {n_groups} x {n_bins} elements on {dev}")
+    status = _status(status, dev)
+    ws = _scratch(workspace, dev, lib().trpx_decode_hist_workspace_bytes(code, terse.numel(), n_values, n_frames, block, group, n_bins))
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_hist(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index), n_values, n_frames, block,
+                                     group, lo, shift, n_bins, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
+    return out, status
+
+
 def decode_binned_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, block: int = BLOCK) -> int:
     return lib().trpx_decode_binned_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block)
 

@@ -18,6 +18,7 @@
 #include "decode_sparse.hpp"
 #include "decode_dot.hpp"
 #include "decode_bins.hpp"
+#include "decode_hist.hpp"
 #include "decode_binned.hpp"
 #include "decode_sum.hpp"
 #include "decode_reduce.hpp"
@@ -679,7 +680,7 @@ int trpx_locate_frames(const uint8_t* terse, size_t terse_bytes, size_t n_values
 }
 
 }  // extern "C"
-// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce, trpx_decode_sum_labelled ----
+// ---- the consumers of a decode index: trpx_decode_sum, trpx_decode_roi, trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce, trpx_decode_sum_labelled, trpx_decode_hist ----
 // Each reads: its own checks, the shared checks (stack_limits, consumer_ws), the front (consumer_front), its own few fields, launch.
 namespace {
 // The consumers take three input forms: index given; offsets only -- the index is built by trpx_build_index's walk; neither --
@@ -830,6 +831,13 @@ BinsWs bins_ws(const trpx::FrameGeom& g, size_t n_frames, unsigned n_bins) {
     return w;
 }
 bool bins_count_ok(unsigned n_bins) { return n_bins >= 1 && n_bins <= trpx::kBinsMax; }
+
+// ---- value histograms (decode_hist.hip): its scratch is, with more than one span per group, per (group, span, bin) [partial
+// count u64] -- nothing otherwise ------------------------------------------------------------------------------------------------
+size_t hist_ws(const trpx::FrameGeom& g, size_t n_frames, size_t group, unsigned n_bins) {
+    const size_t spans = trpx::hist_spans_per_group(g, n_frames, group), frames = std::min(group, n_frames);
+    return spans > 1 ? 8 * (size_t)n_bins * ((n_frames + frames - 1) / frames) * spans : 0;
+}
 
 // ---- binned decode (decode_binned.hip): no scratch of its own ------------------------------------------------------------------------
 // the checks the device-pointer and the host-pointer entry point share, behind the stack's own (a frame has < 2^29 values, see
@@ -1070,6 +1078,54 @@ int trpx_decode_bins(int dtype, const uint8_t* terse, size_t terse_bytes, const 
     a.bins_out = bins_out;
     a.status = status;
     HIP_TRY(trpx::launch_decode_bins(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
+size_t trpx_decode_hist_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block, size_t group,
+                                        unsigned n_bins) {
+    trpx::FrameGeom g;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && group && bins_count_ok(n_bins) && grid_ok(g, n_frames) ? front + hist_ws(g, n_frames, group, n_bins) : 0;
+}
+
+unsigned trpx_decode_hist_spans_per_group(size_t n_values, size_t n_frames, size_t group) {
+    trpx::FrameGeom g;
+    // (0 for what the call refuses: also for more groups of 256 blocks than one call takes)
+    return group && geom_of(n_values, kBlock, &g) && sizes_ok(g, n_frames) && grid_ok(g, n_frames) ? trpx::hist_spans_per_group(g, n_frames, group) : 0;
+}
+
+int trpx_decode_hist(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, const void* index,
+                     size_t n_values, size_t n_frames, unsigned block, size_t group, int64_t lo, unsigned shift, unsigned n_bins,
+                     uint64_t* hist_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_hist", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {hist_out, 8}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
+                                   {workspace, 8, false}}, &g))
+        return rc;
+    const Consumer c{"trpx_decode_hist", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
+    if (group == 0) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_hist: group = 0");
+    if (!trpx::hist_args_ok(lo, shift, n_bins))
+        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_hist: lo=%lld shift=%u n_bins=%u (|lo| <= 2^32, shift <= %u, 1..%u bins)", (long long)lo, shift,
+                    n_bins, trpx::kHistMaxShift, trpx::kHistMaxBins);
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, hist_ws(g, n_frames, group, n_bins), nullptr, &w)) return rc;   // (index given, one span a group: no workspace at all)
+    if (const int rc = consumer_front(c, w, true, &f)) return rc;
+    trpx::HistArgs a{};
+    static_cast<trpx::IndexedStack&>(a) = f.stack;
+    a.group = std::min(group, n_frames);
+    a.n_groups = (n_frames + a.group - 1) / a.group;
+    a.lo = lo;
+    a.shift = shift;
+    a.n_bins = n_bins;
+    a.spans = trpx::hist_spans_per_group(g, n_frames, group);
+    a.partials = reinterpret_cast<uint64_t*>(f.own);
+    a.hist_out = hist_out;
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_hist(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
     return TRPX_OK;
 }
 
@@ -1758,6 +1814,31 @@ int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, c
                           reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
     if (rc || (rc = finish("trpx_decode_bins_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, bins_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_hist_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
+                          size_t n_frames, unsigned block, size_t group, int64_t lo, unsigned shift, unsigned n_bins, uint64_t* hist_out,
+                          int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (const int rc = consumer_host_refusals("trpx_decode_hist_host", terse && hist_out && group && trpx::hist_args_ok(lo, shift, n_bins), dtype,
+                                              terse_bytes, n_values, n_frames, block, &g))
+        return rc;
+    const size_t ws_bytes = trpx_decode_hist_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group, n_bins);
+    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_hist_host: bad dtype/sizes");
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_hist_host: frames of >= 2^32 bits");
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_hist_host", device, &hs)) return rc;
+    const size_t frames = std::min(group, n_frames), out_bytes = 8 * ((n_frames + frames - 1) / frames) * (size_t)n_bins;
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_hist(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, group, lo, shift, n_bins,
+                          static_cast<uint64_t*>(d.out), d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_hist_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, hist_out, d.out, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

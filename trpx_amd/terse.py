@@ -438,6 +438,28 @@ class Terse:
                                               lab.ctypes.data, int(n_bins), out.ctypes.data, self._device))
         return out
 
+    def prolix_hist(self, group: int = 1, lo: int = 0, shift: int = 0, n_bins: int = 256) -> np.ndarray:
+        """Per group of ``group`` consecutive frames the histogram of its pixel values in ONE GPU call (trpx_decode_hist_host),
+        without decoding the frames to memory: ``bin(v) = clamp((v - lo) >> shift, 0, n_bins - 1)``, the first and the last bin
+        taking everything below and above.  1 <= n_bins <= 4096, 0 <= shift <= 32, |lo| <= 2^32, group >= 1 (the last group holds
+        what is left).  Returns int64 ``[ceil(number_of_frames / group), n_bins]``: exact counts, each row summing to size() x the
+        group's frames -- ``np.bincount(np.clip((px.astype(np.int64) - lo) >> shift, 0, n_bins - 1).ravel(), minlength=n_bins)``."""
+        group, lo, shift, n_bins = int(group), int(lo), int(shift), int(n_bins)
+        if not 1 <= n_bins <= 4096:
+            raise ValueError("prolix_hist: 1 to 4096 bins")
+        if not 0 <= shift <= 32 or abs(lo) > 2**32:
+            raise ValueError("prolix_hist: 0 <= shift <= 32 and |lo| <= 2^32")
+        if group < 1:
+            raise ValueError("prolix_hist: group >= 1")
+        code, _ = self._stream_type("prolix_hist")
+        f = self.number_of_frames()
+        out = np.zeros((-(-f // min(group, f)) if f else 0, n_bins), np.uint64)
+        if f:
+            buf, offs = self._stream_and_offsets()
+            check(lib().trpx_decode_hist_host(code, buf.ctypes.data, buf.size, offs.ctypes.data, self._size, f, self._block, group, lo,
+                                              shift, n_bins, out.ctypes.data, self._device))
+        return out.astype(np.int64)
+
     def select(self, frames) -> "Terse":
         """A new object holding the frames ``frames`` of this one, in ONE GPU call (trpx_select_frames_host), without decoding
         them: the frames' bytes are copied, so the result is what ``push_back_stack(pixels[frames])`` would make.  ``frames``: a
