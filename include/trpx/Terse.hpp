@@ -432,6 +432,33 @@ public:
         return out;
     }
 
+    /// Frames [first_frame, first_frame + n_frames) (clipped to the stack) as float32 with the dark reference subtracted and the
+    /// gain reference multiplied in, in one device call (trpx_decode_corrected_host): out[f * size() + p] =
+    /// ((float) px[f][p] - dark[p]) * gain[p], three float operations in this order, each rounded once; subnormal results are
+    /// unspecified.  dark / gain: size() values, or nullptr to leave the operation out (both: a plain float decode).
+    std::vector<float> prolix_corrected(const float* dark, const float* gain, std::size_t first_frame = 0,
+                                        std::size_t n_frames = static_cast<std::size_t>(-1)) {
+        if (first_frame > number_of_frames()) throw std::invalid_argument("prolix_corrected: frame index out of range");
+        if (d_prolix_bits > 32) throw std::invalid_argument("prolix_corrected: values of more than 32 bits are not supported");
+        n_frames = std::min(n_frames, number_of_frames() - first_frame);
+        if (n_frames == 0) return {};
+        detail::require_abi();
+        std::vector<float> out(n_frames * d_size);
+        std::size_t start = 0;
+        for (std::size_t i = 0; i < first_frame; ++i) start += d_frame_sizes[i];
+        std::vector<std::uint64_t> offs(n_frames + 1, 0);
+        for (std::size_t i = 0; i < n_frames; ++i) offs[i + 1] = offs[i] + d_frame_sizes[first_frame + i];
+        const int bits = d_prolix_bits <= 8 ? TRPX_U8 : d_prolix_bits <= 16 ? TRPX_U16 : TRPX_U32;   // the narrowest stream type
+        detail::check(trpx_decode_corrected_host(bits + (d_signed ? 1 : 0), TRPX_F32, d_terse_data.data() + start, offs[n_frames], offs.data(), d_size,
+                                                 n_frames, d_block, dark, gain, out.data(), -1), "Terse::prolix_corrected");
+        return out;
+    }
+    std::vector<float> prolix_corrected(std::vector<float> const& dark, std::vector<float> const& gain, std::size_t first_frame = 0,
+                                        std::size_t n_frames = static_cast<std::size_t>(-1)) {
+        if (dark.size() != d_size || gain.size() != d_size) throw std::invalid_argument("prolix_corrected: dark and gain must hold size() values");
+        return prolix_corrected(dark.data(), gain.data(), first_frame, n_frames);
+    }
+
     /// A new object holding the frames `frames` of this one -- any order, repeats allowed, possibly more than the stack has --
     /// in one device call, without decoding them (trpx_select_frames_host): the frames' bytes are copied, so the result is
     /// what push_back of those frames' pixels makes.  dim(), signedness and block are copied; bits_per_val() is kept from the

@@ -54,8 +54,8 @@ typedef enum trpx_status {
  *   - trpx_build_index and trpx_index_from_group_states report such a stream as TRPX_ERR_CORRUPT (every index they leave has
  *     been compared with the stream's headers block by block), and so do trpx_decode_sum, trpx_decode_roi,
  *     trpx_decode_sparse, trpx_decode_dot, trpx_decode_bins, trpx_decode_binned, trpx_decode_reduce,
- *     trpx_decode_sum_labelled and trpx_decode_hist where they build the index themselves (no index given) -- and their _host
- *     forms;
+ *     trpx_decode_sum_labelled, trpx_decode_hist and trpx_decode_corrected where they build the index themselves (no index
+ *     given) -- and their _host forms;
  *   - trpx_decode: the basic route (trpx_set_decode_path(1)) decodes it, and so does every route for 64-bit containers; on
  *     the other routes a frame the per-frame decoder extracts from its own walk is decoded, a frame that goes through a
  *     decode index (header-dense frames, frames of more than 32 K blocks, the tiled route) is TRPX_ERR_CORRUPT;
@@ -558,6 +558,58 @@ int trpx_decode_hist(int dtype, const uint8_t* terse, size_t terse_bytes, const 
 int trpx_decode_hist_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                           size_t n_values, size_t n_frames, unsigned block, size_t group, int64_t lo, unsigned shift,
                           unsigned n_bins, uint64_t* hist_out, int device);
+
+/*
+ * Corrected decode: every frame of a stack as float32 with the detector's dark reference subtracted and its gain reference
+ * multiplied in, straight from the stream and its decode index -- the frames motion correction or any float processing starts
+ * from, without the integer stack and the float temporaries of decode + convert + subtract + multiply.  It stands in for the
+ * loop of Terse.hpp:352-389 / src/prolix.cpp:69-92 with the correction applied to every expanded image.
+ *     out[f][p] = ((float) px[f][p] - dark[p]) * gain[p]
+ * -- in numpy, everything float32, (px.astype(np.float32) - dark[None]) * gain[None]: three IEEE binary32 operations in this
+ * order, each rounded once to nearest even: the conversion (exact for 8- and 16-bit pixels, rounds 32-bit pixels of magnitude
+ * above 2^24), the subtraction, the multiplication.  Nothing is fused or re-associated.  The result equals numpy's bit for bit
+ * wherever that is zero, a normal number, +-inf or NaN (a NaN's payload is not defined); results that are SUBNORMAL are
+ * unspecified: the device may flush them to zero.  gain[p] == 0 blanks a bad pixel; non-finite map entries are legal and
+ * propagate.  The twelve zeros of a width-0 block are pixels: they come out as (0 - dark[p]) * gain[p].
+ *   dtype          the stream's pixel type, TRPX_U8 .. TRPX_I32
+ *   out_dtype      TRPX_F32; anything else is TRPX_ERR_UNSUPPORTED (the parameter is there so that TRPX_F64 can follow without a
+ *                  new symbol)
+ *   terse, frame_offsets, index, workspace
+ *                  the three input forms of trpx_decode_sum, with its rules and status meanings: index given -- validated
+ *                  against the frame sizes, no workspace needed (NULL is legal); offsets only -- the index is built in the
+ *                  workspace by trpx_build_index's walk; offsets NULL -- the frames are located in the workspace first.
+ *                  workspace: DEVICE, 8-byte aligned; trpx_decode_corrected_workspace_bytes() is the need with offsets and index
+ *                  both NULL -- what the index needs, trpx_decode_roi_workspace_bytes(), and 0 for sizes no call takes, the
+ *                  stacks beyond TRPX_MAX_TILES_PER_CALL included; the call checks against what its own form needs
+ *   dark, gain     DEVICE const float[n_values], 4-byte aligned, read by the kernel when it runs: a captured graph is replayed
+ *                  with new maps in the same buffers.  Either may be NULL: dark == NULL leaves the subtraction out, gain == NULL
+ *                  the multiplication -- exactly the results of an all +0.0f and an all 1.0f map; both NULL: a plain float32
+ *                  decode
+ *   out            DEVICE float[n_frames][n_values], 4-byte aligned.  EVERY element is written by every successful call.  The
+ *                  fast case is out and both maps 16-byte aligned with n_values % 4 == 0: whole 16-byte stores and map loads;
+ *                  any other alignment runs on the same kernel with accesses that assume 4 bytes only
+ *   status         DEVICE uint32_t[TRPX_STATUS_WORDS].  Word 0 = TRPX_ERR_CORRUPT: a tile does not fit its frame, a block is
+ *                  wider than dtype allows, a frame lies outside the stream or the index does not fit the offsets, with index ==
+ *                  NULL also for a valid stream with restated widths.  Every tile of every frame is validated.  `out` is then
+ *                  unspecified
+ * Nothing outside terse[0 .. align4(terse_bytes)), dark[0 .. n_values) and gain[0 .. n_values) is read -- a frame's partial last
+ * block reads no map entry behind n_values --, nothing outside out, status and the workspace is written, whatever the status.
+ * Frames [a, b) of a stack alone: frame_offsets + a, n_frames = b - a, index = NULL.
+ * Errors returned before any device call: TRPX_ERR_UNSUPPORTED for block != 12, 64-bit containers, another out_dtype, frames of
+ * >= 2^32 bits, more groups of 256 blocks than one call takes; TRPX_ERR_INVALID_ARG for an unknown or float dtype, zero sizes,
+ * null or misaligned pointers, an index without offsets; TRPX_ERR_CAPACITY for a workspace too small for the call's own form.
+ * Stream-ordered, no allocation, no host synchronisation (capturable into a HIP graph); the launch shape is decided on the host
+ * from n_frames and n_values alone, never from the data.
+ * trpx_decode_corrected_host: host terse / frame_offsets (or NULL) / dark / gain (or NULL) / out; checks its arguments before a
+ * device is looked for, stages, calls trpx_decode_corrected and synchronises.
+ */
+size_t trpx_decode_corrected_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block);
+int trpx_decode_corrected(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                          const void* index, size_t n_values, size_t n_frames, unsigned block, const float* dark, const float* gain,
+                          void* out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int trpx_decode_corrected_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                               size_t n_values, size_t n_frames, unsigned block, const float* dark, const float* gain, void* out,
+                               int device);
 
 /*
  * Binned decode: every frame summed over bins of bin_y x bin_x neighbouring pixels, straight from the stream and its decode

@@ -76,6 +76,9 @@ SYMBOLS = {
     "trpx_decode_hist_spans_per_group": (_U, [_SZ, _SZ, _SZ]),
     "trpx_decode_hist": (_I, [_I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _SZ, _I64, _U, _U, _P, _P, _P, _SZ, _P]),
     "trpx_decode_hist_host": (_I, [_I, _P, _SZ, _P, _SZ, _SZ, _U, _SZ, _I64, _U, _U, _P, _I]),
+    "trpx_decode_corrected_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
+    "trpx_decode_corrected": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _P, _P, _P, _P, _P, _SZ, _P]),
+    "trpx_decode_corrected_host": (_I, [_I, _I, _P, _SZ, _P, _SZ, _SZ, _U, _P, _P, _P, _I]),
     "trpx_decode_binned_workspace_bytes": (_SZ, [_I, _SZ, _SZ, _SZ, _U]),
     "trpx_decode_binned_bands_per_frame": (_U, [_SZ, _SZ, _U, _U, _SZ]),
     "trpx_decode_binned": (_I, [_I, _I, _P, _SZ, _P, _P, _SZ, _SZ, _U, _SZ, _U, _U, _P, _P, _P, _SZ, _P]),

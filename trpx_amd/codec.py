@@ -520,6 +520,48 @@ def decode_hist(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_value
     return out, status
 
 
+def decode_corrected_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, block: int = BLOCK) -> int:
+    return lib().trpx_decode_corrected_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block)
+
+
+def _map(name: str, m: torch.Tensor | None, n_values: int, dev) -> torch.Tensor | None:
+    if m is not None and (m.dtype != torch.float32 or m.numel() != n_values or not m.is_contiguous() or m.device != dev):
+        raise ValueError(f"decode_corrected: {name} must be a contiguous float32 tensor of {n_values} elements on {dev}")
+    return m
+
+
+def decode_corrected(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values: int, n_frames: int, dtype,
+                     dark: torch.Tensor | None = None, gain: torch.Tensor | None = None, index: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None, workspace: Workspace | None = None, status: torch.Tensor | None = None,
+                     block: int = BLOCK):
+    """Every frame of a stack resident on the GPU as float32 with the dark reference subtracted and the gain reference
+    multiplied in (trpx_decode_corrected): ``out[f, p] = (float32(px[f, p]) - dark[p]) * gain[p]``, three float32 operations in
+    this order, each rounded once -- bit for bit ``(px.to(torch.float32) - dark) * gain`` wherever that is not subnormal --
+    without the integer stack and the float temporaries of that expression.
+
+    ``dtype`` is the stream's pixel type; ``dark`` / ``gain``: float32 ``[n_values]`` on the stream's device, read when the
+    kernel runs (a captured call is replayed with new maps in the same tensors), or None to leave the operation out (both None:
+    a plain float32 decode).  Returns (out float32 [n_frames, n_values], status): every element written; asynchronous on the
+    current stream, like ``decode``.  status[0] is 5 for a corrupt stream or index.  ``frame_offsets = None``: the frames are
+    located first; ``index = None``: the decode index is built on the way (both in ``workspace``)."""
+    code = dtype_code(torch_dtype(dtype))
+    dev = terse.device
+    dark, gain = _map("dark", dark, n_values, dev), _map("gain", gain, n_values, dev)
+    if out is None:
+        out = torch.empty((n_frames, n_values), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() != n_frames * n_values or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"decode_corrected: out must be a contiguous float32 tensor of {n_frames} x {n_values} elements on {dev}")
+    status = _status(status, dev)
+    ws = None                                               # (offsets and index given: the call needs no workspace)
+    if frame_offsets is None or index is None:
+        ws = _scratch(workspace, dev, lib().trpx_decode_corrected_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+    with torch.cuda.device(dev):
+        check(lib().trpx_decode_corrected(code, _lib.F32, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index), n_values, n_frames,
+                                          block, _ptr(dark), _ptr(gain), out.data_ptr(), status.data_ptr(), _ptr(ws),
+                                          ws.numel() if ws is not None else 0, _stream_ptr(terse)))
+    return out, status
+
+
 def decode_binned_workspace_bytes(terse_bytes: int, n_values: int, n_frames: int, dtype, block: int = BLOCK) -> int:
     return lib().trpx_decode_binned_workspace_bytes(dtype_code(torch_dtype(dtype)), terse_bytes, n_values, n_frames, block)
 

@@ -19,6 +19,7 @@
 #include "decode_dot.hpp"
 #include "decode_bins.hpp"
 #include "decode_hist.hpp"
+#include "decode_corrected.hpp"
 #include "decode_binned.hpp"
 #include "decode_sum.hpp"
 #include "decode_reduce.hpp"
@@ -1129,6 +1130,42 @@ int trpx_decode_hist(int dtype, const uint8_t* terse, size_t terse_bytes, const 
     return TRPX_OK;
 }
 
+// ---- corrected decode (decode_corrected.hip): no scratch of its own ------------------------------------------------------------------
+
+size_t trpx_decode_corrected_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
+    const size_t front = consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
+    return front && grid_ok(g, n_frames) && n_frames <= terse_bytes && frame_bits_fit_32(dtype, n_values, block) ? front : 0;
+}
+
+int trpx_decode_corrected(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                          const void* index, size_t n_values, size_t n_frames, unsigned block, const float* dark, const float* gain,
+                          void* out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    trpx::FrameGeom g;
+    const size_t es = trpx_dtype_size(dtype);
+    if (const int rc = check_args("trpx_decode_corrected", kDtypeFirst | kIndexOnly | kHasStream, dtype, es, 0, terse_bytes, n_values, n_frames, block,
+                                  {{terse, 4}, {out, out_dtype == TRPX_F32 ? 4u : 1u}, {status, 8}, {frame_offsets, 8, false}, {index, 16, false},
+                                   {workspace, 8, false}, {dark, 4, false}, {gain, 4, false}}, &g))
+        return rc;
+    if (out_dtype != TRPX_F32) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_corrected: out_dtype %d (F32)", out_dtype);
+    const Consumer c{"trpx_decode_corrected", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
+                     workspace_bytes, stream};
+    if (const int rc = stack_limits(c)) return rc;
+    IndexWs w;
+    Front f;
+    if (const int rc = consumer_ws(c, 0, nullptr, &w)) return rc;             // (offsets and index given: no workspace at all)
+    // (no k_check_index behind the walk: k_decode_corrected compares every block's header bit with its widths on the way)
+    if (const int rc = consumer_front(c, w, false, &f)) return rc;
+    trpx::CorrectedArgs a{};
+    static_cast<trpx::IndexedStack&>(a) = f.stack;
+    a.dark = dark;
+    a.gain = gain;
+    a.out = static_cast<float*>(out);
+    a.status = status;
+    HIP_TRY(trpx::launch_decode_corrected(dtype, a, f.clear, static_cast<hipStream_t>(stream)));
+    return TRPX_OK;
+}
+
 size_t trpx_decode_binned_workspace_bytes(int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
     trpx::FrameGeom g;
     return consumer_front_bytes(dtype, terse_bytes, n_values, n_frames, block, &g);
@@ -1839,6 +1876,35 @@ int trpx_decode_hist_host(int dtype, const uint8_t* terse, size_t terse_bytes, c
                           static_cast<uint64_t*>(d.out), d.status, d.ws, ws_bytes, hs);
     if (rc || (rc = finish("trpx_decode_hist_host", hs, d.status, st))) return rc;
     HIP_TRY(copy_sync(hs, hist_out, d.out, out_bytes, hipMemcpyDeviceToHost));
+    return TRPX_OK;
+}
+
+int trpx_decode_corrected_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                               size_t n_values, size_t n_frames, unsigned block, const float* dark, const float* gain, void* out, int device) {
+    // (the argument checks need no device: they come first)
+    trpx::FrameGeom g;
+    if (const int rc = consumer_host_refusals("trpx_decode_corrected_host", terse && out, dtype, terse_bytes, n_values, n_frames, block, &g))
+        return rc;
+    if (out_dtype != TRPX_F32) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_corrected_host: out_dtype %d (F32)", out_dtype);
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_corrected_host: frames of >= 2^32 bits");
+    const size_t ws_bytes = trpx_decode_corrected_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
+    if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_corrected_host: bad dtype/sizes");
+    hipStream_t hs = nullptr;
+    if (const int rc = enter("trpx_decode_corrected_host", device, &hs)) return rc;
+    // the maps and the frames in one device block: [dark] [gain] [out]
+    const size_t map_bytes = trpx::align_up(4 * n_values, 16), out_bytes = 4 * n_frames * n_values;
+    Staged d;
+    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, 2 * map_bytes + out_bytes, ws_bytes, &d);
+    if (rc) return rc;
+    char* o = static_cast<char*>(d.out);
+    if (dark) HIP_TRY(copy_sync(hs, o, dark, 4 * n_values, hipMemcpyHostToDevice));
+    if (gain) HIP_TRY(copy_sync(hs, o + map_bytes, gain, 4 * n_values, hipMemcpyHostToDevice));
+    uint32_t st[TRPX_STATUS_WORDS];
+    rc = trpx_decode_corrected(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block,
+                               dark ? reinterpret_cast<const float*>(o) : nullptr, gain ? reinterpret_cast<const float*>(o + map_bytes) : nullptr,
+                               o + 2 * map_bytes, d.status, d.ws, ws_bytes, hs);
+    if (rc || (rc = finish("trpx_decode_corrected_host", hs, d.status, st))) return rc;
+    HIP_TRY(copy_sync(hs, out, o + 2 * map_bytes, out_bytes, hipMemcpyDeviceToHost));
     return TRPX_OK;
 }
 

@@ -460,6 +460,35 @@ class Terse:
                                               shift, n_bins, out.ctypes.data, self._device))
         return out.astype(np.int64)
 
+    def prolix_corrected(self, dark=None, gain=None, first: int = 0, n: int | None = None) -> np.ndarray:
+        """Frames ``[first, first + n)`` (``n = None``: to the end) as float32 with the dark reference subtracted and the gain
+        reference multiplied in, in ONE GPU call (trpx_decode_corrected_host): ``(px.astype(np.float32) - dark) * gain``, three
+        float32 operations in this order, each rounded once; subnormal results are unspecified.  ``dark`` / ``gain``: size()
+        values (any shape, converted to float32), or None to leave the operation out.  Returns float32 ``[n, size()]``."""
+        f = self.number_of_frames()
+        first = int(first)
+        n = f - first if n is None else int(n)
+        if first < 0 or n < 0 or first + n > f:
+            raise ValueError("prolix_corrected: frames out of range")
+        maps = []
+        for name, m in (("dark", dark), ("gain", gain)):
+            if m is not None:
+                m = np.ascontiguousarray(np.asarray(m, dtype=np.float32).reshape(-1))
+                if m.size != self._size:
+                    raise ValueError(f"prolix_corrected: {name} must hold size() values")
+            maps.append(m)
+        code, _ = self._stream_type("prolix_corrected")
+        out = np.empty((n, self._size), np.float32)
+        if n:
+            buf, offs = self._stream_and_offsets()
+            a, b = int(offs[first]), int(offs[first + n])
+            sub = np.ascontiguousarray(buf[a:b])
+            rel = np.ascontiguousarray(offs[first:first + n + 1] - offs[first])
+            check(lib().trpx_decode_corrected_host(code, _lib.F32, sub.ctypes.data, sub.size, rel.ctypes.data, self._size, n, self._block,
+                                                   maps[0].ctypes.data if maps[0] is not None else None,
+                                                   maps[1].ctypes.data if maps[1] is not None else None, out.ctypes.data, self._device))
+        return out
+
     def select(self, frames) -> "Terse":
         """A new object holding the frames ``frames`` of this one, in ONE GPU call (trpx_select_frames_host), without decoding
         them: the frames' bytes are copied, so the result is what ``push_back_stack(pixels[frames])`` would make.  ``frames``: a
