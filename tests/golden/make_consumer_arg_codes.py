@@ -1,4 +1,5 @@
-"""Writes tests/golden/consumer_arg_codes.json: what the library answers to every call of tests/test_consumer_args_order.py.
+"""Writes tests/golden/consumer_arg_codes.json and consumer_arg_codes_more.json: what the library answers to every call of
+tests/test_consumer_args_order.py, each consumer in the file the test's RECORDED names for it.
 
     TRPX_LIB=/path/to/the/recorded/libtrpx_hip.so python tests/golden/make_consumer_arg_codes.py
 
@@ -18,7 +19,9 @@ L = _lib.lib()
 if L.trpx_device_count():
     sys.exit("a HIP device is present: the _host column is recorded without one")
 got = T.answers(L)
-with open(T.GOLDEN, "w") as f:
-    json.dump(got, f, indent=0, sort_keys=True)
-    f.write("\n")
-print(f"{_lib.LIB_PATH}: {len(got['ptr'])} device-pointer calls, {len(got['host'])} host calls -> {T.GOLDEN}")
+for path, names in T.RECORDED.items():
+    part = T._of(got, names)
+    with open(path, "w") as f:
+        json.dump(part, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{_lib.LIB_PATH}: {len(part['ptr'])} device-pointer calls, {len(part['host'])} host calls -> {path}")

@@ -4,6 +4,7 @@ torch is plumbing only (device memory + streams); all compute happens in libtrpx
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -114,6 +115,29 @@ class Workspace:
 
 def _scratch(workspace: Workspace | None, dev, nbytes: int) -> torch.Tensor:
     return (workspace or Workspace(dev)).get(nbytes)
+
+
+def _out(fn: str, out: torch.Tensor | None, shape, dtype, dev, type_name: str | None = None, also=()) -> torch.Tensor:
+    """A consumer's output: a new tensor of this shape and dtype on dev, or the caller's checked against them (also: other
+    dtypes of the same size it may have; type_name: how the message names the type)."""
+    if out is None:
+        return torch.empty(tuple(max(s, 0) for s in shape), dtype=dtype, device=dev)   # (a negative count: left to the library)
+    if out.dtype not in (dtype, *also) or out.numel() != math.prod(shape) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{fn}: out must be a contiguous {type_name or dtype} tensor of {' x '.join(map(str, shape))} elements on {dev}")
+    return out
+
+
+def _consumer_ws(workspace: Workspace | None, dev, frame_offsets, index, always: bool, name: str, *args) -> torch.Tensor | None:
+    """The workspace of a call of the consumer trpx_decode_<name>, as large as its query says for args.  always: the consumer
+    has scratch of its own, so every form of the call brings one; otherwise only a form without offsets or index does (None:
+    the call needs none)."""
+    if always or frame_offsets is None or index is None:
+        return _scratch(workspace, dev, getattr(lib(), f"trpx_decode_{name}_workspace_bytes")(*args))
+    return None
+
+
+def _numel(t: torch.Tensor | None) -> int:
+    return t.numel() if t is not None else 0
 
 
 def index_bytes(dtype, n_values: int, n_frames: int, block: int = BLOCK) -> int:
@@ -305,7 +329,7 @@ def decode_sum(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
     if out is None:
         out = torch.empty((n_out, n_values), dtype=odt, device=dev)
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_sum_workspace_bytes(code, terse.numel(), n_values, n_frames, block, group))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "sum", code, terse.numel(), n_values, n_frames, block, group)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_sum(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
                                     n_values, n_frames, block, group, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -337,19 +361,13 @@ def decode_roi(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
         raise ValueError("decode_roi: boxes must live on the stack's device")
     box_h, box_w = (int(x) for x in box_shape)
     n_boxes = boxes.shape[0]
-    if out is None:
-        out = torch.empty((n_boxes, box_h, box_w), dtype=tdt, device=dev)
-    elif out.dtype != tdt or out.numel() != n_boxes * box_h * box_w or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_roi: out must be a contiguous {tdt} tensor of {n_boxes} x {box_h} x {box_w} elements on {dev}")
+    out = _out("decode_roi", out, (n_boxes, box_h, box_w), tdt, dev)
     status = _status(status, dev)
-    ws_ptr, ws_bytes = None, 0
-    if index is None or frame_offsets is None:
-        ws = _scratch(workspace, dev, lib().trpx_decode_roi_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, False, "roi", code, terse.numel(), n_values, n_frames, block)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_roi(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
                                     n_values, n_frames, block, width, boxes.data_ptr(), n_boxes, box_h, box_w, out.data_ptr(),
-                                    status.data_ptr(), ws_ptr, ws_bytes, _stream_ptr(terse)))
+                                    status.data_ptr(), _ptr(ws), _numel(ws), _stream_ptr(terse)))
     return out, status
 
 
@@ -381,7 +399,7 @@ def decode_sparse(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
     if row_offsets is None:
         row_offsets = torch.empty(n_frames + 1, dtype=torch.int64, device=dev)
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_sparse_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "sparse", code, terse.numel(), n_values, n_frames, block)
 
     def call(pos, val, cap):
         with torch.cuda.device(dev):
@@ -432,12 +450,9 @@ def decode_dot(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_values
     n_maps = weights.shape[0]
     if not 1 <= n_maps <= 16:
         raise ValueError("decode_dot: 1 to 16 maps")
-    if out is None:
-        out = torch.empty((n_frames, n_maps), dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or out.numel() != n_frames * n_maps or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_dot: out must be a contiguous int64 tensor of {n_frames} x {n_maps} elements on {dev}")
+    out = _out("decode_dot", out, (n_frames, n_maps), torch.int64, dev, "int64")
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_dot_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_maps))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "dot", code, terse.numel(), n_values, n_frames, block, n_maps)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_dot(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
                                     n_values, n_frames, block, weights.data_ptr(), n_maps, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
@@ -470,12 +485,9 @@ def decode_bins(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_value
         raise ValueError("decode_bins: labels must live on the stack's device")
     if not 1 <= n_bins <= 4096:
         raise ValueError("decode_bins: 1 to 4096 bins")
-    if out is None:
-        out = torch.empty((n_frames, n_bins), dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or out.numel() != n_frames * n_bins or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_bins: out must be a contiguous int64 tensor of {n_frames} x {n_bins} elements on {dev}")
+    out = _out("decode_bins", out, (n_frames, n_bins), torch.int64, dev, "int64")
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_bins_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_bins))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "bins", code, terse.numel(), n_values, n_frames, block, n_bins)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_bins(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
                                      n_values, n_frames, block, labels.data_ptr(), n_bins, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
@@ -508,12 +520,9 @@ def decode_hist(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_value
     if group < 1:
         raise ValueError("decode_hist: group >= 1")
     n_groups = -(-n_frames // min(group, n_frames)) if n_frames else 0
-    if out is None:
-        out = torch.empty((n_groups, n_bins), dtype=torch.int64, device=dev)     # (counts < 2^63: the uint64 of the C ABI, as int64)
-    elif out.dtype not in (torch.int64, torch.uint64) or out.numel() != n_groups * n_bins or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_hist: out must be a contiguous int64 tensor of {n_groups} x {n_bins} elements on {dev}")
+    out = _out("decode_hist", out, (n_groups, n_bins), torch.int64, dev, "int64", also=(torch.uint64,))   # (counts < 2^63: the uint64 of the C ABI, as int64)
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_hist_workspace_bytes(code, terse.numel(), n_values, n_frames, block, group, n_bins))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "hist", code, terse.numel(), n_values, n_frames, block, group, n_bins)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_hist(code, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index), n_values, n_frames, block,
                                      group, lo, shift, n_bins, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(terse)))
@@ -547,18 +556,13 @@ def decode_corrected(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_
     code = dtype_code(torch_dtype(dtype))
     dev = terse.device
     dark, gain = _map("dark", dark, n_values, dev), _map("gain", gain, n_values, dev)
-    if out is None:
-        out = torch.empty((n_frames, n_values), dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.numel() != n_frames * n_values or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_corrected: out must be a contiguous float32 tensor of {n_frames} x {n_values} elements on {dev}")
+    out = _out("decode_corrected", out, (n_frames, n_values), torch.float32, dev, "float32")
     status = _status(status, dev)
-    ws = None                                               # (offsets and index given: the call needs no workspace)
-    if frame_offsets is None or index is None:
-        ws = _scratch(workspace, dev, lib().trpx_decode_corrected_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, False, "corrected", code, terse.numel(), n_values, n_frames, block)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_corrected(code, _lib.F32, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index), n_values, n_frames,
-                                          block, _ptr(dark), _ptr(gain), out.data_ptr(), status.data_ptr(), _ptr(ws),
-                                          ws.numel() if ws is not None else 0, _stream_ptr(terse)))
+                                          block, _ptr(dark), _ptr(gain), out.data_ptr(), status.data_ptr(), _ptr(ws), _numel(ws),
+                                          _stream_ptr(terse)))
     return out, status
 
 
@@ -596,18 +600,12 @@ def decode_binned(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
     if not (1 <= bin_y <= min(height, 64) and 1 <= bin_x <= min(width, 64)):
         raise ValueError(f"decode_binned: bin {bin_y} x {bin_x} in frames of {height} x {width} (1 .. 64, within the frame)")
     out_h, out_w = -(-height // bin_y), -(-width // bin_x)
-    if out is None:
-        out = torch.empty((n_frames, out_h, out_w), dtype=odt, device=dev)
-    elif out.dtype != odt or out.numel() != n_frames * out_h * out_w or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_binned: out must be a contiguous {odt} tensor of {n_frames} x {out_h} x {out_w} elements on {dev}")
+    out = _out("decode_binned", out, (n_frames, out_h, out_w), odt, dev)
     status = _status(status, dev)
-    ws_ptr, ws_bytes = None, 0
-    if index is None or frame_offsets is None:
-        ws = _scratch(workspace, dev, lib().trpx_decode_binned_workspace_bytes(code, terse.numel(), n_values, n_frames, block))
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, False, "binned", code, terse.numel(), n_values, n_frames, block)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_binned(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
-                                       n_values, n_frames, block, width, bin_y, bin_x, out.data_ptr(), status.data_ptr(), ws_ptr, ws_bytes,
+                                       n_values, n_frames, block, width, bin_y, bin_x, out.data_ptr(), status.data_ptr(), _ptr(ws), _numel(ws),
                                        _stream_ptr(terse)))
     return out.view(n_frames, out_h, out_w), status
 
@@ -650,12 +648,9 @@ def decode_reduce(terse: torch.Tensor, frame_offsets: torch.Tensor | None, n_val
     odt = reduce_out_dtype(dtype, opc)
     dev = terse.device
     n_out = -(-n_frames // group) if group > 0 else 0
-    if out is None:
-        out = torch.empty((n_out, n_values), dtype=odt, device=dev)
-    elif out.dtype != odt or out.numel() != n_out * n_values or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_reduce: out must be a contiguous {odt} tensor of {n_out} x {n_values} elements on {dev}")
+    out = _out("decode_reduce", out, (n_out, n_values), odt, dev)
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_reduce_workspace_bytes(code, opc, terse.numel(), n_values, n_frames, block, group))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "reduce", code, opc, terse.numel(), n_values, n_frames, block, group)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_reduce(code, opc, terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index), n_values, n_frames,
                                        block, group, int(threshold), out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -689,12 +684,9 @@ def decode_sum_labelled(terse: torch.Tensor, frame_offsets: torch.Tensor | None,
         raise ValueError(f"decode_sum_labelled: labels must be a contiguous uint32 / int32 tensor of {n_frames} elements on {dev}")
     if counts is not None and (counts.dtype not in words or counts.numel() != n_out or not counts.is_contiguous() or counts.device != dev):
         raise ValueError(f"decode_sum_labelled: counts must be a contiguous uint32 / int32 tensor of {n_out} elements on {dev}")
-    if out is None:
-        out = torch.empty((max(n_out, 0), n_values), dtype=odt, device=dev)
-    elif out.dtype != odt or out.numel() != n_out * n_values or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"decode_sum_labelled: out must be a contiguous {odt} tensor of {n_out} x {n_values} elements on {dev}")
+    out = _out("decode_sum_labelled", out, (n_out, n_values), odt, dev)
     status = _status(status, dev)
-    ws = _scratch(workspace, dev, lib().trpx_decode_sum_labelled_workspace_bytes(code, terse.numel(), n_values, n_frames, block, n_out))
+    ws = _consumer_ws(workspace, dev, frame_offsets, index, True, "sum_labelled", code, terse.numel(), n_values, n_frames, block, n_out)
     with torch.cuda.device(dev):
         check(lib().trpx_decode_sum_labelled(code, _SUM_OUT[odt], terse.data_ptr(), terse.numel(), _ptr(frame_offsets), _ptr(index),
                                              n_values, n_frames, block, labels.data_ptr(), n_out, out.data_ptr(), _ptr(counts),

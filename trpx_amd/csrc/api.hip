@@ -3,7 +3,8 @@
 // device every compute entry point fails with TRPX_ERR_NO_DEVICE / TRPX_ERR_HIP.
 // Layout: predicates and routes, the one argument prologue, workspace layouts, the device-pointer ABI, the consumers of a decode
 // index behind their shared front (consumer_front), then the host staging helpers (Arena, enter, stage, finish, ...) and the
-// host-pointer wrappers built from them.
+// host-pointer wrappers built from them; those of the index consumers all go through one staged call (consumer_host), which lays
+// their inputs and outputs out as pieces of one device block.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -776,6 +777,34 @@ bool sum_out_ok(int out_dtype) {
            out_dtype == TRPX_F32 || out_dtype == TRPX_F64;
 }
 size_t sum_out_size(int out_dtype) { return out_dtype == TRPX_I32 || out_dtype == TRPX_U32 || out_dtype == TRPX_F32 ? 4 : 8; }
+// What trpx_decode_sum and trpx_decode_sum_labelled check, in an order of their own, not check_args': a 64-bit dtype is UNSUPPORTED
+// before an unknown one is INVALID_ARG (tests/test_decode_sum_args.py; tests/test_consumer_args_order.py pins every pair).  own:
+// the refusal of the consumer's own count (group / n_out), asked where it stands in that order; more: its pointers besides
+// terse, status and the sums, and words4 how the message names those of 4-byte alignment.  Fills c.g.
+template <class Own>
+int sum_checks(Consumer& c, int out_dtype, const void* sums_out, Own&& own, std::initializer_list<PtrReq> more, const char* words4) {
+    if (is64(c.dtype)) return fail(TRPX_ERR_UNSUPPORTED, "%s: no decode index for 64-bit containers", c.fn);
+    if (c.dtype < TRPX_U8 || c.dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "%s: unknown stream dtype %d", c.fn, c.dtype);
+    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "%s: out_dtype %d (I32, U32, I64, U64, F32, F64)", c.fn, out_dtype);
+    if (c.block != kBlock) return fail(TRPX_ERR_UNSUPPORTED, "%s: block=%u (the decode index needs 12)", c.fn, c.block);
+    if (trpx_dtype_is_signed(c.dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
+        return fail(TRPX_ERR_UNSUPPORTED, "%s: signed stream into an unsigned output (Terse.hpp:356-357)", c.fn);
+    if (const int rc = own()) return rc;
+    if (!geom_of(c.n_values, c.block, &c.g) || !sizes_ok(c.g, c.n_frames) || c.terse_bytes == 0 || c.n_frames > c.terse_bytes)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", c.fn, c.n_values, c.n_frames);
+    bool null = !c.terse || !sums_out || !c.status;
+    bool askew = (uintptr_t)c.terse % 4 || (uintptr_t)c.frame_offsets % 8 || (uintptr_t)c.index % 16 || (uintptr_t)c.status % 8 ||
+                 (uintptr_t)c.workspace % 8 || (uintptr_t)sums_out % sum_out_size(out_dtype);
+    for (const PtrReq& q : more) {
+        null = null || (q.required && !q.p);
+        askew = askew || (uintptr_t)q.p % q.align;
+    }
+    if (null) return fail(TRPX_ERR_INVALID_ARG, "%s: null pointer", c.fn);
+    if (c.index && !c.frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "%s: an index needs its frame offsets", c.fn);
+    if (askew)
+        return fail(TRPX_ERR_INVALID_ARG, "%s: misaligned pointer (%s 4 B, offsets / workspace 8 B, index 16 B, sums their type)", c.fn, words4);
+    return stack_limits(c);
+}
 
 // ---- box decode (decode_roi.hip): no scratch of its own ------------------------------------------------------------------------------
 // the geometry checks the device-pointer and the host-pointer entry point share (sizes from the frame: < 2^29 values, see
@@ -876,28 +905,15 @@ size_t trpx_decode_sum_workspace_bytes(int dtype, size_t terse_bytes, size_t n_v
     return front && group ? front + trpx::sum_plan(dtype, g, n_frames, group).partial_bytes : 0;
 }
 
-// (its own order of checks: a 64-bit dtype is UNSUPPORTED before an unknown one is INVALID_ARG, tests/test_decode_sum_args.py)
+// (its own order of checks: sum_checks)
 int trpx_decode_sum(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                     const void* index, size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out,
                     uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-    trpx::FrameGeom g;
-    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: no decode index for 64-bit containers");
-    if (dtype < TRPX_U8 || dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: unknown stream dtype %d", dtype);
-    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: out_dtype %d (I32, U32, I64, U64, F32, F64)", out_dtype);
-    if (block != kBlock) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: block=%u (the decode index needs 12)", block);
-    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
-        return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sum: signed stream into an unsigned output (Terse.hpp:356-357)");
-    if (group == 0) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: group = 0");
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0 || n_frames > terse_bytes)
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: bad sizes n_values=%zu n_frames=%zu", n_values, n_frames);
-    if (!terse || !sums_out || !status) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: null pointer");
-    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: an index needs its frame offsets");
-    if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 ||
-        (uintptr_t)workspace % 8 || (uintptr_t)sums_out % sum_out_size(out_dtype))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: misaligned pointer (terse 4 B, offsets / workspace 8 B, index 16 B, sums their type)");
-    const Consumer c{"trpx_decode_sum", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace,
-                     workspace_bytes, stream};
-    if (const int rc = stack_limits(c)) return rc;
+    Consumer c{"trpx_decode_sum", dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, {}, status, workspace,
+               workspace_bytes, stream};
+    const auto own = [&] { return group ? TRPX_OK : fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum: group = 0"); };
+    if (const int rc = sum_checks(c, out_dtype, sums_out, own, {}, "terse")) return rc;
+    const trpx::FrameGeom& g = c.g;
     const trpx::SumPlan p = trpx::sum_plan(dtype, g, n_frames, group);
     IndexWs w;
     if (const int rc = consumer_ws(c, p.partial_bytes, nullptr, &w)) return rc;
@@ -1277,29 +1293,18 @@ unsigned trpx_decode_sum_labelled_frames_per_chunk(int dtype, size_t n_values, s
     return trpx::labelled_plan(dtype, g, n_frames, 1).fpc;
 }
 
-// (trpx_decode_sum's order of checks, the outputs' count where its group stands)
+// (trpx_decode_sum's order of checks, sum_checks, the outputs' count where its group stands)
 int trpx_decode_sum_labelled(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                              const void* index, size_t n_values, size_t n_frames, unsigned block, const uint32_t* labels, size_t n_out,
                              void* sums_out, uint32_t* counts_out, uint32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
     const char* const fn = "trpx_decode_sum_labelled";
-    trpx::FrameGeom g;
-    if (is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "%s: no decode index for 64-bit containers", fn);
-    if (dtype < TRPX_U8 || dtype > TRPX_I32) return fail(TRPX_ERR_INVALID_ARG, "%s: unknown stream dtype %d", fn, dtype);
-    if (!sum_out_ok(out_dtype)) return fail(TRPX_ERR_INVALID_ARG, "%s: out_dtype %d (I32, U32, I64, U64, F32, F64)", fn, out_dtype);
-    if (block != kBlock) return fail(TRPX_ERR_UNSUPPORTED, "%s: block=%u (the decode index needs 12)", fn, block);
-    if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
-        return fail(TRPX_ERR_UNSUPPORTED, "%s: signed stream into an unsigned output (Terse.hpp:356-357)", fn);
-    if (n_out == 0) return fail(TRPX_ERR_INVALID_ARG, "%s: n_out = 0", fn);
-    if (!labelled_out_ok(n_out)) return fail(TRPX_ERR_UNSUPPORTED, "%s: n_out=%zu (at most 2^20)", fn, n_out);
-    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames) || terse_bytes == 0 || n_frames > terse_bytes)
-        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_values=%zu n_frames=%zu", fn, n_values, n_frames);
-    if (!terse || !labels || !sums_out || !status) return fail(TRPX_ERR_INVALID_ARG, "%s: null pointer", fn);
-    if (index && !frame_offsets) return fail(TRPX_ERR_INVALID_ARG, "%s: an index needs its frame offsets", fn);
-    if ((uintptr_t)terse % 4 || (uintptr_t)frame_offsets % 8 || (uintptr_t)index % 16 || (uintptr_t)status % 8 || (uintptr_t)workspace % 8 ||
-        (uintptr_t)labels % 4 || (uintptr_t)counts_out % 4 || (uintptr_t)sums_out % sum_out_size(out_dtype))
-        return fail(TRPX_ERR_INVALID_ARG, "%s: misaligned pointer (terse / labels / counts 4 B, offsets / workspace 8 B, index 16 B, sums their type)", fn);
-    const Consumer c{fn, dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, g, status, workspace, workspace_bytes, stream};
-    if (const int rc = stack_limits(c)) return rc;
+    Consumer c{fn, dtype, terse, terse_bytes, frame_offsets, index, n_values, n_frames, block, {}, status, workspace, workspace_bytes, stream};
+    const auto own = [&] {
+        if (n_out == 0) return fail(TRPX_ERR_INVALID_ARG, "%s: n_out = 0", fn);
+        return labelled_out_ok(n_out) ? TRPX_OK : fail(TRPX_ERR_UNSUPPORTED, "%s: n_out=%zu (at most 2^20)", fn, n_out);
+    };
+    if (const int rc = sum_checks(c, out_dtype, sums_out, own, {{labels, 4}, {counts_out, 4, false}}, "terse / labels / counts")) return rc;
+    const trpx::FrameGeom& g = c.g;
     const trpx::LabelledPlan p = trpx::labelled_plan(dtype, g, n_frames, n_out);
     IndexWs w;
     if (const int rc = consumer_ws(c, p.total, "the order of the frames lives there", &w)) return rc;
@@ -1473,7 +1478,8 @@ int trpx_select_frames(int dtype, const uint8_t* terse, size_t terse_bytes, cons
 // time, src/prolix.cpp:69-92 expands one frame at a time): a device allocation per call would cost more than the
 // codec.  Every thread keeps ONE grow-only set of device buffers per role (freed by trpx_host_release or at exit of the
 // process); the host wrappers carve their pixels / stream / offsets / status / workspace from it.  Each wrapper reads:
-// enter, validate, stage, call the device-pointer entry point, read the status, copy back.
+// enter, validate, stage, call the device-pointer entry point, read the status, copy back; the ten of the index consumers
+// validate and leave the rest to consumer_host.
 }  // extern "C"
 namespace {
 struct Arena {
@@ -1582,11 +1588,11 @@ int finish(const char* fn, hipStream_t hs, const uint32_t* d_status, uint32_t st
     return rc ? rc : status_result(fn, st);
 }
 // what the host wrappers of the index consumers refuse first (own_ok: the wrapper's own pointers and counts)
-int consumer_host_refusals(const char* fn, bool own_ok, int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block,
-                           trpx::FrameGeom* g) {
+int consumer_host_refusals(const char* fn, bool own_ok, int dtype, size_t terse_bytes, size_t n_values, size_t n_frames, unsigned block) {
+    trpx::FrameGeom g;
     if (!own_ok || !terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "%s: bad argument", fn);
     if (block != kBlock || is64(dtype)) return fail(TRPX_ERR_UNSUPPORTED, "%s: block=%u dtype=%d", fn, block, dtype);
-    if (!geom_of(n_values, block, g) || !sizes_ok(*g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes", fn);
+    if (!geom_of(n_values, block, &g) || !sizes_ok(g, n_frames)) return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes", fn);
     return TRPX_OK;
 }
 // the end of the encoding host wrappers: the offsets back, their total against the caller's room, the stream back
@@ -1709,287 +1715,240 @@ int trpx_frame_offsets_host(const uint8_t* terse, size_t terse_bytes, size_t n_v
     return TRPX_OK;
 }
 
-int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
-                         size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out, int device) {
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_sum_host", device, &hs)) return rc;
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_sum_host", terse && sums_out && sum_out_ok(out_dtype) && group, dtype, terse_bytes, n_values,
-                                              n_frames, block, &g))
-        return rc;
-    const size_t ws_bytes = trpx_decode_sum_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group);
-    if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sum_host: bad dtype/sizes");
-    const size_t out_bytes = (n_frames + group - 1) / group * n_values * sum_out_size(out_dtype);
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
+}  // extern "C"
+namespace {
+// ---- the host forms of the index consumers: one staged call -----------------------------------------------------------------------
+// A wrapper refuses what is its own (consumer_host_refusals, then its own shapes and counts), asks its workspace query and hands
+// the rest to consumer_host: the stack's limits, the device, the staging, the device-pointer call, its status, the copies back.
+// The argument checks need no device, so they come first: the same answers with and without one.
+struct HostStack { int dtype; const uint8_t* terse; size_t terse_bytes; const uint64_t* frame_offsets; size_t n_values, n_frames; unsigned block; };
+// one piece of a call's device block: uploaded from `in` (null: not), downloaded to `out` (null: not)
+struct HostPiece { const void* in; void* out; size_t bytes; };
+constexpr size_t kHostPieces = 4;
+struct HostCall { hipStream_t hs; Staged d; void* at[kHostPieces]; };
+// Everything in front of the device-pointer call.  ws_bytes: the consumer's workspace query (0: it takes no such stack).  The
+// pieces lie 16-byte aligned in the pixels slot, in the order given, c->at[i] the i-th; those with an `in` are uploaded.
+// entered: the stream of a wrapper that looked for the device first, null: the device is looked for here, behind the refusals.
+// frames_late: more frames than bytes are left to the device-pointer call, behind the device.
+int consumer_host_stage(const char* fn, int device, hipStream_t entered, const HostStack& s, size_t ws_bytes, bool frames_late,
+                        std::initializer_list<HostPiece> pieces, HostCall* c) {
+    if (!ws_bytes || (!frames_late && s.n_frames > s.terse_bytes)) return fail(TRPX_ERR_INVALID_ARG, "%s: bad dtype/sizes", fn);
+    if (!frame_bits_fit_32(s.dtype, s.n_values, s.block)) return fail(TRPX_ERR_UNSUPPORTED, "%s: frames of >= 2^32 bits", fn);
+    if (pieces.size() > kHostPieces) return fail(TRPX_ERR_INVALID_ARG, "%s: more than %zu pieces", fn, kHostPieces);
+    c->hs = entered;
+    if (!entered)
+        if (const int rc = enter(fn, device, &c->hs)) return rc;
+    size_t at[kHostPieces + 1] = {0}, n = 0;
+    for (const HostPiece& p : pieces) {
+        at[n + 1] = trpx::align_up(at[n] + p.bytes, 16);
+        ++n;
+    }
+    if (const int rc = stage(c->hs, s.terse, s.terse_bytes, s.frame_offsets, s.n_frames, s.frame_offsets != nullptr, 0, at[n], ws_bytes, &c->d)) return rc;
+    n = 0;
+    for (const HostPiece& p : pieces) {
+        c->at[n] = static_cast<char*>(c->d.out) + at[n];
+        if (p.in) HIP_TRY(copy_sync(c->hs, c->at[n], p.in, p.bytes, hipMemcpyHostToDevice));
+        ++n;
+    }
+    return TRPX_OK;
+}
+// The whole call: staged as above, call(c) -- the device-pointer entry point on c.d, c.at and c.hs --, the status read back as
+// the return code, the pieces with an `out` downloaded.
+template <class Call>
+int consumer_host(const char* fn, int device, hipStream_t entered, const HostStack& s, size_t ws_bytes, bool frames_late,
+                  std::initializer_list<HostPiece> pieces, Call&& call) {
+    HostCall c;
+    int rc = consumer_host_stage(fn, device, entered, s, ws_bytes, frames_late, pieces, &c);
     if (rc) return rc;
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_sum(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, group, d.out, d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_sum_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, sums_out, d.out, out_bytes, hipMemcpyDeviceToHost));
+    rc = call(c);
+    if (rc || (rc = finish(fn, c.hs, c.d.status, st))) return rc;
+    size_t n = 0;
+    for (const HostPiece& p : pieces) {
+        if (p.out) HIP_TRY(copy_sync(c.hs, p.out, c.at[n], p.bytes, hipMemcpyDeviceToHost));
+        ++n;
+    }
     return TRPX_OK;
+}
+}  // namespace
+extern "C" {
+
+int trpx_decode_sum_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
+                         size_t n_values, size_t n_frames, unsigned block, unsigned group, void* sums_out, int device) {
+    const char* const fn = "trpx_decode_sum_host";
+    hipStream_t hs = nullptr;
+    if (const int rc = enter(fn, device, &hs)) return rc;                     // (recorded: NO_DEVICE before every other refusal)
+    if (const int rc = consumer_host_refusals(fn, terse && sums_out && sum_out_ok(out_dtype) && group, dtype, terse_bytes, n_values, n_frames, block))
+        return rc;
+    const size_t ws_bytes = trpx_decode_sum_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group);
+    const size_t out_bytes = (n_frames + group - 1) / group * n_values * sum_out_size(out_dtype);
+    return consumer_host(fn, device, hs, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{nullptr, sums_out, out_bytes}}, [&](const HostCall& c) {
+        return trpx_decode_sum(dtype, out_dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, group, c.at[0], c.d.status,
+                               c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_roi_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                          size_t n_frames, unsigned block, size_t width, const uint32_t* boxes, size_t n_boxes, unsigned box_h,
                          unsigned box_w, void* pixels_out, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_roi_host", terse && boxes && pixels_out, dtype, terse_bytes, n_values, n_frames, block, &g))
-        return rc;
-    if (const int rc = roi_geometry("trpx_decode_roi_host", n_values, width, n_boxes, box_h, box_w)) return rc;
-    const size_t ws_bytes = trpx_decode_roi_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
-    if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad dtype/sizes");
+    const char* const fn = "trpx_decode_roi_host";
+    if (const int rc = consumer_host_refusals(fn, terse && boxes && pixels_out, dtype, terse_bytes, n_values, n_frames, block)) return rc;
+    if (const int rc = roi_geometry(fn, n_values, width, n_boxes, box_h, box_w)) return rc;
     if ((unsigned __int128)n_boxes * box_h * box_w * trpx_dtype_size(dtype) >= ((unsigned __int128)1 << 62) || n_boxes >= ((size_t)1 << 40))
-        return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: bad sizes n_boxes=%zu", n_boxes);
+        return fail(TRPX_ERR_INVALID_ARG, "%s: bad sizes n_boxes=%zu", fn, n_boxes);
     for (size_t i = 0; i < n_boxes; ++i)
         if (boxes[3 * i] >= n_frames || (uint64_t)boxes[3 * i + 1] + box_h > n_values / width || (uint64_t)boxes[3 * i + 2] + box_w > width)
-            return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_roi_host: box %zu (frame %u, y0 %u, x0 %u) leaves the stack", i, boxes[3 * i],
-                        boxes[3 * i + 1], boxes[3 * i + 2]);
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_roi_host", device, &hs)) return rc;
-    const size_t out_bytes = n_boxes * box_h * box_w * trpx_dtype_size(dtype);
-    Staged d;                                                                  // (the offsets slot: the offsets, then the boxes)
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, true, 12 * n_boxes, out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    uint32_t* d_boxes = reinterpret_cast<uint32_t*>(d.offs + (n_frames + 1));
-    HIP_TRY(copy_sync(hs, d_boxes, boxes, 12 * n_boxes, hipMemcpyHostToDevice));
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_roi(dtype, d.terse, terse_bytes, frame_offsets ? d.offs : nullptr, nullptr, n_values, n_frames, block, width, d_boxes,
-                         n_boxes, box_h, box_w, d.out, d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_roi_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, pixels_out, d.out, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+            return fail(TRPX_ERR_INVALID_ARG, "%s: box %zu (frame %u, y0 %u, x0 %u) leaves the stack", fn, i, boxes[3 * i], boxes[3 * i + 1],
+                        boxes[3 * i + 2]);
+    const size_t ws_bytes = trpx_decode_roi_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
+    // (recorded: more frames than bytes get as far as the device, and are trpx_decode_roi's to refuse)
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, true,
+                         {{boxes, nullptr, 12 * n_boxes}, {nullptr, pixels_out, n_boxes * box_h * box_w * trpx_dtype_size(dtype)}},
+                         [&](const HostCall& c) {
+        return trpx_decode_roi(dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, width, static_cast<const uint32_t*>(c.at[0]),
+                               n_boxes, box_h, box_w, c.at[1], c.d.status, c.d.ws, ws_bytes, c.hs);
+    });
 }
 
+// (its tail is its own: a capacity too small is an answer, not a failure, and what comes back depends on the total)
 int trpx_decode_sparse_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                             size_t n_frames, unsigned block, int64_t threshold, uint64_t* row_offsets, uint32_t* positions,
                             void* values, size_t capacity, size_t* n_found, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_sparse_host", terse && row_offsets && n_found, dtype, terse_bytes, n_values, n_frames, block, &g))
-        return rc;
+    const char* const fn = "trpx_decode_sparse_host";
+    if (const int rc = consumer_host_refusals(fn, terse && row_offsets && n_found, dtype, terse_bytes, n_values, n_frames, block)) return rc;
     const size_t ws_bytes = trpx_decode_sparse_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad dtype/sizes");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_sparse_host: frames of >= 2^32 bits");
-    if (const int rc = sparse_outputs("trpx_decode_sparse_host", positions, values, capacity)) return rc;
+    if (const int rc = sparse_outputs(fn, positions, values, capacity)) return rc;
     const size_t es = trpx_dtype_size(dtype);
-    if ((unsigned __int128)capacity * (4 + es) >= ((unsigned __int128)1 << 62)) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_sparse_host: bad capacity %zu", capacity);
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_sparse_host", device, &hs)) return rc;
-    // the outputs in one device block: [row_offsets] [positions] [values]
-    const size_t pos_at = trpx::align_up(8 * (n_frames + 1), 16), val_at = trpx::align_up(pos_at + 4 * capacity, 16);
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, val_at + es * capacity, ws_bytes, &d);
+    if ((unsigned __int128)capacity * (4 + es) >= ((unsigned __int128)1 << 62)) return fail(TRPX_ERR_INVALID_ARG, "%s: bad capacity %zu", fn, capacity);
+    HostCall c;                                                                // (the stage step downloads nothing: the copies back are below)
+    int rc = consumer_host_stage(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                                 {{nullptr, row_offsets, 8 * (n_frames + 1)}, {nullptr, positions, 4 * capacity}, {nullptr, values, es * capacity}}, &c);
     if (rc) return rc;
-    char* o = static_cast<char*>(d.out);
     uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_sparse(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, threshold, reinterpret_cast<uint64_t*>(o),
-                            positions ? reinterpret_cast<uint32_t*>(o + pos_at) : nullptr, positions ? o + val_at : nullptr, capacity, d.status,
-                            d.ws, ws_bytes, hs);
-    if (rc || (rc = read_status(hs, d.status, st))) return rc;
-    if (st[0] && st[0] != TRPX_ERR_CAPACITY) return status_result("trpx_decode_sparse_host", st);
-    HIP_TRY(copy_sync(hs, row_offsets, o, 8 * (n_frames + 1), hipMemcpyDeviceToHost));   // (valid when the capacity is too small, too)
+    rc = trpx_decode_sparse(dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, threshold, static_cast<uint64_t*>(c.at[0]),
+                            positions ? static_cast<uint32_t*>(c.at[1]) : nullptr, positions ? c.at[2] : nullptr, capacity, c.d.status, c.d.ws,
+                            ws_bytes, c.hs);
+    if (rc || (rc = read_status(c.hs, c.d.status, st))) return rc;
+    if (st[0] && st[0] != TRPX_ERR_CAPACITY) return status_result(fn, st);
+    HIP_TRY(copy_sync(c.hs, row_offsets, c.at[0], 8 * (n_frames + 1), hipMemcpyDeviceToHost));   // (valid when the capacity is too small, too)
     const size_t total = (size_t)row_offsets[n_frames];
     *n_found = total;
-    if (st[0]) return fail(TRPX_ERR_CAPACITY, "trpx_decode_sparse_host: %zu events, capacity %zu", total, capacity);
+    if (st[0]) return fail(TRPX_ERR_CAPACITY, "%s: %zu events, capacity %zu", fn, total, capacity);
     if (total) {
-        HIP_TRY(copy_sync(hs, positions, o + pos_at, 4 * total, hipMemcpyDeviceToHost));
-        HIP_TRY(copy_sync(hs, values, o + val_at, es * total, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(c.hs, positions, c.at[1], 4 * total, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_sync(c.hs, values, c.at[2], es * total, hipMemcpyDeviceToHost));
     }
     return TRPX_OK;
 }
 
 int trpx_decode_dot_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                          size_t n_frames, unsigned block, const int32_t* weights, unsigned n_maps, int64_t* dots_out, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_dot_host", terse && weights && dots_out && dot_maps_ok(n_maps), dtype, terse_bytes, n_values,
-                                              n_frames, block, &g))
+    const char* const fn = "trpx_decode_dot_host";
+    if (const int rc = consumer_host_refusals(fn, terse && weights && dots_out && dot_maps_ok(n_maps), dtype, terse_bytes, n_values, n_frames, block))
         return rc;
     const size_t ws_bytes = trpx_decode_dot_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_maps);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_dot_host: bad dtype/sizes");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_dot_host: frames of >= 2^32 bits");
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_dot_host", device, &hs)) return rc;
-    // the maps and the sums in one device block: [weights] [dots]
-    const size_t w_bytes = 4 * (size_t)n_maps * n_values, out_at = trpx::align_up(w_bytes, 16), out_bytes = 8 * n_frames * (size_t)n_maps;
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_at + out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    char* o = static_cast<char*>(d.out);
-    HIP_TRY(copy_sync(hs, o, weights, w_bytes, hipMemcpyHostToDevice));
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_dot(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const int32_t*>(o), n_maps,
-                         reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_dot_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, dots_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{weights, nullptr, 4 * (size_t)n_maps * n_values}, {nullptr, dots_out, 8 * n_frames * (size_t)n_maps}},
+                         [&](const HostCall& c) {
+        return trpx_decode_dot(dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, static_cast<const int32_t*>(c.at[0]), n_maps,
+                               static_cast<int64_t*>(c.at[1]), c.d.status, c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_bins_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                           size_t n_frames, unsigned block, const uint16_t* labels, unsigned n_bins, int64_t* bins_out, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_bins_host", terse && labels && bins_out && bins_count_ok(n_bins), dtype, terse_bytes, n_values,
-                                              n_frames, block, &g))
+    const char* const fn = "trpx_decode_bins_host";
+    if (const int rc = consumer_host_refusals(fn, terse && labels && bins_out && bins_count_ok(n_bins), dtype, terse_bytes, n_values, n_frames, block))
         return rc;
     const size_t ws_bytes = trpx_decode_bins_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_bins);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_bins_host: bad dtype/sizes");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_bins_host: frames of >= 2^32 bits");
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_bins_host", device, &hs)) return rc;
-    // the map and the sums in one device block: [labels] [bins]
-    const size_t l_bytes = 2 * n_values, out_at = trpx::align_up(l_bytes, 16), out_bytes = 8 * n_frames * (size_t)n_bins;
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_at + out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    char* o = static_cast<char*>(d.out);
-    HIP_TRY(copy_sync(hs, o, labels, l_bytes, hipMemcpyHostToDevice));
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_bins(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const uint16_t*>(o), n_bins,
-                          reinterpret_cast<int64_t*>(o + out_at), d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_bins_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, bins_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{labels, nullptr, 2 * n_values}, {nullptr, bins_out, 8 * n_frames * (size_t)n_bins}}, [&](const HostCall& c) {
+        return trpx_decode_bins(dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, static_cast<const uint16_t*>(c.at[0]), n_bins,
+                                static_cast<int64_t*>(c.at[1]), c.d.status, c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_hist_host(int dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                           size_t n_frames, unsigned block, size_t group, int64_t lo, unsigned shift, unsigned n_bins, uint64_t* hist_out,
                           int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_hist_host", terse && hist_out && group && trpx::hist_args_ok(lo, shift, n_bins), dtype,
-                                              terse_bytes, n_values, n_frames, block, &g))
+    const char* const fn = "trpx_decode_hist_host";
+    if (const int rc = consumer_host_refusals(fn, terse && hist_out && group && trpx::hist_args_ok(lo, shift, n_bins), dtype, terse_bytes, n_values,
+                                              n_frames, block))
         return rc;
     const size_t ws_bytes = trpx_decode_hist_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, group, n_bins);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_hist_host: bad dtype/sizes");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_hist_host: frames of >= 2^32 bits");
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_hist_host", device, &hs)) return rc;
     const size_t frames = std::min(group, n_frames), out_bytes = 8 * ((n_frames + frames - 1) / frames) * (size_t)n_bins;
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_hist(dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, group, lo, shift, n_bins,
-                          static_cast<uint64_t*>(d.out), d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_hist_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, hist_out, d.out, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{nullptr, hist_out, out_bytes}}, [&](const HostCall& c) {
+        return trpx_decode_hist(dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, group, lo, shift, n_bins,
+                                static_cast<uint64_t*>(c.at[0]), c.d.status, c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_corrected_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                                size_t n_values, size_t n_frames, unsigned block, const float* dark, const float* gain, void* out, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_corrected_host", terse && out, dtype, terse_bytes, n_values, n_frames, block, &g))
-        return rc;
-    if (out_dtype != TRPX_F32) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_corrected_host: out_dtype %d (F32)", out_dtype);
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_corrected_host: frames of >= 2^32 bits");
+    const char* const fn = "trpx_decode_corrected_host";
+    if (const int rc = consumer_host_refusals(fn, terse && out, dtype, terse_bytes, n_values, n_frames, block)) return rc;
+    if (out_dtype != TRPX_F32) return fail(TRPX_ERR_UNSUPPORTED, "%s: out_dtype %d (F32)", fn, out_dtype);
+    // (its workspace query answers 0 for such frames as well: asked first, they stay UNSUPPORTED)
+    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "%s: frames of >= 2^32 bits", fn);
     const size_t ws_bytes = trpx_decode_corrected_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
-    if (!ws_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_corrected_host: bad dtype/sizes");
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_corrected_host", device, &hs)) return rc;
-    // the maps and the frames in one device block: [dark] [gain] [out]
-    const size_t map_bytes = trpx::align_up(4 * n_values, 16), out_bytes = 4 * n_frames * n_values;
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, 2 * map_bytes + out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    char* o = static_cast<char*>(d.out);
-    if (dark) HIP_TRY(copy_sync(hs, o, dark, 4 * n_values, hipMemcpyHostToDevice));
-    if (gain) HIP_TRY(copy_sync(hs, o + map_bytes, gain, 4 * n_values, hipMemcpyHostToDevice));
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_corrected(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block,
-                               dark ? reinterpret_cast<const float*>(o) : nullptr, gain ? reinterpret_cast<const float*>(o + map_bytes) : nullptr,
-                               o + 2 * map_bytes, d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_corrected_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, out, o + 2 * map_bytes, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{dark, nullptr, 4 * n_values}, {gain, nullptr, 4 * n_values}, {nullptr, out, 4 * n_frames * n_values}},
+                         [&](const HostCall& c) {
+        return trpx_decode_corrected(dtype, out_dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block,
+                                     dark ? static_cast<const float*>(c.at[0]) : nullptr, gain ? static_cast<const float*>(c.at[1]) : nullptr, c.at[2],
+                                     c.d.status, c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_binned_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                             size_t n_values, size_t n_frames, unsigned block, size_t width, unsigned bin_y, unsigned bin_x,
                             void* binned_out, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_binned_host", terse && binned_out, dtype, terse_bytes, n_values, n_frames, block, &g))
-        return rc;
+    const char* const fn = "trpx_decode_binned_host";
+    if (const int rc = consumer_host_refusals(fn, terse && binned_out, dtype, terse_bytes, n_values, n_frames, block)) return rc;
+    if (const int rc = binned_geometry(fn, dtype, out_dtype, n_values, width, bin_y, bin_x)) return rc;
     const size_t ws_bytes = trpx_decode_binned_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_binned_host: bad dtype/sizes");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_binned_host: frames of >= 2^32 bits");
-    if (const int rc = binned_geometry("trpx_decode_binned_host", dtype, out_dtype, n_values, width, bin_y, bin_x)) return rc;
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_binned_host", device, &hs)) return rc;
-    const trpx::BinnedGeom geo = trpx::binned_geom((uint32_t)n_values, (uint32_t)width, bin_y, bin_x);
-    const size_t out_bytes = n_frames * (size_t)geo.out_h * geo.out_w * sum_out_size(out_dtype);
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_binned(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, width, bin_y, bin_x, d.out,
-                            d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_binned_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, binned_out, d.out, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    const size_t out_h = (n_values / width + bin_y - 1) / bin_y, out_w = (width + bin_x - 1) / bin_x;
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{nullptr, binned_out, n_frames * out_h * out_w * sum_out_size(out_dtype)}}, [&](const HostCall& c) {
+        return trpx_decode_binned(dtype, out_dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, width, bin_y, bin_x, c.at[0],
+                                  c.d.status, c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_reduce_host(int dtype, int op, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets, size_t n_values,
                             size_t n_frames, unsigned block, unsigned group, int64_t threshold, void* out, int device) {
-    // (the argument checks need no device: they come first)
-    trpx::FrameGeom g;
-    if (const int rc = consumer_host_refusals("trpx_decode_reduce_host", terse && out && reduce_op_ok(op) && group, dtype, terse_bytes, n_values,
-                                              n_frames, block, &g))
-        return rc;
+    const char* const fn = "trpx_decode_reduce_host";
+    if (const int rc = consumer_host_refusals(fn, terse && out && reduce_op_ok(op) && group, dtype, terse_bytes, n_values, n_frames, block)) return rc;
     const size_t ws_bytes = trpx_decode_reduce_workspace_bytes(dtype, op, terse_bytes, n_values, n_frames, block, group);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "trpx_decode_reduce_host: bad dtype/sizes");
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "trpx_decode_reduce_host: frames of >= 2^32 bits");
-    hipStream_t hs = nullptr;
-    if (const int rc = enter("trpx_decode_reduce_host", device, &hs)) return rc;
     const size_t out_bytes = (n_frames + group - 1) / group * n_values * trpx::reduce_out_size(op, trpx_dtype_size(dtype));
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, out_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_reduce(dtype, op, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, group, threshold, d.out, d.status, d.ws,
-                            ws_bytes, hs);
-    if (rc || (rc = finish("trpx_decode_reduce_host", hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, out, d.out, out_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{nullptr, out, out_bytes}}, [&](const HostCall& c) {
+        return trpx_decode_reduce(dtype, op, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block, group, threshold, c.at[0], c.d.status,
+                                  c.d.ws, ws_bytes, c.hs);
+    });
 }
 
 int trpx_decode_sum_labelled_host(int dtype, int out_dtype, const uint8_t* terse, size_t terse_bytes, const uint64_t* frame_offsets,
                                   size_t n_values, size_t n_frames, unsigned block, const uint32_t* labels, size_t n_out, void* sums_out,
                                   uint32_t* counts_out, int device) {
-    // (the argument checks need no device: they come first)
     const char* const fn = "trpx_decode_sum_labelled_host";
-    trpx::FrameGeom g;
     if (const int rc = consumer_host_refusals(fn, terse && labels && sums_out && sum_out_ok(out_dtype) && n_out, dtype, terse_bytes, n_values, n_frames,
-                                              block, &g))
+                                              block))
         return rc;
     if (!labelled_out_ok(n_out)) return fail(TRPX_ERR_UNSUPPORTED, "%s: n_out=%zu (at most 2^20)", fn, n_out);
     if (trpx_dtype_is_signed(dtype) && (out_dtype == TRPX_U32 || out_dtype == TRPX_U64))
         return fail(TRPX_ERR_UNSUPPORTED, "%s: signed stream into an unsigned output (Terse.hpp:356-357)", fn);
     const size_t ws_bytes = trpx_decode_sum_labelled_workspace_bytes(dtype, terse_bytes, n_values, n_frames, block, n_out);
-    if (!ws_bytes || n_frames > terse_bytes) return fail(TRPX_ERR_INVALID_ARG, "%s: bad dtype/sizes", fn);
-    if (!frame_bits_fit_32(dtype, n_values, block)) return fail(TRPX_ERR_UNSUPPORTED, "%s: frames of >= 2^32 bits", fn);
-    hipStream_t hs = nullptr;
-    if (const int rc = enter(fn, device, &hs)) return rc;
-    // the labels, the sums and the counts in one device block: [labels] [sums] [counts]
-    const size_t l_bytes = 4 * n_frames, out_at = trpx::align_up(l_bytes, 16), out_bytes = n_out * n_values * sum_out_size(out_dtype);
-    const size_t counts_at = out_at + trpx::align_up(out_bytes, 8), counts_bytes = 4 * n_out;
-    Staged d;
-    int rc = stage(hs, terse, terse_bytes, frame_offsets, n_frames, frame_offsets != nullptr, 0, counts_at + counts_bytes, ws_bytes, &d);
-    if (rc) return rc;
-    char* o = static_cast<char*>(d.out);
-    HIP_TRY(copy_sync(hs, o, labels, l_bytes, hipMemcpyHostToDevice));
-    uint32_t st[TRPX_STATUS_WORDS];
-    rc = trpx_decode_sum_labelled(dtype, out_dtype, d.terse, terse_bytes, d.offs, nullptr, n_values, n_frames, block, reinterpret_cast<const uint32_t*>(o),
-                                  n_out, o + out_at, reinterpret_cast<uint32_t*>(o + counts_at), d.status, d.ws, ws_bytes, hs);
-    if (rc || (rc = finish(fn, hs, d.status, st))) return rc;
-    HIP_TRY(copy_sync(hs, sums_out, o + out_at, out_bytes, hipMemcpyDeviceToHost));
-    if (counts_out) HIP_TRY(copy_sync(hs, counts_out, o + counts_at, counts_bytes, hipMemcpyDeviceToHost));
-    return TRPX_OK;
+    // (the counts are made on the device whether the caller wants them or not)
+    return consumer_host(fn, device, nullptr, {dtype, terse, terse_bytes, frame_offsets, n_values, n_frames, block}, ws_bytes, false,
+                         {{labels, nullptr, 4 * n_frames}, {nullptr, sums_out, n_out * n_values * sum_out_size(out_dtype)}, {nullptr, counts_out, 4 * n_out}},
+                         [&](const HostCall& c) {
+        return trpx_decode_sum_labelled(dtype, out_dtype, c.d.terse, terse_bytes, c.d.offs, nullptr, n_values, n_frames, block,
+                                        static_cast<const uint32_t*>(c.at[0]), n_out, c.at[1], static_cast<uint32_t*>(c.at[2]), c.d.status, c.d.ws, ws_bytes,
+                                        c.hs);
+    });
 }
 
 int trpx_encode_sparse_host(int dtype, const uint64_t* row_offsets, const uint32_t* positions, const void* values, size_t n_events,
